@@ -20,9 +20,18 @@ of the communicator the timed steps used, 0 for the host transport).  Corpus and
 in HBM before the timed region (the reference also times only its query loop,
 gip_retrieval.py:107,161-163).
 
-The default invocation (N=1, config 3) also times 5 steps each of config 2 (dense-only) and config 1
-(BM25, 100 k rows) and attaches them as `other_configs` to the same JSON line, and 3 steps each of the
-two-stage modes of the reference's docs on the resident config-3 index (`two_stage`).
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the
+outputs of the last timed step if --dump-outputs DIR is given, the JSON line.  Everything else is behind
+--full: the CPU baseline, the oracle check of a corpus slice (N>1: the property check of the sharded
+result), the device-resident and kernel-alone side figures, and for the default hybrid workload (N=1,
+config 3) 5 steps each of config 2 (dense-only) and config 1 (BM25, 100 k rows) attached as
+`other_configs` and 3 steps each of the two-stage modes of the reference's docs on the resident
+config-3 index (`two_stage`).
+
+--dump-outputs DIR writes the result lists of the last timed step as the caller receives them on the host
+(DIR/scores.npy float32 [Q, k], DIR/rows.npy global row numbers, float32 while they are exact there,
+else float64); over 64 MB in all, a fixed seeded sample of the queries (DIR/query_index.npy).  The
+inputs are generated from --seed, so the same arguments give the same inputs on every run.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md section "Measurement" for the field definitions.
 """
@@ -47,6 +56,7 @@ MFMA_PEAK_TFLOPS = 2500.0      # dense fp16/bf16 MFMA peak, MI355X_MICROARCH.md 
 MFMA_PEAK_I8_TOPS = 5000.0     # dense int8 MFMA peak (same table): the ungated columns of a dense_i8 index run on it
 SMFMAC_I8_PEAK_TOPS = 6650.0   # v_smfmac_i32_32x32x64_i8, logical (2 bucket columns per slice): 48 cycles per issue measured with zero operands (profiles/r03_smfmac8_probe.txt)
 GEN_CHUNK = 1 << 18            # the synthetic corpus is seeded per GLOBAL chunk of this many rows: a shard of any world size is a slice of the same corpus
+OUTPUT_BUDGET = 64_000_000     # bytes --dump-outputs may write in all
 
 # BASELINE.json config 5: the 13 public BEIR corpora (documents, test queries), sizes from the public BEIR table
 BEIR = [("trec-covid", 171_332, 50), ("nfcorpus", 3_633, 323), ("nq", 2_681_468, 3_452), ("hotpotqa", 5_233_329, 7_405),
@@ -130,11 +140,36 @@ def cpu_baseline_legs(sample, k, n_full, q_one, q_all):
                     "barely faster than one thread, as measured"}
 
 
-def main():
+def dump_outputs(out_dir, arrays, budget=OUTPUT_BUDGET, seed=0):
+    """--dump-outputs: name -> host array [Q, ...] (float32 / float64, one row per query) as out_dir/<name>.npy.  When they would
+    take more than `budget` bytes, the same fixed seeded sample of the queries is written of every array, and the query numbers
+    of the sample as <prefix>query_index.npy.  -> a summary for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    nq = next(iter(arrays.values())).shape[0]
+    per_query = sum(a.nbytes // max(a.shape[0], 1) for a in arrays.values())
+    sel = None
+    if per_query * nq > budget:
+        m = min(nq, budget // (per_query + 8))          # (+ 8: the float64 query number of each sampled query)
+        if m < 1:
+            raise SystemExit("--dump-outputs: one query's outputs alone exceed %d bytes" % budget)
+        sel = np.sort(np.random.default_rng(seed).choice(nq, m, replace=False))
+        prefix = os.path.commonprefix(list(arrays))
+        arrays = {**{name: a[sel] for name, a in arrays.items()}, prefix + "query_index": sel.astype(np.float64)}
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "queries": nq if sel is None else int(sel.size), "of_queries": nq}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: CPU baseline, oracle / property check, "
+                                                        "device-resident and kernel-alone side figures, and for the default hybrid workload two_stage and other_configs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write the result lists of the last one as DIR/<name>.npy "
+                                                                     "(float32 / float64, at most 64 MB in all: a fixed seeded sample of the queries beyond that)")
     ap.add_argument("--workload", default="hybrid", choices=["hybrid", "dense", "bm25", "beir"],
                     help="hybrid = config 3 / 4 (768 DLR + 768 dense, 8.84 M rows); dense = config 2 (768 dense, no index array); "
                          "bm25 = config 1 (100 k rows, DLR only, int16 whole-word slice index); beir = config 5 sweep (13 corpus sizes, "
@@ -175,16 +210,23 @@ def main():
     ap.add_argument("--parity-queries", type=int, default=24)
     ap.add_argument("--seed", type=int, default=1237)
     ap.add_argument("--rccl-timeout", type=float, default=300.0, help="N > 1: seconds the bring-up of the library's RCCL communicator (incl. one untimed sharded step) may take before every rank degrades to the host transport")
-    ap.add_argument("--two-stage", type=int, default=-1, help="1: after the timed steps also time 3 steps each of the two-stage modes of the reference's docs on the resident index (--theta 0.3 --rerank and --IP --rerank, agip_topk 10000) and attach them as two_stage (default: on for the plain N=1 hybrid invocation)")
-    ap.add_argument("--other-configs", type=int, default=-1, help="1: after the headline workload also time 5 steps each of config 2 (dense) and config 1 (bm25) and attach them as other_configs (default: on for the plain N=1 hybrid invocation)")
+    ap.add_argument("--two-stage", type=int, default=-1, help="1: after the timed steps also time 3 steps each of the two-stage modes of the reference's docs on the resident index (--theta 0.3 --rerank and --IP --rerank, agip_topk 10000) and attach them as two_stage (default: on for the default N=1 hybrid invocation with --full)")
+    ap.add_argument("--other-configs", type=int, default=-1, help="1: after the headline workload also time 5 steps each of config 2 (dense) and config 1 (bm25) and attach them as other_configs (default: on for the default N=1 hybrid invocation with --full)")
     ap.add_argument("--data", default="iid", choices=["iid", "clustered"], help="dense columns: iid Gaussian (SURVEY 8d) or the structured variant (2 000 clusters, decaying spectrum, 1 %% near-duplicate rows, 5 %% hot queries)")
     ap.add_argument("--per-step", action="store_true", help="diagnostics: attach the library's own total_ms of every timed step (per_step_total_ms) -- a slow step among fast ones is a host-side stall, not kernel time")
     ap.add_argument("--dist-backend", default="nccl", help="testing only: 'gloo' lets several ranks share ONE GPU (with DHR_BENCH_SINGLE_DEVICE=1)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.quick:
         args.cpu_queries, args.cpu_queries_1t = min(args.cpu_queries, 8), min(args.cpu_queries_1t, 4)
     if bool(args.index_path) != bool(args.query_path):
         raise SystemExit("--index-path and --query-path go together")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     from dhr_amd import _lib, dist as D, synth
@@ -207,11 +249,11 @@ def main():
 
     ctx = dict(torch=torch, _lib=_lib, D=D, synth=synth, world=world, rank=rank, local_rank=local_rank, device=device)
     if args.workload == "beir":
-        for name, n_docs, n_q in BEIR:
-            if args.beir_only and name != args.beir_only:
-                continue
+        corpora = [c for c in BEIR if not args.beir_only or c[0] == args.beir_only]
+        for name, n_docs, n_q in corpora:
             spec = dict(name="beir/" + name, n=args.n_docs or n_docs, nq=args.n_queries or n_q, d_dlr=768, d_cls=128, kind="encoder",
-                        baseline_config="config 5: DeLADE-CLS-P on BEIR-13 (%s)" % name, seed=args.seed + 5 + (zlib.crc32(name.encode()) % 997))
+                        baseline_config="config 5: DeLADE-CLS-P on BEIR-13 (%s)" % name, seed=args.seed + 5 + (zlib.crc32(name.encode()) % 997),
+                        dump_prefix="beir_%s_" % name, dump_budget=OUTPUT_BUDGET // len(corpora))
             out = run_workload(args, spec, ctx)
             if rank == 0:
                 print(json.dumps(out), flush=True)
@@ -231,17 +273,17 @@ def main():
                 raise SystemExit("the real-data leg runs on one GPU (--gpus 1)")
             spec = load_real(args, torch)
         out = run_workload(args, spec, ctx)
-        # configs 1 and 2 on the same clock: the plain default invocation (N = 1, config 3 at full size) also times 5 steps each of the
+        # configs 1 and 2 on the same clock: the default invocation with --full (N = 1, config 3 at full size) also times 5 steps each of the
         # dense-only and the BM25 workload -- same code path, same seed rule, their own roofline and checksum -- and attaches them to the line
         plain = (args.workload == "hybrid" and not args.index_path and world == 1 and not args.n_docs and not args.n_queries and not args.uniform_idx and args.data == "iid"
                  and not args.pq and args.topk == 1000)
-        if (args.other_configs == 1 or (args.other_configs < 0 and plain)) and world == 1 and args.workload == "hybrid":
+        if (args.other_configs == 1 or (args.other_configs < 0 and plain and args.full)) and world == 1 and args.workload == "hybrid":
             import copy
             other = {}
             for wl, tag in (("dense", "config2"), ("bm25", "config1")):
                 a2 = copy.copy(args)
                 a2.workload, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.n_docs, a2.n_queries = wl, 5, 2, True, 0, 0
-                a2.two_stage = 0
+                a2.two_stage, a2.dump_outputs = 0, ""
                 o = run_workload(a2, specs[wl], ctx)
                 if rank == 0:
                     other[tag] = {key: o[key] for key in ("value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "roofline", "whole_job_frac_of_gemm_roofline",
@@ -335,9 +377,9 @@ def run_workload(args, spec, ctx):
     elif args.progressive_thr >= 0:
         index.set_param(_lib.PARAM_PROGRESSIVE_THR, args.progressive_thr)
 
-    # host samples for the CPU baseline and the in-bench parity check (rank 0, N=1 only; BEFORE the corpus tensors are dropped)
+    # host samples for the CPU baseline and the in-bench parity check (--full, rank 0, N=1 only; BEFORE the corpus tensors are dropped)
     cpu_sample = par_sample = None
-    if rank == 0 and world == 1 and cv is not None:
+    if args.full and rank == 0 and world == 1 and cv is not None:
         def host_slice(m, mq):
             m, mq = min(m, hi - lo), min(mq, nq)
             return (cv[:m].cpu().numpy(), None if ci is None else ci[:m].cpu().numpy(), qv[:mq].cpu().numpy(), None if qi is None else qi[:mq].cpu().numpy())
@@ -464,15 +506,26 @@ def run_workload(args, spec, ctx):
     ms_per_step = elapsed * 1e3 / args.steps
     qps = nq * args.steps / elapsed
 
+    # the result lists of the last timed step as the caller holds them (pinned host copies, complete after the closing barrier)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        rows_dtype = np.float32 if n <= 1 << 24 else np.float64          # row numbers stay exact
+        pre = spec.get("dump_prefix", "")
+        outputs = dump_outputs(args.dump_outputs, {pre + "scores": host_s.numpy(), pre + "rows": host_r.numpy().astype(rows_dtype)},
+                               spec.get("dump_budget", OUTPUT_BUDGET))
+
     checksum = result_checksum(torch, gs[:, :kk], gr[:, :kk])
-    # side figure: the same K steps with the lists left in device memory (what a caller that consumes them on the GPU sees)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    ms_device_resident = (time.perf_counter() - t1) * 1e3 / args.steps
-    if not stats_in_timed:
+    # side figure (--full): the same K steps with the lists left in device memory (what a caller that consumes them on the GPU sees)
+    ms_device_resident = None
+    if args.full:
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        ms_device_resident = (time.perf_counter() - t1) * 1e3 / args.steps
+    have_stats = stats_in_timed or args.full
+    if not stats_in_timed and args.full:
         index.set_param(_lib.PARAM_PROFILE, 1)
         for _ in range(args.steps):
             step()
@@ -480,11 +533,11 @@ def run_workload(args, spec, ctx):
         barrier()
     gemm_ms, gemm_flops_alg, launches = acc["gemm_ms"], acc["gemm_flops_alg"], acc["launches"]
 
-    # side figure 2 (N = 1): the bound GEMM ALONE.  In the timed steps refine / rescoring / select of a chunk run beside the next chunk's GEMM
+    # side figure 2 (--full, N = 1): the bound GEMM ALONE.  In the timed steps refine / rescoring / select of a chunk run beside the next chunk's GEMM
     # (library default since round 4), so the GEMM's launch durations there include what it loses to the gathers; two extra steps with
     # DHR_PARAM_OVERLAP_AUX = 0 time the same launches with the chip to themselves (roofline.achieved; the timed region's own figure beside it)
     serial = None
-    if world == 1 and pq is None and args.overlap_aux < 0:
+    if args.full and world == 1 and pq is None and args.overlap_aux < 0:
         index.set_param(_lib.PARAM_OVERLAP_AUX, 0)
         step()
         s_ms = s_fl = 0.0
@@ -499,12 +552,12 @@ def run_workload(args, spec, ctx):
                   "ms_per_step": (time.perf_counter() - t2) * 1e3 / 3}
         index.set_param(_lib.PARAM_OVERLAP_AUX, -1)
 
-    # side figure 3 (N = 1, hybrid): the two-stage modes every doc page of the reference recommends (gip_retrieval.py:128-156;
+    # side figure 3 (--full, N = 1, hybrid): the two-stage modes every doc page of the reference recommends (gip_retrieval.py:128-156;
     # docs/dhr/msmarco-passage-train-eval.md:114-125), both stages on the device (dhr_search_rerank), agip_topk 10 000 -> top-k, result lists on the host
     index_device_bytes = index.device_bytes()          # (before the two-stage leg: agip_topk 10 000 grows the workspace)
     two_stage = None
     plain_hybrid = (spec["name"] == "hybrid" and world == 1 and pq is None and not args.n_docs and not args.n_queries and not args.uniform_idx and args.topk == 1000)
-    if spec["name"] == "hybrid" and world == 1 and pq is None and (args.two_stage == 1 or (args.two_stage < 0 and plain_hybrid and args.data == "iid")):
+    if spec["name"] == "hybrid" and world == 1 and pq is None and (args.two_stage == 1 or (args.two_stage < 0 and args.full and plain_hybrid and args.data == "iid")):
         q32 = qv.float()
         k1 = min(args.agip_topk, n)
         two_stage = {"agip_topk": k1, "topk": min(k, k1), "steps": 3}
@@ -519,11 +572,11 @@ def run_workload(args, spec, ctx):
                                "result_checksum": {"rows": int(((r2.astype(np.int64) + 1) * (np.arange(r2.shape[1], dtype=np.int64) + 1)[None, :]).sum() & ((1 << 62) - 1))}}
         del q32
 
-    # ---- N > 1: size-independent checks of the sharded result, outside the timed region (the oracle cannot hold the
+    # ---- --full, N > 1: size-independent checks of the sharded result, outside the timed region (the oracle cannot hold the
     # corpus): sorted lists of distinct rows; every returned score is the exact score of its row on the rank that holds
     # the row (dhr_score_rows, an independent code path); no sampled row of any shard outside a list beats its k-th score
     dist_check = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         ds = gs[:, 1:] - gs[:, :-1]
         ok_sorted = bool((ds <= 0).all()) and bool((gr[:, 1:][ds == 0] > gr[:, :-1][ds == 0]).all())
@@ -620,19 +673,27 @@ def run_workload(args, spec, ctx):
                          "avg_launch_ms_kernel_alone": round(serial["gemm_ms_per_step"] * 3 / max(serial["launches"], 1), 3) if serial else None,
                          "alg_flops_per_step": gemm_flops_alg / args.steps},
             "whole_job_frac_of_gemm_roofline": round(qps * 2.0 * n * K / (peak * 1e12 * world), 4),
-            "device_resident": {"ms_per_step": round(ms_device_resident, 3), "queries_per_s": round(nq / (ms_device_resident * 1e-3), 1),
-                                "note": "the same steps with the result lists left in device memory"},
+            **({"device_resident": {"ms_per_step": round(ms_device_resident, 3), "queries_per_s": round(nq / (ms_device_resident * 1e-3), 1),
+                                    "note": "the same steps with the result lists left in device memory"}} if ms_device_resident is not None else {}),
             "result_checksum": checksum,
             "phase_ms_per_step": {key: round(v / args.steps, 3) for key, v in stats_acc.items() if key.endswith("_ms")}
                                  | {"gemm_ms": round(gemm_ms / args.steps, 3)},
-            "candidates_per_query": {"bound": round(stats_acc["candidates_bound"] / args.steps / nq, 1),
-                                     "exact": round(stats_acc["candidates_exact"] / args.steps / nq, 1)},
+            "candidates_per_query": {"bound": round(stats_acc.get("candidates_bound", 0) / args.steps / nq, 1),
+                                     "exact": round(stats_acc.get("candidates_exact", 0) / args.steps / nq, 1)},
             **({"per_step_total_ms": acc.get("total_by_step", [])} if args.per_step else {}),
-            "sample_fallback_queries_per_step": stats_acc["sample_fallback_queries"] / args.steps,
-            "overflow_retries_per_step": stats_acc["overflow_retries"] / args.steps,
+            "sample_fallback_queries_per_step": stats_acc.get("sample_fallback_queries", 0) / args.steps,
+            "overflow_retries_per_step": stats_acc.get("overflow_retries", 0) / args.steps,
             "setup_s": {"generate": round(t_gen, 2), "index_build": round(t_build, 2)},
             "index_device_gb": round(index_device_bytes / 1e9, 2),
         }
+        if not have_stats:
+            # N > 1 without --full: the timed steps ran without the kernel timers and no profiled steps followed -- no kernel figures
+            for key in ("achieved", "frac", "frac_of_instruction_mix_peak", "traffic", "algorithmic_bytes_per_launch", "launches", "avg_launch_ms", "alg_flops_per_step"):
+                out["roofline"][key] = None
+            out["roofline"]["achieved_note"] = "the kernel timers cost a sharded step a host synchronisation: --full adds %d profiled, untimed steps for these figures" % args.steps
+            out["phase_ms_per_step"] = out["candidates_per_query"] = out["sample_fallback_queries_per_step"] = out["overflow_retries_per_step"] = None
+        if outputs is not None:
+            out["outputs"] = outputs
         if two_stage is not None:
             out["two_stage"] = two_stage
         if real is not None and args.qrels:

@@ -1932,12 +1932,12 @@ def test_random_mode_configurations(G, monkeypatch):
 def test_bench_two_ranks_share_one_gpu():
     """bench.py's N>1 path end to end (torch.distributed.run, staged sharded search, collectives, JSON line) with two
     ranks on ONE GPU over gloo (DHR_BENCH_SINGLE_DEVICE=1, testing mode); the line must carry the contract's fields
-    and bench.py's own oracle check of a corpus slice must have passed (it raises otherwise)."""
+    and bench.py's own property check of the sharded result (--full) must have passed (it raises otherwise)."""
     import json, os, subprocess, sys
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     env = dict(os.environ, DHR_BENCH_SINGLE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--dist-backend", "gloo",
+           "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--dist-backend", "gloo",
            "--n-docs", "700000", "--n-queries", "512"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -1947,6 +1947,45 @@ def test_bench_two_ranks_share_one_gpu():
     assert j["config"]["parallelism"] == "rowshard2+allgather"
     pc = j["parity_check"]                               # the sharded result's property check ran on both ranks
     assert pc["sorted"] and pc["distinct_rows"] and pc["scores_equal_exact_rescoring"] and pc["rows_beating_kth_outside_list"] == 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain bench run (no --full) times its steps and does nothing the headline figure does not need; --dump-outputs writes the host
+    result lists of the last timed step.  The lists are the exact top-k of bench.py's own seeded inputs (regenerated here with
+    bench.gen_rows, checked against the float64 oracle), and a second run with another --steps writes the same arrays."""
+    import json, os, subprocess, sys
+    import torch
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    n, nq, k = 60_000, 48, 100
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / ("out%d" % steps)
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--n-docs", str(n), "--n-queries", str(nq),
+               "--topk", str(k), "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "queries/s" and j["higher_is_better"] is True
+        assert j["metric"].startswith("queries/sec") and j["dtype"]
+        for key in ("cpu_baseline", "parity_check", "two_stage", "other_configs", "device_resident"):
+            assert key not in j, key
+        assert j["roofline"]["achieved_kernel_alone"] is None and j["roofline"]["achieved"] > 0
+        assert sorted(os.listdir(d)) == ["rows.npy", "scores.npy"] and j["outputs"]["queries"] == nq
+        dumps.append({name: np.load(d / (name + ".npy")) for name in ("scores", "rows")})
+    for name in ("scores", "rows"):
+        assert dumps[0][name].dtype == np.float32 and dumps[0][name].shape == (nq, k)
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    from dhr_amd import synth
+    dev = torch.device("cuda", 0)
+    cv, ci = bench.gen_rows(torch, synth, dev, 1237, 0, n, 768, 768, 30, 90, False, dup=True)
+    qv, qi = bench.gen_rows(torch, synth, dev, 1237 + 999_983, 0, nq, 768, 768, 4, 12, False)
+    c32, ci, q32, qi = cv.float().cpu().numpy(), ci.cpu().numpy(), qv.float().cpu().numpy(), qi.cpu().numpy()
+    del cv, qv
+    for i in range(0, nq, 6):
+        O.check_topk(dumps[0]["rows"][i], dumps[0]["scores"][i], O.gip_scores_f64(q32[i], qi[i], c32, ci), k)
 
 
 def test_bench_real_data_leg(tmp_path):
@@ -1970,7 +2009,7 @@ def test_bench_real_data_leg(tmp_path):
             for j, r in enumerate(top):
                 f.write("%s\t0\t%s\t%d\n" % (qid, docids[int(r)], 2 if j == 0 else 1))
             f.write("%s\t0\t%s\t0\n" % (qid, docids[int(np.argmin(ex))]))
-    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--quick", "--cpu-rows", "20000", "--topk", "100", "--index-path", str(tmp_path / "corpus.index.pt"),
+    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--full", "--quick", "--cpu-rows", "20000", "--topk", "100", "--index-path", str(tmp_path / "corpus.index.pt"),
            "--query-path", str(tmp_path / "queries.pt"), "--qrels", str(tmp_path / "qrels.tsv"), "--emb-dim", "768"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -1990,7 +2029,7 @@ def test_bench_rccl_bring_up_hangs_on_one_rank():
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     env = dict(os.environ, DHR_BENCH_SINGLE_DEVICE="1", DHR_BENCH_FORCE_RCCL_TRIAL="1", DHR_TEST_COMM_HANG_RANK="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29537", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--dist-backend", "gloo",
+           "--master-port", "29537", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--dist-backend", "gloo",
            "--n-docs", "300000", "--n-queries", "256", "--rccl-timeout", "20"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -21,21 +21,21 @@ P
 if [ $PART = bench ] || [ $PART = all ]; then
   ( while true; do echo "t=$(date +%s.%N) $(rocm-smi --showpower --showclocks 2>/dev/null | grep -E 'sclk|Package Power' | tr '\n' ' ')"; sleep 0.25; done ) > $O/${TAG}_bench.smi 2>&1 &
   SMI=$!
-  timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_${TAG}_hybrid.json 2> $O/bench_hybrid.err
+  timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_${TAG}_hybrid.json 2> $O/bench_hybrid.err
   kill $SMI
-  timeout 400 python bench.py --workload dense --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_dense.json 2> $O/bench_dense.err
-  timeout 400 python bench.py --workload dense --dense-i8 0 --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_dense_fp16.json 2> $O/bench_dense_fp16.err
-  timeout 400 python bench.py --uniform-idx --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_uniform_idx.json 2> $O/bench_uniform.err
-  DHR_GATED_I8=0 timeout 400 python bench.py --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_fp16_gated.json 2> $O/bench_hybrid_fp16.err
-  timeout 400 python bench.py --overlap-aux 0 --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_serial.json 2> $O/bench_hybrid_serial.err
-  timeout 300 python bench.py --workload bm25 --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_bm25.json 2> $O/bench_bm25.err
-  timeout 400 python bench.py --data clustered --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_clustered.json 2> $O/bench_clustered.err
+  timeout 400 python bench.py --full --workload dense --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_dense.json 2> $O/bench_dense.err
+  timeout 400 python bench.py --full --workload dense --dense-i8 0 --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_dense_fp16.json 2> $O/bench_dense_fp16.err
+  timeout 400 python bench.py --full --uniform-idx --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_uniform_idx.json 2> $O/bench_uniform.err
+  DHR_GATED_I8=0 timeout 400 python bench.py --full --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_fp16_gated.json 2> $O/bench_hybrid_fp16.err
+  timeout 400 python bench.py --full --overlap-aux 0 --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_serial.json 2> $O/bench_hybrid_serial.err
+  timeout 300 python bench.py --full --workload bm25 --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_bm25.json 2> $O/bench_bm25.err
+  timeout 400 python bench.py --full --data clustered --no-cpu-baseline --other-configs 0 > $O/bench_${TAG}_hybrid_clustered.json 2> $O/bench_clustered.err
   summ "hybrid dense dense_fp16 hybrid_uniform_idx hybrid_fp16_gated hybrid_serial bm25 hybrid_clustered"
 fi
 if [ $PART = trace ] || [ $PART = all ]; then
   cd /tmp && export TMPDIR=/tmp
-  timeout 400 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --other-configs 0 --two-stage 0 > $O/trace_bench.log 2>&1
-  timeout 400 rocprofv3 --kernel-trace --stats -d $O/trace_serial -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --other-configs 0 --two-stage 0 --overlap-aux 0 > $O/trace_serial_bench.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --other-configs 0 --two-stage 0 > $O/trace_bench.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -d $O/trace_serial -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --other-configs 0 --two-stage 0 --overlap-aux 0 > $O/trace_serial_bench.log 2>&1
   cd $R
   DB=$(ls $O/trace/*/*_results.db 2>/dev/null | head -1)
   [ -n "$DB" ] && python tools/rocpd_summary.py $DB $O/${TAG}_kernel_stats.txt | head -14
@@ -64,8 +64,8 @@ if [ $PART = pmc ] || [ $PART = all ]; then
   tail -1 $O/pmc_g8_f.log; tail -1 $O/pmc_dense_f.log; tail -1 $O/pmc_densei8_f.log
 fi
 if [ $PART = beir ] || [ $PART = all ]; then
-  timeout 1500 python bench.py --workload beir --no-cpu-baseline --steps 10 --warmup 3 --per-step > $O/bench_${TAG}_beir_exact.jsonl 2> $O/bench_beir_exact.err
-  [ "${BEIR_PQ:-0}" = 1 ] && timeout 2400 python bench.py --workload beir --pq --no-cpu-baseline --steps 5 --warmup 2 > $O/bench_${TAG}_beir_pq.jsonl 2> $O/bench_beir_pq.err
+  timeout 1500 python bench.py --full --workload beir --no-cpu-baseline --steps 10 --warmup 3 --per-step > $O/bench_${TAG}_beir_exact.jsonl 2> $O/bench_beir_exact.err
+  [ "${BEIR_PQ:-0}" = 1 ] && timeout 2400 python bench.py --full --workload beir --pq --no-cpu-baseline --steps 5 --warmup 2 > $O/bench_${TAG}_beir_pq.jsonl 2> $O/bench_beir_pq.err
   python3 - <<P
 import json
 for f in ("exact", "pq"):
@@ -77,7 +77,7 @@ for f in ("exact", "pq"):
 P
 fi
 if [ $PART = cpu32 ] || [ $PART = all ]; then
-  timeout 1200 python bench.py --steps 5 --warmup 2 --other-configs 0 --cpu-queries 32 --cpu-queries-1t 32 > $O/bench_${TAG}_hybrid_cpu32.json 2> $O/bench_cpu32.err
+  timeout 1200 python bench.py --full --steps 5 --warmup 2 --other-configs 0 --cpu-queries 32 --cpu-queries-1t 32 > $O/bench_${TAG}_hybrid_cpu32.json 2> $O/bench_cpu32.err
   python3 -c "
 import json
 d=json.loads(open('$O/bench_${TAG}_hybrid_cpu32.json').read().strip().splitlines()[-1]); print(json.dumps(d['cpu_baseline'])[:1500])"

@@ -1,0 +1,404 @@
+// The lexical head of the DHR / Aggretriever encoders (tevatron/DHR/modeling.py:297-300,328-331, tevatron/Aggretriever/modeling.py:274-278,
+// 306-310) fused with what the encoder driver does next to its output: densify (tevatron/DHR/utils.py:5-22 + encode.py:155-170,179-194) or
+// aggregate (tevatron/Aggretriever/utils.py:16-44 + merge_reps + encode.py:149-153,174-178).  The reference materialises
+//   p = softmax(logits[:, 1:])  (fp32, [B, L-1, V]),  reps = max_t (p * w) * mask  ([B, V])
+// in three fp32 [B, L-1, V] temporaries; here two kernels read the logits (pass 1 twice per row, the second read mostly from L2) and write the
+// index record directly:
+//   lexical_stats_kernel  one workgroup per (b, t) row: max_v x, then sum_v exp(x - max) (accumulated in fp64), as torch's softmax does; packs
+//                         (max, sum, w, mask) per token.  Masked rows are not read.
+//   lexical_fold_kernel   one workgroup per (b, block of output column pairs); the four / eight wave slices of a workgroup split the groups of
+//                         the column.  A lane keeps two adjacent columns, walks tokens (coalesced along the vocabulary) inside each group and
+//                         the groups in order, then the slices are folded in order through LDS and the epilogue (raw / densify / aggregate)
+//                         writes the record.  The logits of masked tokens are not loaded.
+// Semantics kept literally: every contribution is (p * w) * mask in fp32 (a masked token folds in a zero with the sign of w), ties keep the
+// first token and the first group (torch.max on the device), aggregate(full) is pos * (pos > neg) - neg * (pos <= neg) with its signs of zero.
+// NaN and +inf logits are out of scope (an unmasked row must hold a finite value).
+#include "dhr_state.h"
+
+namespace {
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+
+template <typename TIN> struct Vec;
+template <> struct Vec<_Float16> { typedef half8 type; static constexpr int n = 8; };
+template <> struct Vec<float> { typedef float4 type; static constexpr int n = 4; };
+
+// f(v) for every element of x[0, n): a scalar head up to the first 16-byte boundary, 16-byte vector loads, a scalar tail
+template <typename TIN, typename F>
+__device__ __forceinline__ void row_for_each(const TIN* __restrict__ x, int n, F&& f) {
+  constexpr int VN = Vec<TIN>::n;
+  const int head = min(n, (int)(((16 - ((uintptr_t)x & 15)) & 15) / sizeof(TIN)));
+  if ((int)threadIdx.x < head) f((float)x[threadIdx.x]);
+  const int n_vec = (n - head) / VN;
+  const typename Vec<TIN>::type* xv = reinterpret_cast<const typename Vec<TIN>::type*>(x + head);
+#pragma unroll 4
+  for (int i = threadIdx.x; i < n_vec; i += 256) {
+    const typename Vec<TIN>::type v = xv[i];
+#pragma unroll
+    for (int u = 0; u < VN; ++u) f((float)v[u]);
+  }
+  const int tail = head + n_vec * VN;
+  if (tail + (int)threadIdx.x < n) f((float)x[tail + threadIdx.x]);
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <typename TIN>
+__global__ void __launch_bounds__(256) lexical_stats_kernel(const TIN* __restrict__ logits, int64_t ld_batch, int64_t ld_token, int T, int V,
+                                                            const float* __restrict__ w, int64_t ld_w, const float* __restrict__ mk, int64_t ld_m,
+                                                            float4* __restrict__ stats) {
+  __shared__ float red[4];
+  __shared__ double red_d[4];
+  const int64_t row = blockIdx.x;
+  const int64_t b = row / T;
+  const int t = (int)(row - b * T);
+  const float wt = w[b * ld_w + t], mt = mk[b * ld_m + t];
+  if (mt == 0.f) {                                  // a masked token: its logits never take part (lexical_fold_kernel folds (0 * w) * 0)
+    if (threadIdx.x == 0) stats[row] = make_float4(0.f, 1.f, wt, mt);
+    return;
+  }
+  const TIN* x = logits + b * ld_batch + (int64_t)t * ld_token;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float m = -INFINITY;
+  row_for_each(x, V, [&](float v) { m = fmaxf(m, v); });
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  double s = 0.0;                                   // the normaliser is accumulated in fp64: fp32 rounded once, whatever the summation order
+  row_for_each(x, V, [&](float v) { s += (double)expf(v - m); });
+  s = wave_sum(s);
+  if (lane == 0) red_d[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) stats[row] = make_float4(m, (float)((red_d[0] + red_d[1]) + (red_d[2] + red_d[3])), wt, mt);
+}
+
+enum { MODE_RAW = 0, MODE_DENSIFY = 1, MODE_AGG_FULL = 2, MODE_AGG_SEMI = 3 };
+
+struct FoldArgs {
+  int64_t ld_batch, ld_token;
+  int T, V;
+  const float4* stats;       // [batch * T] (max, sum, w, mask); NULL: the input already is [batch, V] lexical reps (T = 1, no softmax)
+  int remove;                // first vocabulary column of group 0 (>= 0); a negative remove pads -remove zero columns at the end instead
+  int W, n_groups;           // group width (columns of the view [n_groups, W]) and count
+  int GS, PB, n_pairs;       // group slices per workgroup, column pairs per workgroup (GS * PB = 256), column pairs of the output
+  int64_t batch;
+  void* out_val;
+  int val_f32;
+  int64_t ld_val;
+  void* out_idx;
+  int idx_i16;
+  int64_t ld_idx;
+};
+
+template <typename TIN> struct Pair;
+template <> struct Pair<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(2))); };
+template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
+
+template <typename TIN, int MODE>
+__global__ void __launch_bounds__(256) lexical_fold_kernel(const TIN* __restrict__ logits, FoldArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float sh_best[256][2];
+  __shared__ int sh_arg[256][2];
+  const int lp = threadIdx.x % a.PB, sl = threadIdx.x / a.PB;
+  const int pair = blockIdx.x * a.PB + lp;
+  const int c0 = 2 * pair;
+  const bool live = pair < a.n_pairs;
+  const bool has1 = live && c0 + 1 < a.W;
+  const int g_lo = (int)((int64_t)sl * a.n_groups / a.GS), g_hi = (int)((int64_t)(sl + 1) * a.n_groups / a.GS);
+  const int base = a.remove > 0 ? a.remove : 0;
+  for (int64_t b = blockIdx.y; b < a.batch; b += gridDim.y) {
+    const TIN* xb = logits + b * a.ld_batch;
+    const float4* st = a.stats ? a.stats + b * a.T : nullptr;
+    float best0 = 0.f, best1 = 0.f;
+    int arg0 = 0, arg1 = 0;
+    for (int g = g_lo; g < g_hi; ++g) {
+      const int64_t v0 = (int64_t)base + (int64_t)g * a.W + c0;
+      const bool in0 = live && v0 < a.V, in1 = has1 && v0 + 1 < a.V;
+      // the pair is one aligned load when the group's first column is aligned to the pair (uniform across the workgroup)
+      const bool vec = in1 && ((((uintptr_t)(xb + base + (int64_t)g * a.W)) | (uintptr_t)(a.ld_token * sizeof(TIN))) % (2 * sizeof(TIN)) == 0);
+      float r0 = 0.f, r1 = 0.f;
+      for (int t = 0; t < a.T; ++t) {
+        float x0 = 0.f, x1 = 0.f;
+        const float4 s = st ? st[t] : make_float4(0.f, 1.f, 1.f, 1.f);
+        if (s.w != 0.f) {
+          const TIN* p = xb + (int64_t)t * a.ld_token + v0;
+          if (vec) {
+            const typename Pair<TIN>::type v = *reinterpret_cast<const typename Pair<TIN>::type*>(p);
+            x0 = (float)v.x; x1 = (float)v.y;
+          } else {
+            if (in0) x0 = (float)p[0];
+            if (in1) x1 = (float)p[1];
+          }
+        }
+        float c0v, c1v;
+        if (st) {
+          const float p0 = s.w != 0.f ? expf(x0 - s.x) / s.y : 0.f;
+          const float p1 = s.w != 0.f ? expf(x1 - s.x) / s.y : 0.f;
+          c0v = (p0 * s.z) * s.w;
+          c1v = (p1 * s.z) * s.w;
+        } else {
+          c0v = x0; c1v = x1;
+        }
+        if (t == 0 || c0v > r0) r0 = c0v;                 // first token wins a tie (the sign of a zero maximum)
+        if (t == 0 || c1v > r1) r1 = c1v;
+      }
+      if (!in0) r0 = 0.f;                                  // a padded column (aggregate with a negative remove) is +0
+      if (!in1) r1 = 0.f;
+      if (g == g_lo || r0 > best0) { best0 = r0; arg0 = g; }   // first group wins a tie
+      if (g == g_lo || r1 > best1) { best1 = r1; arg1 = g; }
+    }
+    if (a.GS > 1) {
+      sh_best[threadIdx.x][0] = best0; sh_best[threadIdx.x][1] = best1;
+      sh_arg[threadIdx.x][0] = arg0; sh_arg[threadIdx.x][1] = arg1;
+      __syncthreads();
+      if (sl == 0) {
+        for (int k = 1; k < a.GS; ++k) {                    // slices in group order: the earlier one keeps a tie
+          const int o = k * a.PB + lp;
+          if (sh_best[o][0] > best0) { best0 = sh_best[o][0]; arg0 = sh_arg[o][0]; }
+          if (sh_best[o][1] > best1) { best1 = sh_best[o][1]; arg1 = sh_arg[o][1]; }
+        }
+      }
+      __syncthreads();
+    }
+    if (sl != 0 || !live) continue;
+    if (MODE == MODE_AGG_FULL) {
+      const float pos = best0, neg = best1;
+      const float tok = pos * (float)(pos > neg) - neg * (float)(pos <= neg);
+      if (a.val_f32) ((float*)a.out_val)[b * a.ld_val + pair] = tok;
+      else ((__half*)a.out_val)[b * a.ld_val + pair] = __float2half(tok);
+      continue;
+    }
+    if (a.val_f32) {
+      ((float*)a.out_val)[b * a.ld_val + c0] = best0;
+      if (has1) ((float*)a.out_val)[b * a.ld_val + c0 + 1] = best1;
+    } else {
+      ((__half*)a.out_val)[b * a.ld_val + c0] = __float2half(best0);
+      if (has1) ((__half*)a.out_val)[b * a.ld_val + c0 + 1] = __float2half(best1);
+    }
+    if (MODE == MODE_DENSIFY) {
+      if (a.idx_i16) {
+        ((int16_t*)a.out_idx)[b * a.ld_idx + c0] = (int16_t)arg0;
+        if (has1) ((int16_t*)a.out_idx)[b * a.ld_idx + c0 + 1] = (int16_t)arg1;
+      } else {
+        ((uint8_t*)a.out_idx)[b * a.ld_idx + c0] = (uint8_t)arg0;
+        if (has1) ((uint8_t*)a.out_idx)[b * a.ld_idx + c0 + 1] = (uint8_t)arg1;
+      }
+    }
+  }
+}
+
+// the [CLS] reps into the record columns [col0, col0 + cls_dim) (merge_reps; the fp16 cast of encode.py)
+__global__ void __launch_bounds__(256) lexical_cls_kernel(const void* __restrict__ cls, int cls_f32, int64_t ld_cls, int cls_dim, int64_t batch,
+                                                          void* __restrict__ out, int out_f32, int64_t ld_out, int col0) {
+  const int64_t n = batch * cls_dim;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / cls_dim;
+    const int j = (int)(i - b * cls_dim);
+    const float v = cls_f32 ? ((const float*)cls)[b * ld_cls + j] : (float)((const _Float16*)cls)[b * ld_cls + j];
+    if (out_f32) ((float*)out)[b * ld_out + col0 + j] = v;
+    else ((__half*)out)[b * ld_out + col0 + j] = __float2half(v);
+  }
+}
+
+struct Geometry {
+  int out_cols, W, n_groups, remove;
+};
+
+hipError_t launch_fold(const void* logits, int in_f32, int mode, const FoldArgs& a0, hipStream_t s) {
+  FoldArgs a = a0;
+  a.GS = a.n_groups >= 8 ? 8 : a.n_groups >= 4 ? 4 : a.n_groups >= 2 ? 2 : 1;
+  a.PB = 256 / a.GS;
+  a.n_pairs = mode == MODE_AGG_FULL ? a.W / 2 : (a.W + 1) / 2;
+  const dim3 grid((unsigned)((a.n_pairs + a.PB - 1) / a.PB), (unsigned)std::min<int64_t>(a.batch, 65535));
+#define DHR_FOLD(T_, M_) hipLaunchKernelGGL((lexical_fold_kernel<T_, M_>), grid, dim3(256), 0, s, (const T_*)logits, a)
+#define DHR_FOLD_MODES(T_)                                 \
+  switch (mode) {                                          \
+    case MODE_RAW: DHR_FOLD(T_, MODE_RAW); break;          \
+    case MODE_DENSIFY: DHR_FOLD(T_, MODE_DENSIFY); break;  \
+    case MODE_AGG_FULL: DHR_FOLD(T_, MODE_AGG_FULL); break; \
+    default: DHR_FOLD(T_, MODE_AGG_SEMI); break;           \
+  }
+  if (in_f32) { DHR_FOLD_MODES(float) } else { DHR_FOLD_MODES(_Float16) }
+#undef DHR_FOLD_MODES
+#undef DHR_FOLD
+  return hipGetLastError();
+}
+
+// validates mode / dims / remove against the vocabulary; the geometry of the view the epilogue folds
+int geometry(int mode, int vocab, int dims, int remove, Geometry& g) {
+  if (mode == MODE_RAW) { g = {vocab, vocab, 1, 0}; return DHR_OK; }
+  if (mode != MODE_DENSIFY && mode != MODE_AGG_FULL && mode != MODE_AGG_SEMI) return set_error(DHR_ERR_INVALID, "bad lexical mode");
+  if (dims <= 0) return set_error(DHR_ERR_INVALID, "dims must be > 0");
+  if (mode == MODE_AGG_FULL && dims > (1 << 29)) return set_error(DHR_ERR_INVALID, "dims too large");
+  const int64_t W = mode == MODE_AGG_FULL ? 2 * (int64_t)dims : dims;
+  if (remove < 0 && mode != MODE_AGG_FULL) return set_error(DHR_ERR_INVALID, "remove_dims must be >= 0 (negative values pad, aggregate(full) only)");
+  const int64_t cols = remove >= 0 ? (int64_t)vocab - remove : (int64_t)vocab - (int64_t)remove;
+  if (cols <= 0 || cols % W != 0) {
+    if (mode == MODE_DENSIFY) return set_error(DHR_ERR_INVALID, "Input lexical representation cannot be densified, please fix dims or remove_dims");
+    return set_error(DHR_ERR_INVALID, "the vocabulary after remove_dims is not a whole number of groups");
+  }
+  if (cols / W > 32767) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 groups");
+  g = {dims, (int)W, (int)(cols / W), remove};
+  return DHR_OK;
+}
+
+int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
+
+}  // namespace
+
+extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void* logits, int32_t logits_dtype, int64_t batch,
+                                int32_t n_tokens, int32_t vocab, int64_t ld_batch, int64_t ld_token, const float* term_weights, int64_t ld_weights,
+                                const float* mask, int64_t ld_mask, int32_t dims, int32_t remove_dims, void* out_value, int32_t out_value_dtype,
+                                int64_t ld_value, void* out_index, int32_t index_dtype, int64_t ld_index, const void* cls, int32_t cls_dtype,
+                                int64_t ld_cls, int32_t cls_dim, void* workspace, void* stream) try {
+  dhr::alloc_checkpoint();
+  if (!logits || !term_weights || !mask || !out_value) return set_error(DHR_ERR_INVALID, "null pointer");
+  if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
+  if (!val_ok(logits_dtype) || !val_ok(out_value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (batch < 0 || n_tokens <= 0 || vocab <= 0 || ld_token < vocab || ld_batch < (int64_t)(n_tokens - 1) * ld_token + vocab ||
+      ld_weights < n_tokens || ld_mask < n_tokens || cls_dim < 0 || (int64_t)batch * n_tokens > ((int64_t)1 << 31) - 1)
+    return set_error(DHR_ERR_INVALID, "bad sizes / strides");
+  Geometry geo;
+  int rc = geometry(mode, vocab, dims, remove_dims, geo);
+  if (rc) return rc;
+  if (ld_value < (int64_t)geo.out_cols + cls_dim) return set_error(DHR_ERR_INVALID, "ld_value is smaller than the record's columns");
+  if (cls_dim > 0 && (!cls || !val_ok(cls_dtype) || ld_cls < cls_dim)) return set_error(DHR_ERR_INVALID, "bad cls reps");
+  if (mode == MODE_DENSIFY) {
+    if (!out_index) return set_error(DHR_ERR_INVALID, "null index pointer");
+    if (index_dtype != DHR_IDX_U8 && index_dtype != DHR_IDX_I16) return set_error(DHR_ERR_INVALID, "index dtype must be uint8 or int16");
+    if (index_dtype == DHR_IDX_U8 && geo.n_groups > 256) return set_error(DHR_ERR_UNSUPPORTED, "more than 256 groups need the int16 index dtype");
+    if (ld_index < geo.out_cols) return set_error(DHR_ERR_INVALID, "ld_index < dims");
+  }
+  if (batch == 0) return DHR_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const int ies = logits_dtype == DHR_VAL_F32 ? 4 : 2, oes = out_value_dtype == DHR_VAL_F32 ? 4 : 2, xes = index_dtype == DHR_IDX_I16 ? 2 : 1;
+  const int ces = cls_dtype == DHR_VAL_F32 ? 4 : 2;
+  const int T = n_tokens;
+  FoldArgs a{};
+  a.T = T; a.V = vocab; a.remove = geo.remove; a.W = geo.W; a.n_groups = geo.n_groups;
+  a.val_f32 = out_value_dtype == DHR_VAL_F32; a.idx_i16 = index_dtype == DHR_IDX_I16;
+  auto run = [&](const void* lg, int64_t ldb, int64_t ldt, const float* w, int64_t ldw, const float* m, int64_t ldm, int64_t rows, float4* stats,
+                 void* val, int64_t ldv, void* idx, int64_t ldi, const void* c, int64_t ldc) -> hipError_t {
+    if (logits_dtype == DHR_VAL_F32)
+      hipLaunchKernelGGL(lexical_stats_kernel<float>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const float*)lg, ldb, ldt, T, vocab, w, ldw, m,
+                         ldm, stats);
+    else
+      hipLaunchKernelGGL(lexical_stats_kernel<_Float16>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const _Float16*)lg, ldb, ldt, T, vocab, w,
+                         ldw, m, ldm, stats);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    FoldArgs f = a;
+    f.ld_batch = ldb; f.ld_token = ldt; f.stats = stats; f.batch = rows;
+    f.out_val = val; f.ld_val = ldv; f.out_idx = idx; f.ld_idx = ldi;
+    if ((e = launch_fold(lg, logits_dtype == DHR_VAL_F32, mode, f, s)) != hipSuccess) return e;
+    if (cls_dim > 0) {
+      const unsigned blocks = (unsigned)std::min<int64_t>((rows * cls_dim + 255) / 256, 4096);
+      hipLaunchKernelGGL(lexical_cls_kernel, dim3(blocks), dim3(256), 0, s, c, cls_dtype == DHR_VAL_F32, ldc, cls_dim, rows, val,
+                         out_value_dtype == DHR_VAL_F32, ldv, geo.out_cols);
+      e = hipGetLastError();
+    }
+    return e;
+  };
+  if (mem_kind == DHR_MEM_DEVICE) {
+    DevMem ws_mem;
+    void* ws = workspace;
+    if (!ws) HIP_TRY(hipMalloc(&ws_mem.p, (size_t)batch * T * sizeof(float4)));
+    if (!ws) ws = ws_mem.p;
+    HIP_TRY(run(logits, ld_batch, ld_token, term_weights, ld_weights, mask, ld_mask, batch, (float4*)ws, out_value, ld_value, out_index, ld_index, cls,
+                ld_cls));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DHR_OK;
+  }
+  // host arrays: stage blocks of rows through the device (logits packed [rows, T, vocab])
+  const int64_t per_row = (int64_t)T * vocab * ies;
+  const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / per_row));
+  const int64_t ldv = geo.out_cols + cls_dim;
+  DevMem m_in, m_w, m_m, m_st, m_val, m_idx, m_cls;
+  if (hipMalloc(&m_in.p, (size_t)(block * per_row)) != hipSuccess || hipMalloc(&m_w.p, (size_t)block * T * 4) != hipSuccess ||
+      hipMalloc(&m_m.p, (size_t)block * T * 4) != hipSuccess || hipMalloc(&m_st.p, (size_t)block * T * sizeof(float4)) != hipSuccess ||
+      hipMalloc(&m_val.p, (size_t)(block * ldv * oes)) != hipSuccess ||
+      (mode == MODE_DENSIFY && hipMalloc(&m_idx.p, (size_t)block * geo.out_cols * xes) != hipSuccess) ||
+      (cls_dim > 0 && hipMalloc(&m_cls.p, (size_t)block * cls_dim * ces) != hipSuccess))
+    return set_error(DHR_ERR_HIP, "hipMalloc failed");
+  for (int64_t lo = 0; lo < batch; lo += block) {
+    const int64_t rows = std::min(block, batch - lo);
+    for (int64_t r = 0; r < rows; ++r)
+      if (hipMemcpy2DAsync((char*)m_in.p + r * per_row, (size_t)vocab * ies, (const char*)logits + (lo + r) * ld_batch * ies, (size_t)ld_token * ies,
+                           (size_t)vocab * ies, (size_t)T, hipMemcpyHostToDevice, s) != hipSuccess)
+        return set_error(DHR_ERR_HIP, "H2D failed");
+    if (hipMemcpy2DAsync(m_w.p, (size_t)T * 4, term_weights + lo * ld_weights, (size_t)ld_weights * 4, (size_t)T * 4, (size_t)rows,
+                         hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpy2DAsync(m_m.p, (size_t)T * 4, mask + lo * ld_mask, (size_t)ld_mask * 4, (size_t)T * 4, (size_t)rows, hipMemcpyHostToDevice, s) !=
+            hipSuccess ||
+        (cls_dim > 0 && hipMemcpy2DAsync(m_cls.p, (size_t)cls_dim * ces, (const char*)cls + lo * ld_cls * ces, (size_t)ld_cls * ces,
+                                         (size_t)cls_dim * ces, (size_t)rows, hipMemcpyHostToDevice, s) != hipSuccess))
+      return set_error(DHR_ERR_HIP, "H2D failed");
+    if (run(m_in.p, (int64_t)T * vocab, vocab, (const float*)m_w.p, T, (const float*)m_m.p, T, rows, (float4*)m_st.p, m_val.p, ldv, m_idx.p,
+            geo.out_cols, m_cls.p, cls_dim) != hipSuccess)
+      return set_error(DHR_ERR_HIP, "lexical head launch failed");
+    if (hipMemcpy2DAsync((char*)out_value + lo * ld_value * oes, (size_t)ld_value * oes, m_val.p, (size_t)ldv * oes, (size_t)ldv * oes, (size_t)rows,
+                         hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (mode == MODE_DENSIFY &&
+         hipMemcpy2DAsync((char*)out_index + lo * ld_index * xes, (size_t)ld_index * xes, m_idx.p, (size_t)geo.out_cols * xes,
+                          (size_t)geo.out_cols * xes, (size_t)rows, hipMemcpyDeviceToHost, s) != hipSuccess))
+      return set_error(DHR_ERR_HIP, "D2H failed");
+    if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "lexical head failed on the device");
+  }
+  return DHR_OK;
+} DHR_CATCH_STATUS
+
+extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
+                             int32_t dims, int32_t remove_dims, int32_t full, void* out, int32_t out_dtype, int64_t ld_out, void* stream) try {
+  dhr::alloc_checkpoint();
+  if (!lexical || !out) return set_error(DHR_ERR_INVALID, "null pointer");
+  if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
+  if (!val_ok(value_dtype) || !val_ok(out_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (batch < 0 || vocab <= 0 || ld < vocab || ld_out < dims) return set_error(DHR_ERR_INVALID, "bad sizes / strides");
+  const int mode = full ? MODE_AGG_FULL : MODE_AGG_SEMI;
+  Geometry geo;
+  int rc = geometry(mode, vocab, dims, remove_dims, geo);
+  if (rc) return rc;
+  if (batch == 0) return DHR_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const int ies = value_dtype == DHR_VAL_F32 ? 4 : 2, oes = out_dtype == DHR_VAL_F32 ? 4 : 2;
+  FoldArgs a{};
+  a.ld_batch = ld; a.ld_token = vocab; a.T = 1; a.V = vocab; a.stats = nullptr;
+  a.remove = geo.remove; a.W = geo.W; a.n_groups = geo.n_groups; a.val_f32 = out_dtype == DHR_VAL_F32;
+  if (mem_kind == DHR_MEM_DEVICE) {
+    a.batch = batch; a.out_val = out; a.ld_val = ld_out;
+    HIP_TRY(launch_fold(lexical, value_dtype == DHR_VAL_F32, mode, a, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DHR_OK;
+  }
+  const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * ies)));
+  DevMem m_in, m_out;
+  if (hipMalloc(&m_in.p, (size_t)block * vocab * ies) != hipSuccess || hipMalloc(&m_out.p, (size_t)block * dims * oes) != hipSuccess)
+    return set_error(DHR_ERR_HIP, "hipMalloc failed");
+  a.ld_batch = vocab; a.out_val = m_out.p; a.ld_val = dims;
+  for (int64_t lo = 0; lo < batch; lo += block) {
+    const int64_t rows = std::min(block, batch - lo);
+    a.batch = rows;
+    if (hipMemcpy2DAsync(m_in.p, (size_t)vocab * ies, (const char*)lexical + lo * ld * ies, (size_t)ld * ies, (size_t)vocab * ies, (size_t)rows,
+                         hipMemcpyHostToDevice, s) != hipSuccess)
+      return set_error(DHR_ERR_HIP, "H2D failed");
+    if (launch_fold(m_in.p, value_dtype == DHR_VAL_F32, mode, a, s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate launch failed");
+    if (hipMemcpy2DAsync((char*)out + lo * ld_out * oes, (size_t)ld_out * oes, m_out.p, (size_t)dims * oes, (size_t)dims * oes, (size_t)rows,
+                         hipMemcpyDeviceToHost, s) != hipSuccess)
+      return set_error(DHR_ERR_HIP, "D2H failed");
+    if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate failed on the device");
+  }
+  return DHR_OK;
+} DHR_CATCH_STATUS

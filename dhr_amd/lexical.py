@@ -1,0 +1,213 @@
+"""The lexical head of the DHR / Aggretriever encoders on the fused HIP op `dhr_lexical_head`, and the Aggretriever twin of
+`dhr_amd.densify.densify` (`aggregate`, `cal_remove_dim`, tevatron/Aggretriever/utils.py) on the same kernel.
+
+The reference computes, in eager torch (tevatron/DHR/modeling.py:297-300, tevatron/Aggretriever/modeling.py:274-278),
+
+    p_logits = softmax(psg_out.logits[:, 1:])                                                  # fp32 [B, L-1, V]
+    p_lexical_reps = torch.max((p_logits * p_term_weights) * attention_mask, dim=-2).values    # [B, V]
+
+and the encoder driver then densifies (DHR) or aggregates (Aggretriever) the reps and casts them to fp16 into the index record
+(tevatron/driver/encode.py:149-194).  Here one op reads the logits and writes the record:
+
+    lexical_reps(logits, term_weights, attention_mask)                          -> [B, V] fp32 reps
+    densify_lexical_into(..., value_out, index_out, dims, remove_dims, semantic_reps)   DHR / DLR records
+    aggregate_lexical_into(..., value_out, agg_dim, full, semantic_reps)                Aggretriever records
+
+Arguments: `logits` [B, T, V] fp16 or fp32 (pass `psg_out.logits[:, 1:]`: any batch / token strides, the last dimension contiguous, the view
+is read in place), `term_weights` [B, T] or [B, T, 1] fp16 / fp32, `attention_mask` [B, T] or [B, T, 1] of any integer or bool dtype (the
+reference's `psg['attention_mask'][:, 1:]`).  Each contribution is (p * w) * mask in fp32, so a masked token folds in a zero with the sign of
+its weight, and ties keep the first token and the first group, like torch.max on the device.  Finite logits and -inf are in scope; NaN and
++inf are not, and every unmasked token needs one finite logit.
+
+Torch CUDA tensors are processed on their device; numpy arrays are staged through device 0.  There is no CPU implementation: without the HIP
+library / a GPU the calls raise."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+VOCAB_SIZE = 30522
+
+
+def cal_remove_dim(dims, vocab_size=VOCAB_SIZE):
+    """tevatron/Aggretriever/utils.py:8-14: the unused leading vocabulary ids (negative: zero columns padded at the end)."""
+    remove_dims = vocab_size % dims
+    if remove_dims > 1000:  # the first 1000 tokens in BERT are useless
+        remove_dims -= dims
+    return remove_dims
+
+
+def _agg_geometry(batch, vocab, dims, full):
+    """-> (remove, group width) of aggregate(), raising what the reference's view raises."""
+    if full:
+        remove, width = cal_remove_dim(dims * 2), dims * 2
+        cols = vocab - remove if remove < 0 else max(0, vocab - remove)
+    else:
+        remove, width = cal_remove_dim(dims), dims
+        if remove < 0:
+            raise ValueError('aggregate(full=False): cal_remove_dim({}) = {} is negative; the semi-aggregated view does not exist'.format(dims, remove))
+        cols = max(0, vocab - remove)
+    if batch * cols == 0:
+        raise RuntimeError("cannot reshape tensor of 0 elements into shape [{}, -1, {}] because the unspecified dimension size -1 can be any "
+                           "value and is ambiguous".format(batch, width))
+    if cols % width:
+        raise RuntimeError("shape '[{}, -1, {}]' is invalid for input of size {}".format(batch, width, batch * cols))
+    return remove, width
+
+
+def _densify_check(vocab, dims, remove_dims):
+    if (vocab - remove_dims) % dims != 0:                                                    # tevatron/DHR/utils.py:14-16
+        raise ValueError('Input lexical representation cannot be densified, please fix dims or remove_dims')
+
+
+def _is_np(a):
+    return isinstance(a, np.ndarray)
+
+
+def _device_of(a):
+    return 0 if _is_np(a) or not a.is_cuda else (a.device.index or 0)
+
+
+def _inputs(logits, term_weights, attention_mask):
+    """-> (logits view, pointer, batch / token strides, w fp32 [B, T], mask fp32 [B, T], B, T, V, mem_kind)."""
+    if len(logits.shape) != 3:
+        raise ValueError('logits must be [batch, tokens, vocab], got {} dimensions'.format(len(logits.shape)))
+    B, T, V = (int(d) for d in logits.shape)
+    if T == 0:
+        raise ValueError('no tokens: the maximum over tokens of an empty sequence is undefined')
+    if _is_np(logits):
+        if logits.dtype not in (np.float16, np.float32):
+            raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
+        es = logits.itemsize
+        if logits.strides[2] != es or any(s % es or s < 0 for s in logits.strides[:2]) or logits.strides[1] < V * es or logits.strides[0] < (T - 1) * logits.strides[1] + V * es:
+            logits = np.ascontiguousarray(logits)
+        ldb, ldt = logits.strides[0] // es, logits.strides[1] // es
+        w = np.ascontiguousarray(np.asarray(term_weights).reshape(B, T), dtype=np.float32)
+        m = np.ascontiguousarray(np.asarray(attention_mask).reshape(B, T), dtype=np.float32)
+        return logits, logits.ctypes.data, ldb, ldt, w, m, B, T, V, _lib.MEM_HOST
+    import torch
+    if logits.dtype not in (torch.float16, torch.float32):
+        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
+    logits = logits.detach()
+    if logits.stride(2) != 1 or logits.stride(1) < V or logits.stride(0) < (T - 1) * logits.stride(1) + V:
+        logits = logits.contiguous()
+    w = term_weights.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
+    m = attention_mask.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
+    kind = _lib.MEM_DEVICE if logits.is_cuda else _lib.MEM_HOST
+    return logits, logits.data_ptr(), logits.stride(0), logits.stride(1), w, m, B, T, V, kind
+
+
+def _ptr(a):
+    return a.ctypes.data if _is_np(a) else a.data_ptr()
+
+
+def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps):
+    lib = _lib.load()
+    lg, p_lg, ldb, ldt, w, m, B, T, V, kind = _inputs(logits, term_weights, attention_mask)
+    p_v, ld_v, kind_v = _lib._ptr_ld(value_out)
+    if kind_v != kind:
+        raise _lib.DhrError("lexical head: inputs and outputs must live in the same memory kind")
+    p_i, ld_i, idx_dt = None, 0, _lib.IDX_NONE
+    if index_out is not None:
+        p_i, ld_i, kind_i = _lib._ptr_ld(index_out)
+        if kind_i != kind:
+            raise _lib.DhrError("lexical head: inputs and outputs must live in the same memory kind")
+        idx_dt = _lib.idx_code(index_out.dtype)
+    p_c, ld_c, c_dt, c_dim, keep = None, 0, _lib.VAL_F16, 0, None
+    if semantic_reps is not None:
+        c = semantic_reps if _is_np(semantic_reps) else semantic_reps.detach()
+        if _is_np(c) and c.dtype not in (np.float16, np.float32):
+            c = c.astype(np.float32)
+        elif not _is_np(c) and str(c.dtype) not in ("torch.float16", "torch.float32"):
+            c = c.float()
+        p_c, ld_c, kind_c = _lib._ptr_ld(c)
+        if kind_c != kind:
+            raise _lib.DhrError("lexical head: semantic reps must live in the same memory kind as the logits")
+        if int(c.shape[0]) != B:
+            raise ValueError("semantic reps do not match the batch")
+        c_dt, c_dim, keep = _lib._val_code(c), int(c.shape[1]), c
+    ws = None
+    if kind == _lib.MEM_DEVICE and B:
+        import torch
+        ws = torch.empty(B * T * 16, dtype=torch.uint8, device=lg.device)
+    if B:
+        _lib.check(lib.dhr_lexical_head(_device_of(lg), kind, mode, p_lg, _lib._val_code(lg), B, T, V, ldb, ldt, _ptr(w), T, _ptr(m), T, dims,
+                                        remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim,
+                                        None if ws is None else ws.data_ptr(), None), "dhr_lexical_head")
+    del keep
+    return B, V
+
+
+def lexical_reps(logits, term_weights, attention_mask):
+    """-> [B, V] fp32 lexical reps, torch.max((softmax(logits) * term_weights) * attention_mask, dim=-2).values.
+    numpy in -> numpy out; torch in -> torch out (same device)."""
+    B, V = int(logits.shape[0]), int(logits.shape[-1])
+    if _is_np(logits):
+        out = np.empty((B, V), np.float32)
+    else:
+        import torch
+        out = torch.empty((B, V), dtype=torch.float32, device=logits.device)
+    _run(_lib.LEX_RAW, logits, term_weights, attention_mask, out, None, 0, 0, None)
+    return out
+
+
+def _check_out(value_out, B, cols):
+    if int(value_out.shape[0]) != B or int(value_out.shape[1]) < cols:
+        raise ValueError("output arrays do not match the batch / dims")
+
+
+def densify_lexical_into(logits, term_weights, attention_mask, value_out, index_out, dims: int = 768, remove_dims: int = 570, semantic_reps=None):
+    """The DHR / DLR branch of encode.py:155-170,179-194 in one op: densify(lexical reps, dims, remove_dims) written into the first `dims`
+    columns of the record's value array (fp16 or fp32, rows of width dims + cls_dim) and its index array (uint8, or int16 beyond 256
+    groups); semantic_reps [B, cls_dim], if given, into the value columns [dims, dims + cls_dim).  -> (value_out, index_out)."""
+    B, V = int(logits.shape[0]), int(logits.shape[-1])
+    _densify_check(V, dims, remove_dims)
+    cls = 0 if semantic_reps is None else int(semantic_reps.shape[1])
+    _check_out(value_out, B, dims + cls)
+    _check_out(index_out, B, dims)
+    _run(_lib.LEX_DENSIFY, logits, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps)
+    return value_out, index_out
+
+
+def aggregate_lexical_into(logits, term_weights, attention_mask, value_out, agg_dim: int = 640, full: bool = True, semantic_reps=None):
+    """The `agg` branch of encode.py:149-153,174-178 in one op: aggregate(lexical reps, agg_dim, full) (+ merge_reps with semantic_reps)
+    written into the record's value array [B, >= agg_dim + cls_dim] (fp16 or fp32).  -> value_out."""
+    B, V = int(logits.shape[0]), int(logits.shape[-1])
+    remove, _ = _agg_geometry(B, V, agg_dim, full)
+    cls = 0 if semantic_reps is None else int(semantic_reps.shape[1])
+    _check_out(value_out, B, agg_dim + cls)
+    _run(_lib.LEX_AGG_FULL if full else _lib.LEX_AGG_SEMI, logits, term_weights, attention_mask, value_out, None, agg_dim, remove, semantic_reps)
+    return value_out
+
+
+def aggregate(lexical_reps, dims: int = 640, remove_dims: int = -198, full: bool = True):
+    """tevatron/Aggretriever/utils.py:16-44 on the HIP kernel: [B, V] reps -> [B, dims] in the input dtype.  As in the reference,
+    full=True takes remove = cal_remove_dim(2 * dims) and ignores `remove_dims`; full=False removes cal_remove_dim(dims) columns.
+    numpy in -> numpy out; torch in -> torch out (same device)."""
+    del remove_dims                                     # (the reference overwrites it in both branches)
+    if len(lexical_reps.shape) != 2:
+        raise ValueError('Input lexical representation shape should be 2 (batch, vocab), but the input shape is {}'.format(len(lexical_reps.shape)))
+    B, V = int(lexical_reps.shape[0]), int(lexical_reps.shape[1])
+    remove, _ = _agg_geometry(B, V, dims, full)
+    lib = _lib.load()
+    if _is_np(lexical_reps):
+        src = lexical_reps if lexical_reps.dtype in (np.float16, np.float32) else lexical_reps.astype(np.float32)
+        src = np.ascontiguousarray(src)
+        out = np.empty((B, dims), src.dtype)
+        dev = 0
+    else:
+        import torch
+        src = lexical_reps.detach()
+        if src.dtype not in (torch.float16, torch.float32):
+            src = src.float()
+        src = src.contiguous()
+        out = torch.empty((B, dims), dtype=src.dtype, device=src.device)
+        dev = _device_of(src)
+    p_in, ld_in, kind = _lib._ptr_ld(src)
+    p_o, ld_o, _ = _lib._ptr_ld(out)
+    _lib.check(lib.dhr_aggregate(dev, kind, p_in, _lib._val_code(src), ld_in, B, V, dims, remove, 1 if full else 0, p_o, _lib._val_code(out), ld_o,
+                                 None), "dhr_aggregate")
+    if _is_np(lexical_reps):
+        return out.astype(lexical_reps.dtype, copy=False)
+    return out.to(lexical_reps.dtype)

@@ -297,6 +297,34 @@ int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t v
                 int32_t remove_dims, int32_t dims, void* out_value, int32_t out_value_dtype, int64_t ld_value, void* out_index,
                 int32_t index_dtype, int64_t ld_index, void* stream);
 
+/* The lexical head of the encoders fused with the step after it (tevatron/DHR/modeling.py:297-300,328-331,
+ * tevatron/Aggretriever/modeling.py:274-278,306-310; then densify or aggregate and the fp16 casts of tevatron/driver/encode.py:149-194).
+ * logits is [batch, n_tokens, vocab] (value_dtype DHR_VAL_F16 / DHR_VAL_F32, strides ld_batch / ld_token / 1: the [:, 1:] view of the
+ * model's [B, L, V] logits), term_weights and mask are fp32 [batch, n_tokens] (row strides ld_weights / ld_mask).  With
+ * p = softmax over the whole vocabulary in fp32,
+ *   reps[b][v] = max_t (p[b][t][v] * w[b][t]) * mask[b][t]       (first token on ties: a fully masked column keeps the sign of its first w)
+ * and mode selects what is written, with row strides, straight into the caller's record arrays:
+ *   DHR_LEX_RAW       out_value [batch, vocab] = reps                                      (dims / remove_dims ignored)
+ *   DHR_LEX_DENSIFY   densify(reps, dims, remove_dims): out_value [batch, dims], out_index (DHR_IDX_U8 / DHR_IDX_I16, first group on ties)
+ *   DHR_LEX_AGG_FULL  aggregate(reps, dims, full=True): groups of 2*dims columns from remove_dims (a negative remove_dims pads -remove_dims
+ *                     zero columns at the end), then pos * (pos > neg) - neg * (pos <= neg) of the even / odd columns
+ *   DHR_LEX_AGG_SEMI  aggregate(reps, dims, full=False): groups of dims columns from remove_dims >= 0
+ * out_value_dtype DHR_VAL_F16 rounds to fp16.  cls_dim > 0 copies cls [batch, cls_dim] (row stride ld_cls) into the record columns that follow
+ * (vocab or dims), so ld_value >= those + cls_dim.  workspace: NULL, or batch * n_tokens * 16 bytes of device memory on `device` (device
+ * arrays only).  All arrays live in mem_kind memory; host arrays are staged through the device in blocks of rows.  NaN and +inf logits
+ * are out of scope; every unmasked row needs a finite logit.  DHR_ERR_INVALID when the vocabulary does not split into whole groups. */
+typedef enum dhr_lexical_mode { DHR_LEX_RAW = 0, DHR_LEX_DENSIFY = 1, DHR_LEX_AGG_FULL = 2, DHR_LEX_AGG_SEMI = 3 } dhr_lexical_mode;
+int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void* logits, int32_t value_dtype, int64_t batch, int32_t n_tokens,
+                     int32_t vocab, int64_t ld_batch, int64_t ld_token, const float* term_weights, int64_t ld_weights, const float* mask,
+                     int64_t ld_mask, int32_t dims, int32_t remove_dims, void* out_value, int32_t out_value_dtype, int64_t ld_value,
+                     void* out_index, int32_t index_dtype, int64_t ld_index, const void* cls, int32_t cls_dtype, int64_t ld_cls, int32_t cls_dim,
+                     void* workspace, void* stream);
+/* aggregate of already computed lexical reps [batch, vocab] (tevatron/Aggretriever/utils.py:16-44) on the same kernel: full != 0 is
+ * DHR_LEX_AGG_FULL, else DHR_LEX_AGG_SEMI; out [batch, dims] (row stride ld_out).  The caller passes remove_dims as the reference computes it
+ * (cal_remove_dim). */
+int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
+                  int32_t dims, int32_t remove_dims, int32_t full, void* out, int32_t out_dtype, int64_t ld_out, void* stream);
+
 /* Product quantiser for the first stage of --PQIP.  The reference calls faiss
  * IndexPQ(d, M = 64, nbits = 8, METRIC_INNER_PRODUCT) (retrieval/quantize_index.py:27-37, gip_retrieval.py:167-231); faiss is not
  * part of the reference tree, so these restate its published algorithm (per-subspace Lloyd k-means, nearest-centroid codes, ADC

@@ -325,6 +325,37 @@ int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void*
 int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
                   int32_t dims, int32_t remove_dims, int32_t full, void* out, int32_t out_dtype, int64_t ld_out, void* stream);
 
+/* The gated inner product of a training step and of the in-model reranker, with its gradient (tevatron/DHR/modeling.py:161-170, 212-226,
+ * 250-285: listwise_gip_scores / pairwise_gip_scores, which repeat the passage batch once per query and keep [n_q, n_p, dims] tensors for
+ * autograd).  q_value [n_q, dims] and p_value [n_p, dims] are densified values (value_dtype DHR_VAL_F16 / DHR_VAL_F32, both sides alike, row
+ * strides: the [:, :dims] view of a record is read in place), q_index / p_index their group indices (index_dtype DHR_IDX_U8 / I8 / I16, both
+ * sides alike).  group = 0 is the listwise form, every query against every passage; group = n > 0 the pairwise form, passage row b * n + j
+ * belongs to query b and n_p == n_q * n.
+ *   dhr_gip_scores           out[b][p] = sum_d (q_index[b][d] == p_index[p][d]) * q_value[b][d] * p_value[p][d], fp32 products and sums whatever
+ *                            the input dtype; out is fp32 [n_q, n_p] listwise, [n_q, n] pairwise (row stride ld_out).
+ *   dhr_gip_scores_backward  with grad_out = dL/d out (fp32, row stride ld_grad):
+ *                            grad_q[b][d] = sum_p grad_out[b][p] * match * p_value[p][d],  grad_p[p][d] = sum_b grad_out[b][p] * match * q_value[b][d]
+ *                            (pairwise: over the query's own block), fp32 [n_q, dims] / [n_p, dims]; either may be NULL and is then not computed.
+ *   dhr_densify_backward     the gradient of dhr_densify (max sends it to the one index it returned): grad_lexical [batch, vocab] (grad_dtype
+ *                            DHR_VAL_F32 / DHR_VAL_F16) gets grad_value[b][j] at column remove_dims + index[b][j] * dims + j and zero in every
+ *                            other column, the remove_dims leading ones included: the whole row is written, in one pass.
+ * Every sum runs in a fixed order: two calls on the same arguments are bit-identical.  Small listwise problems split dims over workgroups
+ * and fold the partial sums in order; that needs dhr_gip_scores_workspace bytes of device memory from the caller (0: none needed; a NULL or
+ * too small workspace runs unsplit, slower and with another summation order).  For device arrays the library allocates nothing and the calls
+ * ENQUEUE on `stream` and return without waiting (a training step stays asynchronous); host arrays are staged through the device and are
+ * complete on return.  DHR_ERR_INVALID for NULL / negative sizes / unknown dtypes, n_p != n_q * group, a vocabulary that does not split. */
+int64_t dhr_gip_scores_workspace(int64_t n_q, int64_t n_p, int32_t dims, int32_t group);
+int dhr_gip_scores(int32_t device, int32_t mem_kind, const void* q_value, int64_t ld_q_value, const void* q_index, int64_t ld_q_index, int64_t n_q,
+                   const void* p_value, int64_t ld_p_value, const void* p_index, int64_t ld_p_index, int64_t n_p, int32_t dims, int32_t value_dtype,
+                   int32_t index_dtype, int32_t group, float* out, int64_t ld_out, void* workspace, int64_t workspace_bytes, void* stream);
+int dhr_gip_scores_backward(int32_t device, int32_t mem_kind, const void* q_value, int64_t ld_q_value, const void* q_index, int64_t ld_q_index,
+                            int64_t n_q, const void* p_value, int64_t ld_p_value, const void* p_index, int64_t ld_p_index, int64_t n_p, int32_t dims,
+                            int32_t value_dtype, int32_t index_dtype, int32_t group, const float* grad_out, int64_t ld_grad, float* grad_q,
+                            int64_t ld_grad_q, float* grad_p, int64_t ld_grad_p, void* stream);
+int dhr_densify_backward(int32_t device, int32_t mem_kind, const float* grad_value, int64_t ld_grad_value, const void* index, int32_t index_dtype,
+                         int64_t ld_index, int64_t batch, int32_t vocab, int32_t remove_dims, int32_t dims, void* grad_lexical, int32_t grad_dtype,
+                         int64_t ld_grad, void* stream);
+
 /* Product quantiser for the first stage of --PQIP.  The reference calls faiss
  * IndexPQ(d, M = 64, nbits = 8, METRIC_INNER_PRODUCT) (retrieval/quantize_index.py:27-37, gip_retrieval.py:167-231); faiss is not
  * part of the reference tree, so these restate its published algorithm (per-subspace Lloyd k-means, nearest-centroid codes, ADC

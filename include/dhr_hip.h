@@ -356,6 +356,33 @@ int dhr_densify_backward(int32_t device, int32_t mem_kind, const float* grad_val
                          int64_t ld_index, int64_t batch, int32_t vocab, int32_t remove_dims, int32_t dims, void* grad_lexical, int32_t grad_dtype,
                          int64_t ld_grad, void* stream);
 
+/* The lexical head of a TRAINING step, forward and backward (the same lines of modeling.py as dhr_lexical_head, with autograd on): device
+ * arrays only (DHR_ERR_UNSUPPORTED for DHR_MEM_HOST: training tensors live on the device), enqueued on `stream` without waiting, nothing
+ * allocated.  logits is the model's [batch, skip_tokens + n_tokens, vocab] tensor (value_dtype DHR_VAL_F16 / DHR_VAL_F32, strides ld_batch /
+ * ld_token / 1); the first skip_tokens tokens take no part (the reference drops token 0; pass the [:, 1:] view with skip_tokens = 0 for the
+ * same numbers).  term_weights and mask are fp32 [batch, n_tokens].  n_tokens <= 32767.
+ *   dhr_lexical_head_train_workspace  bytes of device memory the two calls share: (max, sum, w, mask) per token, written by the forward and
+ *                                     read by the backward, then one float per token the backward writes (0 for invalid sizes).
+ *   dhr_lexical_head_train            out_reps fp32 [batch, vocab], bit-identical to dhr_lexical_head(DHR_LEX_RAW); out_tokens int16
+ *                                     [batch, vocab], the first token that attains the maximum (counted after the skipped ones).
+ *   dhr_lexical_head_backward         with grad_reps = dL/d reps (fp32 [batch, vocab]), tokens and workspace as the forward left them, and
+ *                                     A[b][t] = sum over {v : tokens[b][v] == t} of grad_reps[b][v] * p[b][t][v]:
+ *                                     grad_weights[b][t] = mask * A (fp32 [batch, n_tokens]),
+ *                                     grad_logits[b][t][v] = p * ([tokens[b][v] == t] * grad_reps[b][v] * w * mask - w * mask * A), in the
+ *                                     logits' dtype, the WHOLE [batch, skip_tokens + n_tokens, vocab] tensor (strides ld_grad_batch /
+ *                                     ld_grad_token / 1): skipped and masked tokens are written as zeros.  Either output may be NULL.
+ * p is recomputed from the logits, never stored.  A is accumulated in fp64 in a fixed order (no atomics): two calls on the same arguments are
+ * bit-identical. */
+int64_t dhr_lexical_head_train_workspace(int64_t batch, int32_t n_tokens);
+int dhr_lexical_head_train(int32_t device, int32_t mem_kind, const void* logits, int32_t value_dtype, int64_t batch, int32_t n_tokens,
+                           int32_t skip_tokens, int32_t vocab, int64_t ld_batch, int64_t ld_token, const float* term_weights, int64_t ld_weights,
+                           const float* mask, int64_t ld_mask, float* out_reps, int64_t ld_reps, int16_t* out_tokens, int64_t ld_tokens,
+                           void* workspace, void* stream);
+int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logits, int32_t value_dtype, int64_t batch, int32_t n_tokens,
+                              int32_t skip_tokens, int32_t vocab, int64_t ld_batch, int64_t ld_token, const float* grad_reps, int64_t ld_grad_reps,
+                              const int16_t* tokens, int64_t ld_tokens, void* workspace, void* grad_logits, int64_t ld_grad_batch,
+                              int64_t ld_grad_token, float* grad_weights, int64_t ld_grad_weights, void* stream);
+
 /* Product quantiser for the first stage of --PQIP.  The reference calls faiss
  * IndexPQ(d, M = 64, nbits = 8, METRIC_INNER_PRODUCT) (retrieval/quantize_index.py:27-37, gip_retrieval.py:167-231); faiss is not
  * part of the reference tree, so these restate its published algorithm (per-subspace Lloyd k-means, nearest-centroid codes, ADC

@@ -47,14 +47,28 @@ constexpr int SP_SLOT = SP_STAGE_A + SP_STAGE_B;   // LDS ring slot (34 KiB): co
 //   query : [256 queries][64 bytes = 32 slices x (bucket-0 column, bucket-1 column)], 16-byte chunks swizzled like every other image.
 constexpr int S8_A_BYTES = 8192;
 constexpr int S8_STAGE_A = S8_A_BYTES + 2048;
-#ifndef DHR_HEAVY
-#define DHR_HEAVY 64
-#endif
-constexpr int HEAVY = DHR_HEAVY;        // per-row list of the largest gated values used by the refine step (64, or 32 in A/B builds: 8 lanes x HEAVY / 8 entries)
-// ... stored as ONE 6 x HEAVY-byte record per row (384 B): HEAVY u32 keys, then HEAVY fp16 values (a candidate's refine read is one contiguous
-// segment instead of a 256-byte and a 128-byte one in two arrays): heavy_key = record base, heavy_val = base + 4 x HEAVY bytes
+constexpr int HEAVY = 64;               // per-row list of the largest gated values used by the refine step, heaviest first
+// ... stored as ONE 6 x HEAVY-byte record per row (384 B = three 128-byte lines), blocked for the two levels of refine_kernel.  64 entries x
+// (u32 key + fp16 value) fill the 384 bytes exactly, so there is no byte to pad with and the split follows from the lane geometry:
+//   line 1   : 4 pieces of 32 bytes, piece s = the keys of entries 5s .. 5s+4 (20 bytes), their values (10 bytes) and ONE spare fp16:
+//              HEAVY_B0 = 20 entries that level 1 reads with 4 lanes per candidate;
+//   lines 2-3: 4 pieces of 64 bytes, piece s = the keys of entries 20 + 11s .. 20 + 11s + 10 (44 bytes) and the values of the first ten of
+//              them (20 bytes); the value of the eleventh is the spare fp16 of piece s of line 1 (level 1 hands it on with the survivor).
+// heavy_key = record base in u32 words, heavy_val = the same base in fp16 units.
+constexpr int HEAVY_B0 = 20;                       // entries of line 1
 constexpr int HEAVY_KEY_STRIDE = HEAVY * 6 / 4;    // u32 per record
 constexpr int HEAVY_VAL_STRIDE = HEAVY * 6 / 2;    // fp16 per record
+__host__ __device__ inline int heavy_key_word(int r) {       // u32 offset of the key of entry r in its record
+  if (r < HEAVY_B0) return 8 * (r / 5) + r % 5;
+  r -= HEAVY_B0;
+  return 32 + 16 * (r / 11) + r % 11;
+}
+__host__ __device__ inline int heavy_val_half(int r) {       // fp16 offset of its value
+  if (r < HEAVY_B0) return 2 * (8 * (r / 5) + 5) + r % 5;
+  r -= HEAVY_B0;
+  const int s = r / 11, e = r % 11;
+  return e < 10 ? 2 * (32 + 16 * s + 11) + e : 2 * (8 * s + 5) + 5;
+}
 #ifndef DHR_DOC_GROUP
 #define DHR_DOC_GROUP 4
 #endif
@@ -317,7 +331,7 @@ hipError_t launch_heavy_build(const __half* vals_rm, int k_rm, const void* idx, 
 #ifndef REFINE_PER_WG_N
 #define REFINE_PER_WG_N 512   // round 5: 256 -> 512 takes 1.0 ms off the refine level of a config-3 step (11.1 -> 10.05 ms alone; 1 024: 9.8)
 #endif
-constexpr int REFINE_PER_WG = REFINE_PER_WG_N;       // candidates of ONE query per refine workgroup (its operand words are staged in LDS once); a multiple of 32
+constexpr int REFINE_PER_WG = REFINE_PER_WG_N;       // candidates of ONE query per refine workgroup (its operand words are staged in LDS once); a multiple of 64 (refine_kernel: 64 candidates per round)
 struct RefineArgs {
   const uint2* cand; const uint32_t* cnt; uint32_t cap;      // bound candidates (row, U bits)
   const uint2* ovf; const uint32_t* ovf_off; const uint32_t* ovf_cap;   // ... their second tier (GemmArgs), or null

@@ -433,10 +433,10 @@ extern "C" int dhr_index_create(const dhr_index_desc* d_user, dhr_index** out) t
   // pass 2: operand tiles
   if ((rc = build_tiles(ix, s)) != DHR_OK) return fail(rc);
   if (has_idx && d->d_dlr <= 4096) {
-    const size_t hb = (size_t)d->n_rows * HEAVY_KEY_STRIDE * 4;       // one 6 x HEAVY-byte record per row: the keys, then the values
+    const size_t hb = (size_t)d->n_rows * HEAVY_KEY_STRIDE * 4;       // one 6 x HEAVY-byte record per row (layout: dhr_internal.h)
     if (hipMalloc((void**)&ix->heavy_key, hb) != hipSuccess)
       return fail(set_error(DHR_ERR_HIP, "hipMalloc of the refine lists failed"));
-    ix->heavy_val = (__half*)((char*)ix->heavy_key + HEAVY * 4);
+    ix->heavy_val = (__half*)ix->heavy_key;
     ix->index_bytes += (int64_t)hb;
     if (launch_heavy_build(ix->vals_rm, ix->k_rm, ix->c_idx, ix->idx_dtype, d->n_rows, d->d_dlr, ix->bucket_map, ix->n_buckets,
                            ix->heavy_key, ix->heavy_val, ix->gated_i8 ? ix->g8_inv_cs : nullptr, ix->abs_mode ? 1 : 0, s) != hipSuccess)

@@ -883,6 +883,7 @@ __device__ __forceinline__ bool flat_block(const uint32_t* __restrict__ offs, in
 // ------------------------------------------------------------------------------------------ heavy lists + refine
 // Build (once per index): per row the HEAVY largest-magnitude gated entries, as
 //   key = slice << 20 | bucket << 16 | index value (16 bits),  val = the fp16 value;  unused slots key = ~0.
+// Entry r (0 = the heaviest) goes to heavy_key_word(r) / heavy_val_half(r) of the row's record: line 1 = the 20 heaviest (dhr_internal.h).
 // One wave per row, HEAVY rounds of wave-wide arg-max over a register copy of the row (d_dlr <= 1024).
 template <int SL>      // key registers per lane: 16 (d_dlr <= 1024) or 64 (<= 4096)
 __global__ void __launch_bounds__(256) heavy_build_kernel(const __half* __restrict__ vals_rm, int k_rm,
@@ -913,7 +914,7 @@ __global__ void __launch_bounds__(256) heavy_build_kernel(const __half* __restri
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) { const uint32_t ob = __shfl_xor(best, o, 64); best = ob > best ? ob : best; }
       if (best == 0u) {                       // fewer than HEAVY non-zero entries: pad
-        if (lane == 0) for (int rr = r; rr < HEAVY; ++rr) { heavy_key[row * HEAVY_KEY_STRIDE + rr] = 0xFFFFFFFFu; heavy_val[row * HEAVY_VAL_STRIDE + rr] = __float2half(0.f); }
+        if (lane == 0) for (int rr = r; rr < HEAVY; ++rr) { heavy_key[row * HEAVY_KEY_STRIDE + heavy_key_word(rr)] = 0xFFFFFFFFu; heavy_val[row * HEAVY_VAL_STRIDE + heavy_val_half(rr)] = __float2half(0.f); }
         break;
       }
       const int j = MAXJ - (int)(best & 0xFFFFu);
@@ -930,8 +931,8 @@ __global__ void __launch_bounds__(256) heavy_build_kernel(const __half* __restri
           const uint32_t lvl = d > 0.f ? (uint32_t)quant_up_i8(d, g8_inv_cs[j]) : 0u;
           key_out = ((uint32_t)j << 20) | ((lvl >> 4) << 17) | ((bk & 1u) << 16) | ((lvl & 0xFu) << 12) | ((uint32_t)iv & 0xFFFu);
         }
-        heavy_key[row * HEAVY_KEY_STRIDE + r] = key_out;
-        heavy_val[row * HEAVY_VAL_STRIDE + r] = vals_rm[row * k_rm + j];
+        heavy_key[row * HEAVY_KEY_STRIDE + heavy_key_word(r)] = key_out;
+        heavy_val[row * HEAVY_VAL_STRIDE + heavy_val_half(r)] = vals_rm[row * k_rm + j];
 #pragma unroll
         for (int sl = 0; sl < SL; ++sl) if (sl == (j >> 6)) key[sl] = 0u;
       }
@@ -955,22 +956,32 @@ hipError_t launch_heavy_build(const __half* vals_rm, int k_rm, const void* idx, 
 // entries we can afford to look at the real index: same bucket but different index value contributes
 // nothing to the exact score, so |q_j d_j| is taken off the bound.  U2 = U - sum(corr) is still an
 // upper bound of the exact score (only certain mismatches are removed; the query side keeps 12 index
-// bits, an alias there only makes the bound looser).  8 lanes per candidate, 8 heavy entries per lane.
+// bits, an alias there only makes the bound looser).
 // (Round 4: marking the row gathers of the refine / rescoring kernels non-temporal -- they are read once, the idea being that they should
 // not evict the bound GEMM's operand tiles from L2 when the two overlap -- made BOTH kernels slower, with and without overlap: refine
 // 12.0 -> 14.1 ms, rescoring 15.8 -> 16.6 ms per config-3 step, step 121.7 -> 124.5 ms.  Plain loads stay.)
 static __device__ __forceinline__ uint4 gather16(const void* p) { return *(const uint4*)p; }
 static __device__ __forceinline__ uint2 gather8(const void* p) { return *(const uint2*)p; }
-// (Round 4: refine in two levels -- the record as four blocks of 16 entries, each its keys then its values; the candidate's first two lanes
-// read block 0 = the 16 heaviest entries = one 128-byte line, the candidate is re-tested, and only the survivors' other six lanes read blocks
-// 1-3 -- prunes 60 % of the candidates after one line instead of three, and was SLOWER: refine 11.3 -> 15.9 ms per config-3 step.  The kernel
-// is bound by the round trips a wave waits for, not by bytes: nearly every wave holds a survivor among its 8 candidates and then pays two
-// dependent gathers per iteration.  It would take a compacting pass between the levels (a third list set); not built.)
+// Refine in two levels.  The entries of a record are stored heaviest first and every listed entry can only LOWER the bound, so a candidate
+// that is under the threshold after the 20 entries of line 1 is under it after all 64: most candidates are decided by one 128-byte line
+// instead of three.  (Round 4 built this with 8 lanes per candidate and no compaction, and it was SLOWER, 11.3 -> 15.9 ms per config-3 step:
+// the kernel is bound by the round trips a wave waits for, not by bytes, nearly every wave held a survivor among its 8 candidates and then
+// paid two dependent gathers per iteration.)  Hence:
+//   level 1: 4 lanes per candidate, 32 bytes each = line 1 of the record (layout: dhr_internal.h): a wave retires 16 candidates per round
+//            trip.  The candidate is re-tested with the partial sums; the survivors go to a list in LDS -- every wave compacts its own 128
+//            candidates of the block into its own segment (ballot + prefix count: no atomic, no count in memory) -- as row, U, the partial
+//            `taken` / `back` (apart, so that the final fp64 expression is today's) and the four spare fp16 of line 1;
+//   level 2: behind one barrier every wave walks its survivors densely, 4 lanes per survivor, 64 bytes each = lines 2-3 in one round trip,
+//            finishes the sums and appends to the output list.
+// LDS: 14 KB of survivor slots (a hot query keeps every candidate: 512 slots) + the query words, 20 KB at 768 slices = 8 workgroups per CU.
 #ifndef REFINE_PREFETCH
-#define REFINE_PREFETCH 2   // rounds of a lane group in flight: 0 = entry -> record -> lookups in sequence, 1 = the next entries ahead, 2 = + the next record
+#define REFINE_PREFETCH 2   // level 1, rounds of a lane group in flight: 0 = entry -> record -> lookups in sequence, 1 = the next entries ahead, 2 = + the next record
+#endif
+#ifndef REFINE_L2_PREFETCH
+#define REFINE_L2_PREFETCH 0   // level 2: 1 = the next round's 64-byte pieces are gathered before the current ones are looked up (16 more registers: 11 spilled at 64; refine 6.38 instead of 6.00 ms per config-3 step)
 #endif
 #ifndef REFINE_WPE
-#define REFINE_WPE 8      // waves per SIMD the register allocation aims at: 8 = 64 registers (8 bytes of scratch); the compiler's own choice (66: 7 waves) runs 9.95 instead of 8.85 ms per config-3 step
+#define REFINE_WPE 8      // waves per SIMD the register allocation aims at: 8 = 64 registers; the one-level kernel ran 9.95 instead of 8.85 ms per config-3 step at the compiler's own choice (66: 7 waves)
 #endif
 #if REFINE_WPE > 0
 #define REFINE_ATTR __attribute__((amdgpu_waves_per_eu(REFINE_WPE)))
@@ -979,10 +990,18 @@ static __device__ __forceinline__ uint2 gather8(const void* p) { return *(const 
 #endif
 template <bool G8>
 __global__ void __launch_bounds__(256) REFINE_ATTR refine_kernel(RefineArgs p) {
+  static_assert(REFINE_PER_WG % 64 == 0 && HEAVY_B0 == 20 && HEAVY == 64, "4 lanes x 5 entries, then 4 lanes x 11 entries per candidate; 64 candidates per round");
   extern __shared__ uint32_t qw[];             // [d_dlr] query words (up to 4096 slices: the slice id has 12 bits in a heavy-list key);
                                                // G8: [d_dlr] pairs {query word, the query's int8 operand level}: one 8-byte LDS read per listed entry
+  constexpr int WSLOTS = REFINE_PER_WG / 4;    // survivor slots of one wave: the candidates it looks at in level 1
+  __shared__ uint2 sv_c[REFINE_PER_WG];        // survivors of level 1: the list entry (row, U bits),
+  __shared__ uint32_t sv_t[REFINE_PER_WG];     // G8: `taken` of line 1; else the bits of its `corr`,
+  __shared__ double sv_b[G8 ? REFINE_PER_WG : 1];      // G8: `back` of line 1,
+  __shared__ uint16_t sv_s[REFINE_PER_WG * 4]; // and the spare fp16 of its four pieces = the value of the eleventh entry of level 2's lane
   int q = blockIdx.y;
   uint32_t blk = blockIdx.x;
+  const int sub = threadIdx.x & 3, lane = threadIdx.x & 63;
+  const uint32_t slot0 = (threadIdx.x >> 6) * WSLOTS;
   for (uint32_t fb = blockIdx.x;; fb += gridDim.x) {       // flat launches: grid stride over the block list (see rescore_kernel); else one pass
   if (p.blk_off && !flat_block(p.blk_off, p.n_queries, fb, q, blk)) return;
   uint32_t count = p.cnt[q];
@@ -990,123 +1009,191 @@ __global__ void __launch_bounds__(256) REFINE_ATTR refine_kernel(RefineArgs p) {
   if (count > cap_q) count = cap_q;
   const uint32_t base = blk * REFINE_PER_WG;
   if (base >= count) { if (p.blk_off) continue; return; }
-  __syncthreads();                                           // the previous block's readers are done with the staged query words
+  __syncthreads();                                           // the previous block's readers are done with the staged query words and the survivor slots
   for (int j = threadIdx.x; j < p.d_dlr; j += 256) {
     if constexpr (G8) { qw[2 * j] = p.q_pack[(int64_t)q * p.d_dlr + j]; qw[2 * j + 1] = p.g8_q8[(int64_t)q * p.d_dlr + j]; }
     else qw[j] = p.q_pack[(int64_t)q * p.d_dlr + j];
   }
   __syncthreads();
-  const int sub = threadIdx.x & 7;
   const float t = p.thr[q];
   const double unit = G8 ? (double)p.g8_unit[q] : 0.0;
-  // (A variant that issued the loads of all 8 candidates of a lane group up front ran 30 % SLOWER: 4x the gathers
-  // in flight per CU only thrash the memory system; the dependent chain below at 8 waves per SIMD is the sweet spot.)
-  // the list entry of the NEXT round is loaded before the current one's record is gathered: one dependent round trip per round instead of two
-  auto entry = [&](uint32_t i) __attribute__((always_inline)) -> uint2 {
-    if (i >= count || i >= base + REFINE_PER_WG) return make_uint2(0u, 0u);
-    return i < p.cap ? p.cand[(int64_t)q * p.cap + i] : p.ovf[(size_t)p.ovf_off[q] + (i - p.cap)];
-  };
-  // ... and so is the next round's RECORD: two rounds of a lane group are in flight (entry of round r + 2, record of round r + 1) while
-  // round r is looked up.  (All 8 records of a lane group up front thrash the memory system, see above; one ahead does not.)
-  constexpr int EPL = HEAVY / 8;              // entries per lane: 8 (two 16-byte key loads + one 16-byte value load) or 4 (one + an 8-byte one)
-  static_assert(EPL == 8 || EPL == 4, "8 lanes per candidate read 8 or 4 entries each");
-  struct Rec { uint4 k0, k1, hv; };
-  auto record = [&](uint32_t i, const uint2 c, Rec& r) __attribute__((always_inline)) {
-    r.k0 = r.k1 = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    r.hv = make_uint4(0u, 0u, 0u, 0u);
-    if (i < count && i < base + REFINE_PER_WG) {
-      const uint32_t* hk = p.heavy_key + (int64_t)c.x * HEAVY_KEY_STRIDE + sub * EPL;
-      r.k0 = gather16(hk);
-      if constexpr (EPL == 8) {
-        r.k1 = gather16(hk + 4);
-        r.hv = gather16(p.heavy_val + (int64_t)c.x * HEAVY_VAL_STRIDE + sub * 8);
-      } else {
-        const uint2 v2 = gather8(p.heavy_val + (int64_t)c.x * HEAVY_VAL_STRIDE + sub * 4);
-        r.hv = make_uint4(v2.x, v2.y, 0u, 0u);
+  const uint32_t end = base + REFINE_PER_WG;
+  // one listed entry: G8 -> taken (operand products, integer units, of the listed same-bucket entries) and back (real-valued products of
+  // those whose index values agree); else corr (|q d| of the same-bucket entries whose index values differ)
+  auto look = [&](const uint32_t key, const uint32_t hbits, int& taken, double& back, float& corr) __attribute__((always_inline)) {
+    if (key == 0xFFFFFFFFu) return;
+    const uint32_t j = key >> 20;
+    union { uint16_t u; _Float16 h; } dv; dv.u = (uint16_t)hbits;
+    if constexpr (G8) {
+      const uint2 wq = *(const uint2*)(qw + 2 * j);
+      const uint32_t w = wq.x;
+      const bool same_bucket = p.ungated || ((w >> 12) & 0x1u) == ((key >> 16) & 0x1u);
+      const bool mismatch = !p.ungated && (w & 0xFFFu) != (key & 0xFFFu);
+      const int lvl = (int)(((key >> 17) & 0x7u) << 4 | ((key >> 12) & 0xFu));      // the entry's int8 operand level (heavy_build_kernel)
+      if (same_bucket && lvl > 0) {
+        taken += (int)wq.y * lvl;
+        if (!mismatch) {
+          union { uint16_t u; _Float16 h; } qv; qv.u = (uint16_t)(w >> 16);
+          const float d = p.abs_mode ? fabsf((float)dv.h) : (float)dv.h;
+          back += (double)(float)qv.h * (double)d;
+        }
       }
+    } else {
+      const uint32_t w = qw[j];
+      const bool same_bucket = ((w >> 12) & 0xFu) == ((key >> 16) & 0xFu);
+      const bool mismatch = (w & 0xFFFu) != (key & 0xFFFu);
+      union { uint16_t u; _Float16 h; } qv; qv.u = (uint16_t)(w >> 16);
+      if (same_bucket && mismatch) corr += fabsf((float)qv.h * (float)dv.h);
     }
   };
-  const uint32_t i_first = base + (threadIdx.x >> 3);
+  // U counted `taken` units for the listed same-bucket entries; the entries whose index values agree contribute their real product, the
+  // others nothing.  fp64: exact up to 2^-53 relative; the result is rounded UP to fp32.
+  auto bound_g8 = [&](const uint32_t u_bits, const int taken, const double back) __attribute__((always_inline)) -> float {
+    const double v = (double)__uint_as_float(u_bits) - (double)taken * unit + back;
+    float u2 = (float)v;
+    if ((double)u2 < v) u2 = nextafterf(u2, INFINITY);
+    return u2;
+  };
+  // ---- level 1.  (A variant of the one-level kernel that issued the loads of all candidates of a lane group up front ran 30 % SLOWER: 4x the
+  // gathers in flight per CU only thrash the memory system; the dependent chain below at 8 waves per SIMD is the sweet spot.)
+  // The list entry of the NEXT round is loaded before the current one's record is gathered, and so is the next round's RECORD: two rounds of a
+  // lane group are in flight (entry of round r + 2, record of round r + 1) while round r is looked up.
+  auto entry = [&](uint32_t i) __attribute__((always_inline)) -> uint2 {
+    if (i >= count || i >= end) return make_uint2(0u, 0u);
+    return i < p.cap ? p.cand[(int64_t)q * p.cap + i] : p.ovf[(size_t)p.ovf_off[q] + (i - p.cap)];
+  };
+  struct Rec1 { uint4 a, b; };                 // a.xyzw, b.x: five keys; b.y, b.z, low half of b.w: their values; high half of b.w: the spare
+  auto record1 = [&](uint32_t i, const uint2 c, Rec1& r) __attribute__((always_inline)) {
+    r.a = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    r.b = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+    if (i < count && i < end) {
+      const uint32_t* h = p.heavy_key + (int64_t)c.x * HEAVY_KEY_STRIDE + sub * 8;
+      r.a = gather16(h);
+      r.b = gather16(h + 4);
+    }
+  };
+  uint32_t n_w = 0;                            // survivors of this wave so far (the same in all its lanes)
+  const uint32_t i_first = base + (threadIdx.x >> 2);
 #if REFINE_PREFETCH >= 1
-  uint2 c_cur = entry(i_first), c_nx = entry(i_first + 32);
+  uint2 c_cur = entry(i_first), c_nx = entry(i_first + 64);
 #endif
 #if REFINE_PREFETCH >= 2
-  Rec r_cur;
-  record(i_first, c_cur, r_cur);
+  Rec1 r_cur;
+  record1(i_first, c_cur, r_cur);
 #endif
-  for (uint32_t i = i_first; i < base + REFINE_PER_WG; i += 32) {
-    float corr = 0.f;
-    int taken = 0;              // G8: operand products (integer units) of the listed same-bucket entries
-    double back = 0.0;          // G8: real-valued products of those whose index values agree
+  for (uint32_t i = i_first; i < end; i += 64) {
 #if REFINE_PREFETCH >= 2
     const uint2 c = c_cur;
-    const Rec rc = r_cur;
-    Rec r_nx;
-    record(i + 32, c_nx, r_nx);
-    const uint2 c_nx2 = entry(i + 64);
+    const Rec1 rc = r_cur;
+    Rec1 r_nx;
+    record1(i + 64, c_nx, r_nx);
+    const uint2 c_nx2 = entry(i + 128);
     c_cur = c_nx; c_nx = c_nx2; r_cur = r_nx;
 #elif REFINE_PREFETCH == 1
     const uint2 c = c_cur;
-    c_cur = c_nx; c_nx = entry(i + 64);
-    Rec rc;
-    record(i, c, rc);
+    c_cur = c_nx; c_nx = entry(i + 128);
+    Rec1 rc;
+    record1(i, c, rc);
 #else
     const uint2 c = entry(i);
-    Rec rc;
-    record(i, c, rc);
+    Rec1 rc;
+    record1(i, c, rc);
 #endif
-    if (i < count) {
-      const uint4 k0 = rc.k0, k1 = rc.k1;
-      union { uint4 u; half8 h; } hvu;
-      hvu.u = rc.hv;
-      const half8 hv = hvu.h;
-      const uint32_t keys[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) {
-        const uint32_t key = keys[e];
-        if (key != 0xFFFFFFFFu) {
-          const uint32_t j = key >> 20;
-          if constexpr (G8) {
-            const uint2 wq = *(const uint2*)(qw + 2 * j);
-            const uint32_t w = wq.x;
-            const bool same_bucket = p.ungated || ((w >> 12) & 0x1u) == ((key >> 16) & 0x1u);
-            const bool mismatch = !p.ungated && (w & 0xFFFu) != (key & 0xFFFu);
-            const int lvl = (int)(((key >> 17) & 0x7u) << 4 | ((key >> 12) & 0xFu));      // the entry's int8 operand level (heavy_build_kernel)
-            if (same_bucket && lvl > 0) {
-              taken += (int)wq.y * lvl;
-              if (!mismatch) {
-                union { uint16_t u; _Float16 h; } qv; qv.u = (uint16_t)(w >> 16);
-                const float d = p.abs_mode ? fabsf((float)hv[e]) : (float)hv[e];
-                back += (double)(float)qv.h * (double)d;
-              }
-            }
-          } else {
-            const uint32_t w = qw[j];
-            const bool same_bucket = ((w >> 12) & 0xFu) == ((key >> 16) & 0xFu);
-            const bool mismatch = (w & 0xFFFu) != (key & 0xFFFu);
-            union { uint16_t u; _Float16 h; } qv; qv.u = (uint16_t)(w >> 16);
-            if (same_bucket && mismatch) corr += fabsf((float)qv.h * (float)hv[e]);
-          }
-        }
-      }
+    float corr = 0.f;
+    int taken = 0;
+    double back = 0.0;
+    const bool valid = i < count;              // (the same in the candidate's four lanes)
+    if (valid) {
+      look(rc.a.x, rc.b.y & 0xFFFFu, taken, back, corr);
+      look(rc.a.y, rc.b.y >> 16, taken, back, corr);
+      look(rc.a.z, rc.b.z & 0xFFFFu, taken, back, corr);
+      look(rc.a.w, rc.b.z >> 16, taken, back, corr);
+      look(rc.b.x, rc.b.w & 0xFFFFu, taken, back, corr);
     }
     if constexpr (G8) {
-      taken += __shfl_xor(taken, 1, 64); taken += __shfl_xor(taken, 2, 64); taken += __shfl_xor(taken, 4, 64);
-      back += __shfl_xor(back, 1, 64); back += __shfl_xor(back, 2, 64); back += __shfl_xor(back, 4, 64);
+      taken += __shfl_xor(taken, 1, 64); taken += __shfl_xor(taken, 2, 64);
+      back += __shfl_xor(back, 1, 64); back += __shfl_xor(back, 2, 64);
     } else {
       corr += __shfl_xor(corr, 1, 64);
       corr += __shfl_xor(corr, 2, 64);
-      corr += __shfl_xor(corr, 4, 64);
     }
-    if (sub == 0 && i < count) {
+    // the partial bound is an upper bound of the final one; G8: one fp32 step of slack, far more than what the fp64 sums of the two levels can
+    // differ by, so that level 1 drops nothing that the final test keeps.  (fp32 corr: a sum of non-negative terms only grows, rounded or not.)
+    bool keep = false;
+    if (valid) {
+      if constexpr (G8) keep = nextafterf(bound_g8(c.y, taken, back), INFINITY) >= t;
+      else keep = __uint_as_float(c.y) - corr >= t;
+    }
+    const unsigned long long m = __ballot(keep);           // four equal bits per candidate
+    if (keep) {
+      const uint32_t slot = slot0 + n_w + (uint32_t)__popcll(m & ((1ull << (lane & ~3)) - 1ull)) / 4u;
+      sv_s[slot * 4 + sub] = (uint16_t)(rc.b.w >> 16);
+      if (sub == 0) {
+        sv_c[slot] = c;
+        if constexpr (G8) { sv_t[slot] = (uint32_t)taken; sv_b[slot] = back; }
+        else sv_t[slot] = __float_as_uint(corr);
+      }
+    }
+    n_w += (uint32_t)__popcll(m) / 4u;
+  }
+  // ---- level 2: the wave's own survivors, 16 per round
+  __syncthreads();
+  n_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_w);
+  struct Rec2 { uint4 a, b, c, d; };           // a, b, c.xyz: eleven keys; c.w, d: the values of the first ten
+  auto record2 = [&](uint32_t k, Rec2& r) __attribute__((always_inline)) {
+    r.a = r.b = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    r.c = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u);
+    r.d = make_uint4(0u, 0u, 0u, 0u);
+    if (k < n_w) {
+      const uint32_t* h = p.heavy_key + (int64_t)sv_c[slot0 + k].x * HEAVY_KEY_STRIDE + 32 + sub * 16;
+      r.a = gather16(h);
+      r.b = gather16(h + 4);
+      r.c = gather16(h + 8);
+      r.d = gather16(h + 12);
+    }
+  };
+#if REFINE_L2_PREFETCH
+  Rec2 s_cur;
+  record2((uint32_t)(lane >> 2), s_cur);
+#endif
+  for (uint32_t k0 = 0; k0 < n_w; k0 += 16) {
+    const uint32_t k = k0 + (uint32_t)(lane >> 2);
+#if REFINE_L2_PREFETCH
+    const Rec2 rc = s_cur;
+    record2(k + 16, s_cur);
+#else
+    Rec2 rc;
+    record2(k, rc);
+#endif
+    float corr = 0.f;
+    int taken = 0;
+    double back = 0.0;
+    const bool valid = k < n_w;
+    if (valid) {
+      look(rc.a.x, rc.c.w & 0xFFFFu, taken, back, corr);
+      look(rc.a.y, rc.c.w >> 16, taken, back, corr);
+      look(rc.a.z, rc.d.x & 0xFFFFu, taken, back, corr);
+      look(rc.a.w, rc.d.x >> 16, taken, back, corr);
+      look(rc.b.x, rc.d.y & 0xFFFFu, taken, back, corr);
+      look(rc.b.y, rc.d.y >> 16, taken, back, corr);
+      look(rc.b.z, rc.d.z & 0xFFFFu, taken, back, corr);
+      look(rc.b.w, rc.d.z >> 16, taken, back, corr);
+      look(rc.c.x, rc.d.w & 0xFFFFu, taken, back, corr);
+      look(rc.c.y, rc.d.w >> 16, taken, back, corr);
+      look(rc.c.z, (uint32_t)sv_s[(slot0 + k) * 4 + sub], taken, back, corr);
+    }
+    if constexpr (G8) {
+      taken += __shfl_xor(taken, 1, 64); taken += __shfl_xor(taken, 2, 64);
+      back += __shfl_xor(back, 1, 64); back += __shfl_xor(back, 2, 64);
+    } else {
+      corr += __shfl_xor(corr, 1, 64);
+      corr += __shfl_xor(corr, 2, 64);
+    }
+    if (sub == 0 && valid) {
+      const uint2 c = sv_c[slot0 + k];
       float u2;
-      if constexpr (G8) {
-        // U counted `taken` units for the listed same-bucket entries; the entries whose index values agree contribute their real
-        // product, the others nothing.  fp64: exact up to 2^-53 relative; the result is rounded UP to fp32.
-        const double v = (double)__uint_as_float(c.y) - (double)taken * unit + back;
-        u2 = (float)v;
-        if ((double)u2 < v) u2 = nextafterf(u2, INFINITY);
-      } else u2 = __uint_as_float(c.y) - corr;
+      if constexpr (G8) u2 = bound_g8(c.y, (int)sv_t[slot0 + k] + taken, sv_b[slot0 + k] + back);
+      else u2 = __uint_as_float(c.y) - (__uint_as_float(sv_t[slot0 + k]) + corr);
       if (u2 >= t) {
         const uint32_t slot = atomicAdd(p.out_cnt + q, 1u);
         if (slot < p.out_cap) p.out[(int64_t)q * p.out_cap + slot] = make_uint2(c.x, __float_as_uint(u2));

@@ -1662,6 +1662,159 @@ __device__ __forceinline__ void rescore_block(const RescoreArgs& p, const int q,
   }
   }      // PATH != 3
 }
+// wave_sum_f64 with the partners below lane distance 32 fetched by ds_swizzle (xor mode: no address register, no address arithmetic): the same
+// v + v[lane ^ o] for o = 32 ... 1, bit for bit
+__device__ __forceinline__ double wave_sum_f64_swz(double v) {
+  v += __shfl_xor(v, 32, 64);
+  auto step = [&](auto o) __attribute__((always_inline)) {
+    constexpr int pat = (decltype(o)::value << 10) | 0x1F;
+    union { double d; int w[2]; } a, b;
+    a.d = v;
+    b.w[0] = __builtin_amdgcn_ds_swizzle(a.w[0], pat);
+    b.w[1] = __builtin_amdgcn_ds_swizzle(a.w[1], pat);
+    v += b.d;
+  };
+  step(std::integral_constant<int, 16>{}); step(std::integral_constant<int, 8>{}); step(std::integral_constant<int, 4>{});
+  step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 1>{});
+  return v;
+}
+// pair_mask as three instructions per register of the row: the builtin form above is canonicalised to a compare per 16-bit lane and comes out as
+// v_cmp_eq_u16 / v_cndmask / v_perm triples (~9 per register)
+__device__ __forceinline__ uint32_t pair_mask_pk(uint32_t x, uint32_t sel, uint32_t one) {
+  uint32_t t = __builtin_amdgcn_perm(0u, x, sel), r;
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(t), "v"(one));
+  asm("v_pk_sub_u16 %0, %1, %2" : "=v"(t) : "v"(r), "v"(one));
+  return t;
+}
+// Wide rows with the whole row in flight (the <T, G> instances of rescore_fast_kernel): T = ceil(chunks / 64) chunks per lane and G = ceil(gated
+// chunks / 64) index words per lane are compile-time constants, so a pair is T + G loads issued back to back and ONE wait.  The query's chunks
+// and index bytes of the lane are loaded once per block; the row ids of the wave's 8 pairs come from one load (lane j holds pair j) and are
+// broadcast as scalars; the loads of the next P - 1 pairs are in flight while a pair is converted and added, P while it is reduced.  Lanes past
+// the row's end and ungated lanes of a half-gated pass load from a clamped address (no branch around a load: the wait counts stay exact) and
+// are predicated in the arithmetic.  A pair whose row is outside the index, or past the list's end, prefetches row 0 and its sum is dropped.
+// Scores are stored once per block by lanes 0..7.  The sum itself is the general loop's: lane l adds chunks l, l + 64, ... in fp64, registers
+// 0..3 low half first, then wave_sum_f64.
+#ifndef RESCORE_WIDE_P
+#define RESCORE_WIDE_P 2       // rows in flight per wave (A/B builds: -DRESCORE_WIDE_P=4 -DRESCORE_WIDE_WPE=4)
+#endif
+// Waves per SIMD of the <T, G> instances: the most that hold P rows, the query and the masks without scratch (72 registers at 7, 80 at 6,
+// 96 at 5, 128 at 4); what counts is the row bytes in flight per SIMD, not the occupancy
+constexpr int rescore_wide_wpe(int T, int G) {
+#ifdef RESCORE_WIDE_WPE
+  return RESCORE_WIDE_WPE;       // A/B builds
+#else
+  static_assert(RESCORE_WIDE_P == 2, "the table below was taken from the P = 2 allocation");
+  return T == 3 ? (G <= 2 ? 7 : 6) : (G == 0 ? 7 : G <= 3 ? 5 : 4);
+#endif
+}
+template <int T, int G, int P>
+__device__ __forceinline__ void rescore_block_wide(const RescoreArgs& p, const int q_in, const uint32_t blk_in) {
+  constexpr int NP = RESCORE_CANDS_PER_WG / 4;      // pairs per wave and block
+  static_assert(NP <= 64 && G <= T && P >= 1, "one lane per pair of the wave");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // (query, block) and the list length are the same in every lane: as scalars, the row bases below are scalar arithmetic
+  const int q = __builtin_amdgcn_readfirstlane(q_in);
+  const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)blk_in);
+  uint32_t count;
+  if (p.cand) { count = p.cnt[q]; if (count > p.cap) count = p.cap; }
+  else count = p.count_all;
+  count = (uint32_t)__builtin_amdgcn_readfirstlane((int)count);
+  const uint32_t first = blk * RESCORE_CANDS_PER_WG + wave;
+  if (first >= count) return;
+  const int npairs = (int)min((uint32_t)NP, (count - first + 3u) >> 2);
+  const uint32_t nchunks = (uint32_t)p.k_rm >> 3;
+  const uint32_t dlr_chunks = (uint32_t)p.d_dlr >> 3;
+  // this lane's row id (lane j: pair j of the wave), and the row it loads from
+  const uint32_t i_own = first + 4u * (uint32_t)lane;
+  uint32_t row_own = 0u;
+  bool valid_own = false;
+  if (lane < npairs) {
+    if (p.cand) row_own = p.cand[(int64_t)q * p.cap + i_own].x;
+    else if (p.rows32) row_own = p.rows32[(int64_t)q * p.ld_rows + i_own];
+    else row_own = (uint32_t)(p.row0 + i_own);
+    valid_own = (int64_t)row_own < p.n_rows;
+  }
+  const uint32_t row_ld = valid_own ? row_own : 0u;
+  // the lane's chunks: c = lane + 64 t, as byte offsets into the row (16 per chunk) and into its index bytes (8 per chunk); only the last
+  // pass can run past the row's end / the gated half's end
+  const uint32_t c_last = (uint32_t)lane + 64u * (T - 1);
+  const bool live_last = c_last < nchunks;
+  const uint32_t voff0 = (uint32_t)lane * 16u, voff_last = (live_last ? c_last : nchunks - 1u) * 16u;
+  const uint32_t g_last = (uint32_t)lane + 64u * (G > 0 ? G - 1 : 0);
+  const bool gated_last = g_last < dlr_chunks;
+  const uint32_t xoff0 = (uint32_t)lane * 8u, xoff_last = (gated_last ? g_last : dlr_chunks - 1u) * 8u;
+  const uint32_t gmask_last = gated_last ? 0xFFFFFFFFu : 0u;
+  uint4 qv[T];
+  uint2 qx[G > 0 ? G : 1];
+  {
+    const char* q16 = (const char*)(p.q16 + (int64_t)q * p.k_rm);
+#pragma unroll
+    for (int t = 0; t < T; ++t) qv[t] = *(const uint4*)(q16 + (t < T - 1 ? voff0 + 1024u * t : voff_last));
+    if constexpr (G > 0) {
+      const char* q8 = (const char*)(p.q_idx8 + (int64_t)q * p.d_dlr);
+#pragma unroll
+      for (int t = 0; t < G; ++t) qx[t] = *(const uint2*)(q8 + (t < G - 1 ? xoff0 + 512u * t : xoff_last));
+    }
+  }
+  uint4 dv[P][T];
+  uint2 dx[P][G > 0 ? G : 1];
+  auto issue = [&](const int s, const uint32_t row) __attribute__((always_inline)) {
+    // (the offsets pass through an empty asm so that their zero-extension stays in this block: hoisted out of it, the loads lose the
+    // scalar-base + 32-bit-offset form and every address becomes a 64-bit vector add)
+    uint32_t v0 = voff0, v1 = voff_last, x0 = xoff0, x1 = xoff_last;
+    asm volatile("" : "+v"(v0), "+v"(v1), "+v"(x0), "+v"(x1));
+    const char* r = (const char*)(p.vals_rm + (int64_t)row * p.k_rm);
+#pragma unroll
+    for (int t = 0; t < T; ++t) dv[s][t] = gather16(r + (t < T - 1 ? v0 + 1024u * t : v1));
+    if constexpr (G > 0) {
+      const char* x = (const char*)p.c_idx + (int64_t)row * p.d_dlr;
+#pragma unroll
+      for (int t = 0; t < G; ++t) dx[s][t] = gather8(x + (t < G - 1 ? x0 + 512u * t : x1));
+    }
+  };
+  const uint32_t one = 0x00010001u;
+  auto chunk = [&](double acc, const int s, const int t) __attribute__((always_inline)) -> double {
+    uint32_t d[4] = {dv[s][t].x, dv[s][t].y, dv[s][t].z, dv[s][t].w};
+    const uint32_t qq[4] = {qv[t].x, qv[t].y, qv[t].z, qv[t].w};
+    if (t < G) {
+      uint32_t x0 = dx[s][t].x ^ qx[t].x, x1 = dx[s][t].y ^ qx[t].y;
+      if (t == G - 1) { x0 &= gmask_last; x1 &= gmask_last; }      // an ungated lane of the boundary pass: every pair agrees
+      d[0] &= pair_mask_pk(x0, 0x0c010c00u, one); d[1] &= pair_mask_pk(x0, 0x0c030c02u, one);
+      d[2] &= pair_mask_pk(x1, 0x0c010c00u, one); d[3] &= pair_mask_pk(x1, 0x0c030c02u, one);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc += (double)fmix_lo(d[e], qq[e]);
+      acc += (double)fmix_hi(d[e], qq[e]);
+    }
+    return acc;
+  };
+#pragma unroll
+  for (int j = 0; j < P && j < NP; ++j) issue(j, (uint32_t)__builtin_amdgcn_readlane((int)row_ld, j));
+  // the query's registers are complete here, once per block: left to the compiler, the last chunk's load sinks into the predicated pass below
+#pragma unroll
+  for (int t = 0; t < T; ++t) asm volatile("" : "+v"(qv[t].x), "+v"(qv[t].y), "+v"(qv[t].z), "+v"(qv[t].w));
+  float res = 0.f;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if (j >= npairs) break;
+    const int s = j % P;
+    double acc = 0.0;
+#pragma unroll
+    for (int t = 0; t < T - 1; ++t) acc = chunk(acc, s, t);
+    if (live_last) acc = chunk(acc, s, T - 1);
+    __builtin_amdgcn_sched_barrier(0);      // the slot's registers are free from here: hoisted above the adds, the loads would need a slot of their own
+    if (j + P < NP) issue(s, (uint32_t)__builtin_amdgcn_readlane((int)row_ld, j + P));
+    acc = wave_sum_f64_swz(acc);
+    if (lane == j) res = (float)acc;
+  }
+  if (lane < npairs) {
+    const float sc = valid_own ? res : -INFINITY;
+    if (p.out_keys) p.out_keys[(int64_t)q * p.ld_keys + i_own] = valid_own ? make_key(sc, row_own) : 0ull;
+    if (p.out_scores && q < p.n_queries) p.out_scores[(int64_t)q * p.ld_scores + i_own] = sc;
+  }
+}
 // Flat launches walk the block list with a grid stride: the grid is the exact block count when the host knows it, and a fixed one when the
 // controller runs without host read-backs (the list lengths then exist in device memory only).
 #ifndef RESCORE_WPE
@@ -1673,14 +1826,18 @@ __device__ __forceinline__ bool rescore_fast_batch(const RescoreArgs& p) {
   return p.q16 && p.q_inexact[0] == 0u && p.q_inexact[1] == 0u &&
          (!p.gate || p.d_dlr == 0 || p.c_idx_dtype == DHR_IDX_U8 || p.c_idx_dtype == DHR_IDX_I8);
 }
-template <int PATH>
-__device__ __forceinline__ void rescore_run(const RescoreArgs& p) {
-  if (!p.blk_off) { rescore_block<PATH>(p, (int)blockIdx.y, blockIdx.x); return; }
+template <class F>
+__device__ __forceinline__ void rescore_for_blocks(const RescoreArgs& p, F block) {
+  if (!p.blk_off) { block((int)blockIdx.y, blockIdx.x); return; }
   for (uint32_t b = blockIdx.x;; b += gridDim.x) {
     int q; uint32_t blk;
     if (!flat_block(p.blk_off, p.n_queries, b, q, blk)) return;
-    rescore_block<PATH>(p, q, blk);
+    block(q, blk);
   }
+}
+template <int PATH>
+__device__ __forceinline__ void rescore_run(const RescoreArgs& p) {
+  rescore_for_blocks(p, [&](const int q, const uint32_t blk) __attribute__((always_inline)) { rescore_block<PATH>(p, q, blk); });
 }
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RESCORE_WPE))) rescore_kernel(RescoreArgs p) {
   if (p.split && rescore_fast_batch(p)) return;
@@ -1691,6 +1848,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RESCOR
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) rescore_fast_kernel(RescoreArgs p) {
   if (!rescore_fast_batch(p) || (p.k_rm >> 3) <= 128) return;
   rescore_run<1>(p);
+}
+// ... and its whole-row-in-flight form for the row widths launch_rescore knows (T chunks per lane, G of them with gated lanes)
+template <int T, int G>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(rescore_wide_wpe(T, G)))) rescore_fast_kernel_wide(RescoreArgs p) {
+  if (!rescore_fast_batch(p)) return;
+  rescore_for_blocks(p, [&](const int q, const uint32_t blk) __attribute__((always_inline)) { rescore_block_wide<T, G, RESCORE_WIDE_P>(p, q, blk); });
 }
 // ... the queries with at most 16 non-zero chunks of a batch that has any (stage 1 of the theta modes, BM25 queries; any index dtype)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) rescore_sparse_kernel(RescoreArgs p) {
@@ -1713,7 +1876,20 @@ hipError_t launch_rescore(const RescoreArgs& a_in, hipStream_t s) {
     if (!a.flat_blocks) return hipSuccess;
     grid = dim3(std::min<uint32_t>(a.flat_blocks, FLAT_GRID_MAX));
   } else grid = dim3((a.max_count + RESCORE_CANDS_PER_WG - 1) / RESCORE_CANDS_PER_WG, (unsigned)a.n_queries);
-  if (a.split && wide) hipLaunchKernelGGL(rescore_fast_kernel, grid, dim3(256), 0, s, a);
+  if (a.split && wide) {
+    // chunks per lane and gated passes of the row width: 3 / 4 (hybrid rows of 129-256 chunks) run the whole-row-in-flight instances,
+    // any other width the loop
+    const int nch = a.k_rm >> 3, T = (nch + 63) / 64;
+    const int G = (a.gate && a.d_dlr > 0) ? ((a.d_dlr >> 3) + 63) / 64 : 0;
+    const bool inflight = (T == 3 || T == 4) && G <= T && (a.k_rm & 7) == 0 && (a.d_dlr & 7) == 0 && a.n_rows > 0;
+    switch (inflight ? T * 8 + G : 0) {
+#define DHR_RESCORE_WIDE(T_, G_) case T_ * 8 + G_: hipLaunchKernelGGL((rescore_fast_kernel_wide<T_, G_>), grid, dim3(256), 0, s, a); break;
+      DHR_RESCORE_WIDE(3, 0) DHR_RESCORE_WIDE(3, 1) DHR_RESCORE_WIDE(3, 2) DHR_RESCORE_WIDE(3, 3)
+      DHR_RESCORE_WIDE(4, 0) DHR_RESCORE_WIDE(4, 1) DHR_RESCORE_WIDE(4, 2) DHR_RESCORE_WIDE(4, 3) DHR_RESCORE_WIDE(4, 4)
+#undef DHR_RESCORE_WIDE
+      default: hipLaunchKernelGGL(rescore_fast_kernel, grid, dim3(256), 0, s, a);
+    }
+  }
   if (a.split && !wide) hipLaunchKernelGGL(rescore_narrow_kernel, grid, dim3(256), 0, s, a);
   if (a.split) hipLaunchKernelGGL(rescore_sparse_kernel, grid, dim3(256), 0, s, a);
   hipLaunchKernelGGL(rescore_kernel, grid, dim3(256), 0, s, a);

@@ -383,6 +383,30 @@ int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logi
                               const int16_t* tokens, int64_t ld_tokens, void* workspace, void* grad_logits, int64_t ld_grad_batch,
                               int64_t ld_grad_token, float* grad_weights, int64_t ld_grad_weights, void* stream);
 
+/* Late-interaction (MaxSim) scores with their gradient (tevatron/ColBERT/modeling.py:188-190, 204-219: listwise_maxsim / pairwise_maxsim and
+ * the paired evaluation branch, which build the [A, B, Lq, Lp] similarity tensor and keep it for autograd).  q is [A, Lq, D], p is [B, Lp, D]
+ * (value_dtype DHR_VAL_F16 / DHR_VAL_F32, both sides alike; strides ld_*_batch / ld_*_tok / 1 in elements: a [:, 1:] view is read in place).
+ * group = 0: every pair, cols = B; group = n > 0: passage row a * n + j belongs to query a, B == A * n, cols = n.  There is no mask: padded
+ * tokens are zero vectors and take part with similarity 0, as in the reference.
+ *   forward   out[a][col] = sum_i max_j <q[a][i], p[b][j]>, fp32 products and sums whatever the input dtype (fp32 inputs are never rounded
+ *             to fp16), fp32 [A, cols] (row stride ld_out).  arg, if not NULL, receives int16 [A][cols][Lq] (packed): the FIRST j that
+ *             attains the maximum.
+ *   backward  with grad_out = dL/d out (fp32, row stride ld_grad) and arg as the forward left it:
+ *             dq[a][i] = sum_b grad_out[a][b] * p[b][arg[a][b][i]],   dp[b][j] = sum_a grad_out[a][b] * sum over {i : arg[a][b][i] == j} of q[a][i]
+ *             over the scored pairs, packed [A, Lq, D] / [B, Lp, D] in grad_dtype (fp32 sums, rounded once for DHR_VAL_F16); every row is
+ *             written, zeros where nothing was routed.  Either may be NULL and is then not computed.
+ * Every sum runs in a fixed order that depends on the shape alone (no atomics): two calls are bit-identical, and the score of a pair does
+ * not depend on which other pairs are scored.  For device arrays the library allocates nothing and the calls ENQUEUE on `stream` and return
+ * without waiting; host arrays are staged through the device and are complete on return.  DHR_ERR_INVALID for NULL / non-positive sizes /
+ * unknown dtypes / strides shorter than D / B != A * group; DHR_ERR_UNSUPPORTED beyond D <= 1024, Lp <= 32767, 131072 rows on a side. */
+int dhr_maxsim_scores(int32_t device, int32_t mem_kind, const void* q, int64_t ld_q_tok, int64_t ld_q_batch, int64_t A, int64_t Lq, const void* p,
+                      int64_t ld_p_tok, int64_t ld_p_batch, int64_t B, int64_t Lp, int32_t D, int32_t value_dtype, int32_t group, float* out,
+                      int64_t ld_out, int16_t* arg, void* stream);
+int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, const void* q, int64_t ld_q_tok, int64_t ld_q_batch, int64_t A, int64_t Lq,
+                               const void* p, int64_t ld_p_tok, int64_t ld_p_batch, int64_t B, int64_t Lp, int32_t D, int32_t value_dtype,
+                               int32_t group, const int16_t* arg, const float* grad_out, int64_t ld_grad, void* dq, void* dp, int32_t grad_dtype,
+                               void* stream);
+
 /* Product quantiser for the first stage of --PQIP.  The reference calls faiss
  * IndexPQ(d, M = 64, nbits = 8, METRIC_INNER_PRODUCT) (retrieval/quantize_index.py:27-37, gip_retrieval.py:167-231); faiss is not
  * part of the reference tree, so these restate its published algorithm (per-subspace Lloyd k-means, nearest-centroid codes, ADC

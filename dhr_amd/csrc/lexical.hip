@@ -17,8 +17,6 @@
 
 namespace {
 
-enum { MODE_RAW = 0, MODE_DENSIFY = 1, MODE_AGG_FULL = 2, MODE_AGG_SEMI = 3 };
-
 struct FoldArgs {
   int64_t ld_batch, ld_token;
   int T, V;
@@ -34,10 +32,6 @@ struct FoldArgs {
   int idx_i16;
   int64_t ld_idx;
 };
-
-template <typename TIN> struct Pair;
-template <> struct Pair<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(2))); };
-template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
 
 template <typename TIN, int MODE>
 __global__ void __launch_bounds__(256) lexical_fold_kernel(const TIN* __restrict__ logits, FoldArgs a) {
@@ -108,7 +102,7 @@ __global__ void __launch_bounds__(256) lexical_fold_kernel(const TIN* __restrict
     if (sl != 0 || !live) continue;
     if (MODE == MODE_AGG_FULL) {
       const float pos = best0, neg = best1;
-      const float tok = pos * (float)(pos > neg) - neg * (float)(pos <= neg);
+      const float tok = agg_full_value(pos, neg);
       if (a.val_f32) ((float*)a.out_val)[b * a.ld_val + pair] = tok;
       else ((__half*)a.out_val)[b * a.ld_val + pair] = __float2half(tok);
       continue;
@@ -145,10 +139,6 @@ __global__ void __launch_bounds__(256) lexical_cls_kernel(const void* __restrict
   }
 }
 
-struct Geometry {
-  int out_cols, W, n_groups, remove;
-};
-
 hipError_t launch_fold(const void* logits, int in_f32, int mode, const FoldArgs& a0, hipStream_t s) {
   FoldArgs a = a0;
   a.GS = a.n_groups >= 8 ? 8 : a.n_groups >= 4 ? 4 : a.n_groups >= 2 ? 2 : 1;
@@ -167,24 +157,6 @@ hipError_t launch_fold(const void* logits, int in_f32, int mode, const FoldArgs&
 #undef DHR_FOLD_MODES
 #undef DHR_FOLD
   return hipGetLastError();
-}
-
-// validates mode / dims / remove against the vocabulary; the geometry of the view the epilogue folds
-int geometry(int mode, int vocab, int dims, int remove, Geometry& g) {
-  if (mode == MODE_RAW) { g = {vocab, vocab, 1, 0}; return DHR_OK; }
-  if (mode != MODE_DENSIFY && mode != MODE_AGG_FULL && mode != MODE_AGG_SEMI) return set_error(DHR_ERR_INVALID, "bad lexical mode");
-  if (dims <= 0) return set_error(DHR_ERR_INVALID, "dims must be > 0");
-  if (mode == MODE_AGG_FULL && dims > (1 << 29)) return set_error(DHR_ERR_INVALID, "dims too large");
-  const int64_t W = mode == MODE_AGG_FULL ? 2 * (int64_t)dims : dims;
-  if (remove < 0 && mode != MODE_AGG_FULL) return set_error(DHR_ERR_INVALID, "remove_dims must be >= 0 (negative values pad, aggregate(full) only)");
-  const int64_t cols = remove >= 0 ? (int64_t)vocab - remove : (int64_t)vocab - (int64_t)remove;
-  if (cols <= 0 || cols % W != 0) {
-    if (mode == MODE_DENSIFY) return set_error(DHR_ERR_INVALID, "Input lexical representation cannot be densified, please fix dims or remove_dims");
-    return set_error(DHR_ERR_INVALID, "the vocabulary after remove_dims is not a whole number of groups");
-  }
-  if (cols / W > 32767) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 groups");
-  g = {dims, (int)W, (int)(cols / W), remove};
-  return DHR_OK;
 }
 
 int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }

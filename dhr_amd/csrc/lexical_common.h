@@ -1,5 +1,7 @@
-// What the two translation units of the lexical head share (lexical.hip: encoding, lexical_train.hip: training): the 16-byte row walk and
-// lexical_stats_kernel, the per-token softmax statistics.  One definition, so the training forward is bit-identical to the encoding one.
+// What the translation units of the lexical head share (lexical.hip: encoding, lexical_train.hip: training, aggretriever_train.hip: the
+// Aggretriever training ops): the 16-byte row walk and lexical_stats_kernel, the per-token softmax statistics; the geometry of the grouped
+// views and the signed fold of aggregate(full); the 4-byte-aligned column vectors of the streaming passes.  One definition each, so the
+// training forwards are bit-identical to the encoding ones.
 #pragma once
 #include "dhr_state.h"
 
@@ -38,6 +40,72 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// two adjacent columns of a row as one load
+template <typename TIN> struct Pair;
+template <> struct Pair<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(2))); };
+template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
+
+template <typename T_, int N> struct VecA4;     // N elements, aligned to 4 bytes (what a multi-dword global access needs)
+template <int N> struct VecA4<_Float16, N> { typedef _Float16 type __attribute__((ext_vector_type(N), aligned(4))); };
+template <int N> struct VecA4<float, N> { typedef float type __attribute__((ext_vector_type(N), aligned(4))); };
+template <int N> struct VecA4<int16_t, N> { typedef int16_t type __attribute__((ext_vector_type(N), aligned(4))); };
+
+// N adjacent columns of a row: one multi-dword access where VEC and all N are inside the row, element-wise otherwise
+template <typename T_, bool VEC, int N>
+__device__ __forceinline__ void load_cols(const T_* __restrict__ p, int n, T_ (&out)[N]) {
+  if (VEC && n == N) {
+    const typename VecA4<T_, N>::type v = *reinterpret_cast<const typename VecA4<T_, N>::type*>(p);
+#pragma unroll
+    for (int u = 0; u < N; ++u) out[u] = v[u];
+  } else {
+#pragma unroll
+    for (int u = 0; u < N; ++u) out[u] = u < n ? p[u] : (T_)0;
+  }
+}
+template <typename T_, bool VEC, int N>
+__device__ __forceinline__ void store_cols(T_* __restrict__ p, int n, const T_ (&in)[N]) {
+  if (VEC && n == N) {
+    typename VecA4<T_, N>::type v;
+#pragma unroll
+    for (int u = 0; u < N; ++u) v[u] = in[u];
+    *reinterpret_cast<typename VecA4<T_, N>::type*>(p) = v;
+  } else {
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+      if (u < n) p[u] = in[u];
+  }
+}
+
+// aggregate(full) of tevatron/Aggretriever/utils.py:32-37 on the maxima of an even / odd column pair, with its signs of zero
+__device__ __forceinline__ float agg_full_value(float pos, float neg) {
+#pragma clang fp contract(off)
+  return pos * (float)(pos > neg) - neg * (float)(pos <= neg);
+}
+
+enum { MODE_RAW = 0, MODE_DENSIFY = 1, MODE_AGG_FULL = 2, MODE_AGG_SEMI = 3 };
+
+struct Geometry {
+  int out_cols, W, n_groups, remove;
+};
+
+// validates mode / dims / remove against the vocabulary; the geometry of the view the epilogue folds
+inline int geometry(int mode, int vocab, int dims, int remove, Geometry& g) {
+  if (mode == MODE_RAW) { g = {vocab, vocab, 1, 0}; return DHR_OK; }
+  if (mode != MODE_DENSIFY && mode != MODE_AGG_FULL && mode != MODE_AGG_SEMI) return set_error(DHR_ERR_INVALID, "bad lexical mode");
+  if (dims <= 0) return set_error(DHR_ERR_INVALID, "dims must be > 0");
+  if (mode == MODE_AGG_FULL && dims > (1 << 29)) return set_error(DHR_ERR_INVALID, "dims too large");
+  const int64_t W = mode == MODE_AGG_FULL ? 2 * (int64_t)dims : dims;
+  if (remove < 0 && mode != MODE_AGG_FULL) return set_error(DHR_ERR_INVALID, "remove_dims must be >= 0 (negative values pad, aggregate(full) only)");
+  const int64_t cols = remove >= 0 ? (int64_t)vocab - remove : (int64_t)vocab - (int64_t)remove;
+  if (cols <= 0 || cols % W != 0) {
+    if (mode == MODE_DENSIFY) return set_error(DHR_ERR_INVALID, "Input lexical representation cannot be densified, please fix dims or remove_dims");
+    return set_error(DHR_ERR_INVALID, "the vocabulary after remove_dims is not a whole number of groups");
+  }
+  if (cols / W > 32767) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 groups");
+  g = {dims, (int)W, (int)(cols / W), remove};
+  return DHR_OK;
 }
 
 template <typename TIN>

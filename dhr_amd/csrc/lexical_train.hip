@@ -29,10 +29,6 @@ constexpr int DT = 8;         // tokens per workgroup of the streaming pass
 constexpr int DC = 8;         // adjacent columns per thread of the streaming pass
 constexpr int MAX_TOKENS = 32767;
 
-template <typename TIN> struct Pair2;
-template <> struct Pair2<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(2))); };
-template <> struct Pair2<float> { typedef float type __attribute__((ext_vector_type(2))); };
-
 // the raw mode of lexical_fold_kernel (one group, no slices) with the argmax token
 template <typename TIN>
 __global__ void __launch_bounds__(256) lexical_fold_tok_kernel(const TIN* __restrict__ logits, int64_t ld_batch, int64_t ld_token, int T, int V,
@@ -53,7 +49,7 @@ __global__ void __launch_bounds__(256) lexical_fold_tok_kernel(const TIN* __rest
       if (s.w != 0.f) {
         const TIN* p = xb + (int64_t)t * ld_token + c0;
         if (vec) {
-          const typename Pair2<TIN>::type v = *reinterpret_cast<const typename Pair2<TIN>::type*>(p);
+          const typename Pair<TIN>::type v = *reinterpret_cast<const typename Pair<TIN>::type*>(p);
           x0 = (float)v.x; x1 = (float)v.y;
         } else {
           if (in0) x0 = (float)p[0];
@@ -123,36 +119,6 @@ __global__ void __launch_bounds__(256) lexical_route_sum_kernel(const TIN* __res
       A[b * T + t0 + k] = a;
       if (dw) dw[b * ld_dw + t0 + k] = sh_st[k].w * a;
     }
-  }
-}
-
-template <typename T_, int N> struct VecA4;     // N elements, aligned to 4 bytes (what a multi-dword global access needs)
-template <int N> struct VecA4<_Float16, N> { typedef _Float16 type __attribute__((ext_vector_type(N), aligned(4))); };
-template <int N> struct VecA4<float, N> { typedef float type __attribute__((ext_vector_type(N), aligned(4))); };
-template <int N> struct VecA4<int16_t, N> { typedef int16_t type __attribute__((ext_vector_type(N), aligned(4))); };
-
-template <typename T_, bool VEC>
-__device__ __forceinline__ void load_cols(const T_* __restrict__ p, int n, T_ (&out)[DC]) {
-  if (VEC && n == DC) {
-    const typename VecA4<T_, DC>::type v = *reinterpret_cast<const typename VecA4<T_, DC>::type*>(p);
-#pragma unroll
-    for (int u = 0; u < DC; ++u) out[u] = v[u];
-  } else {
-#pragma unroll
-    for (int u = 0; u < DC; ++u) out[u] = u < n ? p[u] : (T_)0;
-  }
-}
-template <typename T_, bool VEC>
-__device__ __forceinline__ void store_cols(T_* __restrict__ p, int n, const T_ (&in)[DC]) {
-  if (VEC && n == DC) {
-    typename VecA4<T_, DC>::type v;
-#pragma unroll
-    for (int u = 0; u < DC; ++u) v[u] = in[u];
-    *reinterpret_cast<typename VecA4<T_, DC>::type*>(p) = v;
-  } else {
-#pragma unroll
-    for (int u = 0; u < DC; ++u)
-      if (u < n) p[u] = in[u];
   }
 }
 

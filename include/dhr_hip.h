@@ -383,6 +383,51 @@ int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logi
                               const int16_t* tokens, int64_t ld_tokens, void* workspace, void* grad_logits, int64_t ld_grad_batch,
                               int64_t ld_grad_token, float* grad_weights, int64_t ld_grad_weights, void* stream);
 
+/* The Aggretriever TRAINING ops that follow the encoder, forward and backward: aggregate under autograd (tevatron/Aggretriever/utils.py:16-44 at
+ * modeling.py:173-174) and the head without the MLM logits (--skip_mlm, modeling.py:279-284, 311-316), which the reference computes by
+ * scattering the term weights into a zero [batch, L, 30522] tensor and taking the max over tokens.  Both are selections -- every output is an
+ * input value, its negation or zero -- so parity with the reference is equality.  Device arrays only (DHR_ERR_UNSUPPORTED for DHR_MEM_HOST),
+ * enqueued on `stream` without waiting, nothing allocated.
+ *   dhr_aggregate_train            dhr_aggregate (the same arguments, the same bits in `out`) which also writes route int16 [batch, dims] (row
+ *                                  stride ld_route; NULL: not written).  With groups of W columns from remove_dims (W = 2 * dims for full != 0,
+ *                                  else dims; a negative remove_dims pads zero columns at the end) and m[b][c] = max_g lexical[b][remove + g * W + c]
+ *                                  at its FIRST group g[b][c]:
+ *                                    full == 0:  out[b][j] = m[b][j],  route[b][j] = g[b][j]
+ *                                    full != 0:  pos = m[b][2j], neg = m[b][2j + 1], s = (pos > neg ? 0 : 1),
+ *                                                out[b][j] = pos * (pos > neg) - neg * (pos <= neg),  route[b][j] = 2 * g[b][2j + s] + s
+ *                                  A winner may lie in the zero padding.
+ *   dhr_aggregate_backward         with grad_out = dL/d out ([batch, dims], grad_dtype DHR_VAL_F16 / DHR_VAL_F32) and route as the forward left
+ *                                  it, grad_lexical [batch, vocab] (the same dtype) gets, in one pass over the whole row, without atomics,
+ *                                    full == 0:  grad_out[b][j] at column remove + route[b][j] * dims + j
+ *                                    full != 0:  (s == 0 ? +1 : -1) * grad_out[b][j] at column remove + (route[b][j] >> 1) * 2 * dims + 2j + s,  s = route[b][j] & 1
+ *                                  and zero in every other column, the removed leading ones included.  Nothing is written for a winner in
+ *                                  the padding.
+ *   dhr_term_weight_head           input_ids is the model's [batch, skip_tokens + n_tokens] ids (id_bytes 4: int32, 8: int64; row stride ld_ids),
+ *                                  the first skip_tokens take no part; term_weights is [batch, n_tokens] (value_dtype DHR_VAL_F16 / DHR_VAL_F32).
+ *                                    out_reps[b][v]   = max(0, max over {t : ids[b][skip + t] == v} of w[b][t])                 fp32 [batch, vocab]
+ *                                    out_tokens[b][v] = the first t that attains a strictly positive maximum, -1 where the zero wins  int16
+ *                                  Every column of both rows is written.  There is no mask: a padding token deposits its weight at its own id,
+ *                                  as in the reference.  Ids outside [0, vocab) are ignored and never used as an index.  The result does not
+ *                                  depend on the order in which repeated ids are met: two calls are bit-identical.
+ *   dhr_term_weight_head_backward  with grad_reps = dL/d reps (fp32 [batch, vocab]) and tokens as the forward left them:
+ *                                    grad_weights[b][t] = (tokens[b][v] == t ? grad_reps[b][v] : 0),  v = ids[b][skip + t];  0 for an id outside
+ *                                  the vocabulary.  Every entry of [batch, n_tokens] (grad_dtype, row stride ld_grad_weights) is written.
+ * DHR_ERR_INVALID for NULL / non-positive sizes / unknown dtypes / strides shorter than the row / a vocabulary that does not split into whole
+ * groups; DHR_ERR_UNSUPPORTED for more than 16383 groups (2 * g + 1 must fit the route) or more than 32767 tokens. */
+int dhr_aggregate_train(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
+                        int32_t dims, int32_t remove_dims, int32_t full, void* out, int32_t out_dtype, int64_t ld_out, int16_t* route,
+                        int64_t ld_route, void* stream);
+int dhr_aggregate_backward(int32_t device, int32_t mem_kind, const void* grad_out, int32_t grad_dtype, int64_t ld_grad_out, const int16_t* route,
+                           int64_t ld_route, int64_t batch, int32_t vocab, int32_t dims, int32_t remove_dims, int32_t full, void* grad_lexical,
+                           int64_t ld_grad, void* stream);
+int dhr_term_weight_head(int32_t device, int32_t mem_kind, const void* input_ids, int32_t id_bytes, int64_t ld_ids, const void* term_weights,
+                         int32_t value_dtype, int64_t ld_weights, int64_t batch, int32_t n_tokens, int32_t skip_tokens, int32_t vocab,
+                         float* out_reps, int64_t ld_reps, int16_t* out_tokens, int64_t ld_tokens, void* stream);
+int dhr_term_weight_head_backward(int32_t device, int32_t mem_kind, const void* input_ids, int32_t id_bytes, int64_t ld_ids, int64_t batch,
+                                  int32_t n_tokens, int32_t skip_tokens, int32_t vocab, const float* grad_reps, int64_t ld_grad_reps,
+                                  const int16_t* tokens, int64_t ld_tokens, void* grad_weights, int32_t grad_dtype, int64_t ld_grad_weights,
+                                  void* stream);
+
 /* Late-interaction (MaxSim) scores with their gradient (tevatron/ColBERT/modeling.py:188-190, 204-219: listwise_maxsim / pairwise_maxsim and
  * the paired evaluation branch, which build the [A, B, Lq, Lp] similarity tensor and keep it for autograd).  q is [A, Lq, D], p is [B, Lp, D]
  * (value_dtype DHR_VAL_F16 / DHR_VAL_F32, both sides alike; strides ld_*_batch / ld_*_tok / 1 in elements: a [:, 1:] view is read in place).

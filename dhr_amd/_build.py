@@ -14,7 +14,7 @@ import subprocess
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libdhr_hip.so")
 OBJDIR = os.path.join(CSRC, "build")
-SOURCES = ["abi.cpp", "kernels.hip", "gemm_w4.hip", "gemm_g8.hip", "index_build.hip", "search_core.hip", "api.hip", "sharded.hip", "pq_adc.hip", "select_global.hip", "host_io.hip", "lexical.hip", "gip_train.hip", "lexical_train.hip", "maxsim.hip", "aggretriever_train.hip"]
+SOURCES = ["abi.cpp", "kernels.hip", "gemm_w4.hip", "gemm_g8.hip", "index_build.hip", "search_core.hip", "api.hip", "sharded.hip", "pq_adc.hip", "select_global.hip", "host_io.hip", "lexical.hip", "gip_train.hip", "lexical_train.hip", "maxsim.hip", "aggretriever_train.hip", "lexical_proj.hip"]
 HEADERS = ["dhr_internal.h", "dhr_state.h", "abi_guard.h", "libdhr.map", "gemm_common.h", "gemm_g8.h", "lexical_common.h", os.path.join("..", "..", "include", "dhr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 # A/B builds only (DHR_AB_VARIANTS=1 in the environment of the build, tools/ab_build.sh): the retired persistent-workgroup form of the integer
@@ -57,7 +57,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 return LIB
             hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
             newest_header = max(_mtime(os.path.join(CSRC, h)) for h in HEADERS)
-            with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+            with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1, 16)) as ex:
                 objs = list(ex.map(lambda s: _compile(hipcc, s, newest_header, force, verbose), SOURCES))
             tmp = LIB + ".tmp.%d" % os.getpid()
             cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "libdhr.map"), "-o", tmp] + objs + ["-L/opt/rocm/lib", "-lrccl"]

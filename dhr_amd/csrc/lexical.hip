@@ -163,6 +163,25 @@ int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
 
 }  // namespace
 
+// declared in lexical_common.h: the epilogues above on fp32 reps that another translation unit computed (lexical_proj.hip)
+hipError_t dhr::lexical_record_from_reps(const float* reps, int64_t ld_reps, int mode, int64_t batch, int vocab, int out_cols, int W, int n_groups,
+                                         int remove, void* out_val, int val_f32, int64_t ld_val, void* out_idx, int idx_i16, int64_t ld_idx,
+                                         const void* cls, int cls_f32, int64_t ld_cls, int cls_dim, hipStream_t s) {
+  if (reps) {
+    FoldArgs a{};
+    a.ld_batch = ld_reps; a.ld_token = vocab; a.T = 1; a.V = vocab; a.stats = nullptr;
+    a.remove = remove; a.W = W; a.n_groups = n_groups; a.batch = batch;
+    a.out_val = out_val; a.val_f32 = val_f32; a.ld_val = ld_val; a.out_idx = out_idx; a.idx_i16 = idx_i16; a.ld_idx = ld_idx;
+    const hipError_t e = launch_fold(reps, 1, mode, a, s);
+    if (e != hipSuccess) return e;
+  }
+  if (cls_dim > 0) {
+    const unsigned blocks = (unsigned)std::min<int64_t>((batch * cls_dim + 255) / 256, 4096);
+    hipLaunchKernelGGL(lexical_cls_kernel, dim3(blocks), dim3(256), 0, s, cls, cls_f32, ld_cls, cls_dim, batch, out_val, val_f32, ld_val, out_cols);
+  }
+  return hipGetLastError();
+}
+
 extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void* logits, int32_t logits_dtype, int64_t batch,
                                 int32_t n_tokens, int32_t vocab, int64_t ld_batch, int64_t ld_token, const float* term_weights, int64_t ld_weights,
                                 const float* mask, int64_t ld_mask, int32_t dims, int32_t remove_dims, void* out_value, int32_t out_value_dtype,

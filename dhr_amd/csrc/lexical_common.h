@@ -5,6 +5,15 @@
 #pragma once
 #include "dhr_state.h"
 
+namespace dhr {
+// lexical.hip: its record epilogues (lexical_fold_kernel without statistics, lexical_cls_kernel) on fp32 reps [batch, vocab] (row stride
+// ld_reps) that the caller computed on the device: raw / densify / aggregate into the record's value and index rows, then the [CLS] columns
+// at out_cols.  reps == NULL: the reps already are the fp32 value rows (raw), only the [CLS] columns are written.  Enqueues on s.
+hipError_t lexical_record_from_reps(const float* reps, int64_t ld_reps, int mode, int64_t batch, int vocab, int out_cols, int W, int n_groups,
+                                    int remove, void* out_val, int val_f32, int64_t ld_val, void* out_idx, int idx_i16, int64_t ld_idx,
+                                    const void* cls, int cls_f32, int64_t ld_cls, int cls_dim, hipStream_t s);
+}  // namespace dhr
+
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));

@@ -325,6 +325,26 @@ int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void*
 int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
                   int32_t dims, int32_t remove_dims, int32_t full, void* out, int32_t out_dtype, int64_t ld_out, void* stream);
 
+/* dhr_lexical_head with the vocabulary projection in front of it fused in, for ENCODING (forward only): the MLM logits
+ *   x[b][t][v] = sum_k hidden[b][t][k] * weight[v][k] + bias[v]      (fp32 products and sums, never rounded to fp16)
+ * are never written to memory, and masked tokens are never multiplied.  hidden is [batch, n_tokens, hidden_dim] (value_dtype DHR_VAL_F16,
+ * strides ld_batch / ld_token / 1: the [:, 1:] view of the projector's input, read in place; hidden_dim a multiple of 8), weight is
+ * [vocab, hidden_dim] of the same dtype (row stride ld_weight), bias [vocab] (bias_dtype DHR_VAL_F16 / DHR_VAL_F32) or NULL.  term_weights,
+ * mask, mode, dims, remove_dims and every output argument are those of dhr_lexical_head, and so is what is written: reps, ties (the first
+ * token, the first group) and the signs of zero; a masked token enters as (p * w) * 0.  DHR_LEX_RAW writes fp32 only.
+ * Device memory only (mem_kind DHR_MEM_DEVICE).  The library allocates nothing: the caller passes dhr_lexical_proj_workspace(batch, n_tokens,
+ * vocab, mode) bytes of device memory (at most 4 * batch * vocab + 256 * batch * n_tokens + 65536), aligned to 16 bytes.  The call ENQUEUES
+ * on `stream` and returns without waiting.  No atomics: two calls on the same arguments are bit-identical.  NaN / inf are out of scope.
+ * DHR_ERR_INVALID for NULL pointers, negative sizes, hidden_dim not a multiple of 8, unknown dtypes, host memory, a workspace that is too small,
+ * a vocabulary that does not split into whole groups; DHR_ERR_UNSUPPORTED for fp32 operands and fp16 raw reps. */
+int64_t dhr_lexical_proj_workspace(int64_t batch, int32_t n_tokens, int32_t vocab, int32_t mode);
+int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t mode, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens,
+                          int32_t hidden_dim, int64_t ld_batch, int64_t ld_token, const void* weight, int32_t vocab, int64_t ld_weight,
+                          const void* bias, int32_t bias_dtype, const float* term_weights, int64_t ld_weights, const float* mask, int64_t ld_mask,
+                          int32_t dims, int32_t remove_dims, void* out_value, int32_t out_value_dtype, int64_t ld_value, void* out_index,
+                          int32_t index_dtype, int64_t ld_index, const void* cls, int32_t cls_dtype, int64_t ld_cls, int32_t cls_dim,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The gated inner product of a training step and of the in-model reranker, with its gradient (tevatron/DHR/modeling.py:161-170, 212-226,
  * 250-285: listwise_gip_scores / pairwise_gip_scores, which repeat the passage batch once per query and keep [n_q, n_p, dims] tensors for
  * autograd).  q_value [n_q, dims] and p_value [n_p, dims] are densified values (value_dtype DHR_VAL_F16 / DHR_VAL_F32, both sides alike, row

@@ -1,0 +1,411 @@
+// What lexical_proj.hip (encoding) and lexical_proj_train.hip (training) share: the arguments, the compaction of the unmasked token rows, the
+// staged MFMA tile product, the softmax statistics pass with its combine, and the fold.  One definition each, so the training forward is
+// bit-identical to the encoding one.
+#pragma once
+#include "lexical_common.h"
+
+// Internal linkage on purpose: each translation unit that includes this header compiles its own copy of the kernels below, the non-template
+// ones (count, scan, fill, statistics, combine) included.  The duplication costs code size only and keeps the launches free of cross-unit symbols.
+namespace {
+
+constexpr int TM = 64;                 // token rows of a tile
+constexpr int TN = 256;                // vocabulary columns of a tile: 64 per wave
+constexpr int BK = 64;                 // columns of H staged per step (128 bytes of a row)
+constexpr int PITCH = 2 * BK + 16;     // LDS pitch of a staged row: the 16-byte reads of 16 consecutive rows fall on 16 different slots
+constexpr int MAX_SPLIT = 16;          // shares of the vocabulary in the statistics pass
+constexpr int FILL_WGS = 1024;         // workgroups the statistics pass wants
+constexpr int GROUP_ROWS = 1024;       // token rows (before masking) a fold workgroup owns at least
+
+typedef float float16v __attribute__((ext_vector_type(16)));
+
+struct ProjArgs {
+  const _Float16* hid;
+  int64_t ld_hb, ld_ht;
+  const _Float16* wgt;
+  int64_t ld_w;
+  const void* bias;                    // NULL: none
+  int bias_f32;
+  const float* tw;
+  int64_t ld_tw;
+  const float* mask;
+  int64_t ld_mask;
+  int64_t B;
+  int T, H, V;
+  int vec_h, vec_w;                    // 16-byte loads are aligned
+  int n_split, n_ntiles, group;        // shares / vocabulary tiles of the statistics pass; passages per fold workgroup
+  int* hdr;                            // [0]: unmasked token rows M
+  int* cnt;                            // [B] unmasked tokens
+  int* start;                          // [B + 1] first row of a passage in the list
+  int* tmask;                          // [B] first masked token, -1: none
+  int* rows;                           // [M] b * T + t
+  float4* stats;                       // [M] (max, sum, w, mask)
+  float2* part;                        // [n_split][B * T] (max, sum)
+  float* reps;
+  int64_t ld_reps;
+  int16_t* tok;                        // training only: [B, V] the first maximising token and its p
+  int64_t ld_tok;
+  float* pwin;
+  int64_t ld_pwin;
+};
+
+__global__ void __launch_bounds__(64) proj_count_kernel(ProjArgs a) {
+  const int64_t b = blockIdx.x;
+  const float* m = a.mask + b * a.ld_mask;
+  int n = 0, first = a.T;
+  for (int t = threadIdx.x; t < a.T; t += 64) {
+    if (m[t] != 0.f) ++n;
+    else first = min(first, t);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n += __shfl_xor(n, o, 64);
+    first = min(first, __shfl_xor(first, o, 64));
+  }
+  if (threadIdx.x == 0) {
+    a.cnt[b] = n;
+    a.tmask[b] = first < a.T ? first : -1;
+  }
+}
+
+// one workgroup: start[b] = the unmasked tokens of the passages before b, start[B] = hdr[0] = all of them
+__global__ void __launch_bounds__(256) proj_scan_kernel(ProjArgs a) {
+  __shared__ int sums[256];
+  const int64_t per = (a.B + 255) / 256;
+  const int64_t lo = min(a.B, (int64_t)threadIdx.x * per), hi = min(a.B, lo + per);
+  int s = 0;
+  for (int64_t b = lo; b < hi; ++b) s += a.cnt[b];
+  sums[threadIdx.x] = s;
+  __syncthreads();
+  int base = 0;
+  for (int k = 0; k < (int)threadIdx.x; ++k) base += sums[k];
+  for (int64_t b = lo; b < hi; ++b) {
+    a.start[b] = base;
+    base += a.cnt[b];
+  }
+  if (threadIdx.x == 255) {
+    a.start[a.B] = base;
+    a.hdr[0] = base;
+  }
+}
+
+__global__ void __launch_bounds__(64) proj_fill_kernel(ProjArgs a) {
+  const int64_t b = blockIdx.x;
+  const float* m = a.mask + b * a.ld_mask;
+  int* out = a.rows + a.start[b];
+  int base = 0;
+  for (int t0 = 0; t0 < a.T; t0 += 64) {
+    const int t = t0 + threadIdx.x;
+    const bool on = t < a.T && m[t] != 0.f;
+    const unsigned long long live = __ballot(on);
+    if (on) out[base + __popcll(live & ((1ull << threadIdx.x) - 1))] = (int)(b * a.T + t);
+    base += __popcll(live);
+  }
+}
+
+__device__ __forceinline__ uint4 load16h(const _Float16* p, bool vec) {
+  if (vec) return *reinterpret_cast<const uint4*>(p);
+  union { uint4 u; _Float16 t[8]; } r;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) r.t[e] = p[e];
+  return r.u;
+}
+
+__device__ __forceinline__ float bias_at(const ProjArgs& a, int v) {
+  if (!a.bias) return 0.f;
+  return a.bias_f32 ? ((const float*)a.bias)[v] : (float)((const _Float16*)a.bias)[v];
+}
+
+// The product of 64 staged rows `hrow` (thread t stages 16-byte slot t & 7 of rows (t >> 3) + 32 u; LDS rows [0, TM)) and 256 staged rows
+// `wrow` (LDS rows [TM, TM + TN)) over all of H.  The caller clamps rows beyond the problem to a valid one (their results are never used);
+// columns beyond H are zeros.  W_REG: acc[i][j][k] holds w-row wave * 64 + 32 i + (8 (k >> 2) + 4 h + (k & 3)) against h-row 32 j + r;
+// otherwise h-row 32 i + (...) against w-row wave * 64 + 32 j + r (r = lane & 31, h = lane >> 5, k the accumulator register).
+template <bool W_REG>
+__device__ __forceinline__ void tile_product_rows(unsigned char* lds, int H, const _Float16* const (&hrow)[2], int vec_h,
+                                                  const _Float16* const (&wrow)[TN / 32], int vec_w, float16v (&acc)[2][2]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int slot = tid & 7, rb = tid >> 3;
+  uint4 sh[2], sw[TN / 32];
+  auto fetch = [&](int chunk) {
+    const int col = chunk * BK + slot * 8;
+    const bool in = col < H;                              // H is a multiple of 8: a slot is inside or outside as a whole
+    const int c = in ? col : 0;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      sh[u] = load16h(hrow[u] + c, vec_h);
+      if (!in) sh[u] = make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < TN / 32; ++u) {
+      sw[u] = load16h(wrow[u] + c, vec_w);
+      if (!in) sw[u] = make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.f;
+  const int n_chunks = (H + BK - 1) / BK;
+  fetch(0);
+  for (int chunk = 0; chunk < n_chunks; ++chunk) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) *reinterpret_cast<uint4*>(lds + (rb + 32 * u) * PITCH + slot * 16) = sh[u];
+#pragma unroll
+    for (int u = 0; u < TN / 32; ++u) *reinterpret_cast<uint4*>(lds + (TM + rb + 32 * u) * PITCH + slot * 16) = sw[u];
+    __syncthreads();
+    if (chunk + 1 < n_chunks) fetch(chunk + 1);
+    const int k_steps = min(BK / 16, (H - chunk * BK + 15) / 16);
+#pragma unroll
+    for (int s = 0; s < BK / 16; ++s) {
+      if (s < k_steps) {                                   // (uniform)
+        half8 hf[2], wf[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          hf[i] = *reinterpret_cast<const half8*>(lds + (32 * i + r) * PITCH + s * 32 + h * 16);
+          wf[i] = *reinterpret_cast<const half8*>(lds + (TM + wave * 64 + 32 * i + r) * PITCH + s * 32 + h * 16);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[i][j] = W_REG ? __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i], hf[j], acc[i][j], 0, 0, 0)
+                              : __builtin_amdgcn_mfma_f32_32x32x16_f16(hf[i], wf[j], acc[i][j], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+#endif
+}
+
+// tile_product_rows of the token rows hrow and the weight rows [n0, n0 + TN): TOK_LANE puts the token on the lane (weight rows in the
+// registers), otherwise the token rows are in the registers and the weight row is on the lane
+template <bool TOK_LANE>
+__device__ __forceinline__ void tile_product(unsigned char* lds, const ProjArgs& a, const _Float16* const (&hrow)[2], int n0, float16v (&acc)[2][2]) {
+  const int rb = threadIdx.x >> 3;
+  const _Float16* wrow[TN / 32];
+#pragma unroll
+  for (int u = 0; u < TN / 32; ++u) wrow[u] = a.wgt + (int64_t)min(n0 + rb + 32 * u, a.V - 1) * a.ld_w;
+  tile_product_rows<TOK_LANE>(lds, a.H, hrow, a.vec_h, wrow, a.vec_w, acc);
+}
+
+// (max, sum exp(x - max)) of two disjoint parts of a row -> of their union; a part without a column is (-inf, 0)
+__device__ __forceinline__ void softmax_merge(float& m, float& s, float m2, float s2) {
+  const float mm = fmaxf(m, m2);
+  const float a = m == -INFINITY ? 0.f : s * expf(m - mm);
+  const float b = m2 == -INFINITY ? 0.f : s2 * expf(m2 - mm);
+  m = mm;
+  s = a + b;
+}
+
+// the pointers of the two token rows a thread stages: rows row0 + (t >> 3) + 32 u of the list, clamped to [.., row_end)
+__device__ __forceinline__ void token_rows(const ProjArgs& a, int row0, int row_end, const _Float16* (&hrow)[2]) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int id = a.rows[min(row0 + (int)(threadIdx.x >> 3) + 32 * u, row_end - 1)];
+    const int b = id / a.T, t = id - b * a.T;
+    hrow[u] = a.hid + (int64_t)b * a.ld_hb + (int64_t)t * a.ld_ht;
+  }
+}
+
+// grid: (tiles of TM rows of the worst-case list, shares of the vocabulary)
+__global__ void __launch_bounds__(256) proj_stats_kernel(ProjArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char tile[(TM + TN) * PITCH];
+  __shared__ float sh_bias[TN];
+  __shared__ float2 sh_red[4][TM];
+  const int M = a.hdr[0];
+  const int m0 = blockIdx.x * TM;
+  if (m0 >= M) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+  const _Float16* hrow[2];
+  token_rows(a, m0, M, hrow);
+  const int nt_lo = (int)((int64_t)blockIdx.y * a.n_ntiles / a.n_split), nt_hi = (int)((int64_t)(blockIdx.y + 1) * a.n_ntiles / a.n_split);
+  float m_run[2] = {-INFINITY, -INFINITY}, s_run[2] = {0.f, 0.f};
+  for (int nt = nt_lo; nt < nt_hi; ++nt) {
+    const int n0 = nt * TN;
+    sh_bias[tid] = n0 + tid < a.V ? bias_at(a, n0 + tid) : -INFINITY;      // a column beyond the vocabulary: x = -inf, exp = 0
+    float16v acc[2][2];
+    tile_product<true>(tile, a, hrow, n0, acc);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      float t_max = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          acc[i][j][k] += sh_bias[wave * 64 + 32 * i + 8 * (k >> 2) + 4 * h + (k & 3)];
+          t_max = fmaxf(t_max, acc[i][j][k]);
+        }
+      if (t_max > -INFINITY) {
+        const float m_new = fmaxf(m_run[j], t_max);
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int k = 0; k < 16; ++k) sum += expf(acc[i][j][k] - m_new);
+        s_run[j] = s_run[j] * expf(m_run[j] - m_new) + sum;
+        m_run[j] = m_new;
+      }
+    }
+    __syncthreads();                                                       // sh_bias is rewritten by the next tile
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {                                            // the lane halves: h = 0 first
+    const float om = __shfl_xor(m_run[j], 32, 64), os = __shfl_xor(s_run[j], 32, 64);
+    float m = h ? om : m_run[j], s = h ? os : s_run[j];
+    softmax_merge(m, s, h ? m_run[j] : om, h ? s_run[j] : os);
+    if (h == 0) sh_red[wave][32 * j + r] = make_float2(m, s);
+  }
+  __syncthreads();
+  if (tid < TM && m0 + tid < M) {
+    float m = sh_red[0][tid].x, s = sh_red[0][tid].y;
+    for (int w = 1; w < 4; ++w) softmax_merge(m, s, sh_red[w][tid].x, sh_red[w][tid].y);   // in wave order
+    a.part[(int64_t)blockIdx.y * (a.B * a.T) + m0 + tid] = make_float2(m, s);
+  }
+}
+
+__global__ void __launch_bounds__(256) proj_combine_kernel(ProjArgs a) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= a.hdr[0]) return;
+  const int id = a.rows[row];
+  const int64_t b = id / a.T;
+  const int t = id - (int)b * a.T;
+  const int64_t ld = a.B * a.T;
+  float m = -INFINITY;
+  for (int k = 0; k < a.n_split; ++k) m = fmaxf(m, a.part[k * ld + row].x);
+  double s = 0.0;                                        // in share order, fp64: rounded to fp32 once
+  for (int k = 0; k < a.n_split; ++k) {
+    const float2 p = a.part[k * ld + row];
+    if (p.x > -INFINITY) s += (double)p.y * exp((double)p.x - (double)m);
+  }
+  a.stats[row] = make_float4(m, (float)s, a.tw[b * a.ld_tw + t], a.mask[b * a.ld_mask + t]);
+}
+
+enum { ROW_LIVE = 1, ROW_FIRST = 2, ROW_LAST = 4, ROW_Z_BEFORE = 8, ROW_Z_AFTER = 16 };
+
+// grid: (blocks of TN vocabulary columns, groups of a.group passages).  TRAIN: also the first maximising token of every (passage, column),
+// counted like the mask's columns, and its p (a masked token that wins is named like any other, with p = 0: it is never multiplied)
+template <bool TRAIN>
+__global__ void __launch_bounds__(256) proj_fold_kernel(ProjArgs a) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) unsigned char tile[(TM + TN) * PITCH];
+  __shared__ float4 sh_st[TM];
+  __shared__ int sh_flag[TM];
+  __shared__ float sh_z[TM];
+  __shared__ int sh_b[TM];
+  __shared__ int sh_t[TM], sh_tm[TM];                    // TRAIN: the row's token and its passage's first masked token
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
+  const int n0 = blockIdx.x * TN, col = n0 + tid;        // after the swap a lane owns column wave * 64 + lane of the block
+  const bool col_on = col < a.V;
+  const float bias = col_on ? bias_at(a, col) : 0.f;
+  const int64_t b_lo = (int64_t)blockIdx.y * a.group, b_hi = min(a.B, b_lo + a.group);
+  const int row_lo = a.start[b_lo], row_hi = a.start[b_hi];
+  if (col_on)
+    for (int64_t b = b_lo; b < b_hi; ++b)                // a fully masked passage: its first token's zero
+      if (a.cnt[b] == 0) {
+        a.reps[b * a.ld_reps + col] = (1.f * a.tw[b * a.ld_tw]) * 0.f;
+        if (TRAIN) {
+          a.tok[b * a.ld_tok + col] = 0;
+          a.pwin[b * a.ld_pwin + col] = 0.f;
+        }
+      }
+  float best = 0.f, best_p = 0.f;
+  int best_t = 0;
+  for (int m0 = row_lo; m0 < row_hi; m0 += TM) {
+    if (tid < TM) {
+      const int row = m0 + tid;
+      int flag = 0, bb = 0, tt = 0, tmm = 0;
+      float z = 0.f;
+      float4 st = make_float4(0.f, 1.f, 0.f, 0.f);
+      if (row < row_hi) {
+        const int id = a.rows[row];
+        bb = id / a.T;
+        const int t = id - bb * a.T;
+        const int first = row == a.start[bb], last = row == a.start[bb + 1] - 1;
+        const int tm = a.tmask[bb];
+        tt = t; tmm = tm;
+        const int t_prev = first ? -1 : a.rows[row - 1] - bb * a.T;
+        st = a.stats[row];
+        flag = ROW_LIVE | (first ? ROW_FIRST : 0) | (last ? ROW_LAST : 0);
+        if (tm >= 0) {
+          z = (1.f * a.tw[(int64_t)bb * a.ld_tw + tm]) * 0.f;                 // (p * w) * 0 with p finite and positive
+          if (t_prev < tm && tm < t) flag |= ROW_Z_BEFORE;
+          if (last && tm > t) flag |= ROW_Z_AFTER;
+        }
+      }
+      sh_st[tid] = st; sh_flag[tid] = flag; sh_z[tid] = z; sh_b[tid] = bb;
+      if (TRAIN) { sh_t[tid] = tt; sh_tm[tid] = tmm; }
+    }
+    const _Float16* hrow[2];
+    token_rows(a, m0, row_hi, hrow);
+    float16v acc[2][2];
+    tile_product<false>(tile, a, hrow, n0, acc);          // (its first barrier publishes the row table)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        // rows 32 i + 8 q + 4 hh + e: lane half hh computed them for both column tiles; half h keeps tile h and takes the other half's
+        float lo[4], hi[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float own = h ? acc[i][1][4 * q + e] : acc[i][0][4 * q + e];
+          const float send = h ? acc[i][0][4 * q + e] : acc[i][1][4 * q + e];
+          const float recv = __shfl_xor(send, 32, 64);
+          lo[e] = h ? recv : own;
+          hi[e] = h ? own : recv;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int row = 32 * i + 8 * q + u;
+          const int flag = __builtin_amdgcn_readfirstlane(sh_flag[row]);
+          if (!(flag & ROW_LIVE)) continue;
+          const float4 s = sh_st[row];
+          const float x = (u < 4 ? lo[u & 3] : hi[u & 3]) + bias;
+          const float p = expf(x - s.x) / s.y;
+          const float c = (p * s.z) * s.w;
+          if (flag & ROW_FIRST) best = -INFINITY;
+          if (flag & ROW_Z_BEFORE) {
+            const float z = sh_z[row];
+            if (z > best) {
+              best = z;
+              if (TRAIN) { best_t = sh_tm[row]; best_p = 0.f; }
+            }
+          }
+          if (c > best) {                                 // strict: the first token keeps a tie (the sign of a zero maximum)
+            best = c;
+            if (TRAIN) { best_t = sh_t[row]; best_p = p; }
+          }
+          if (flag & ROW_LAST) {
+            if (flag & ROW_Z_AFTER) {
+              const float z = sh_z[row];
+              if (z > best) {
+                best = z;
+                if (TRAIN) { best_t = sh_tm[row]; best_p = 0.f; }
+              }
+            }
+            if (col_on) {
+              a.reps[(int64_t)sh_b[row] * a.ld_reps + col] = best;
+              if (TRAIN) {
+                a.tok[(int64_t)sh_b[row] * a.ld_tok + col] = (int16_t)best_t;
+                a.pwin[(int64_t)sh_b[row] * a.ld_pwin + col] = best_p;
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();                                      // the row table is rewritten by the next tile
+  }
+}
+
+inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+// shares of the vocabulary in the statistics pass: enough workgroups to fill the chip when there are few token rows
+inline int proj_stats_split(int64_t BT, int n_ntiles) {
+  const int64_t m_tiles = std::max<int64_t>(1, (BT + TM - 1) / TM);
+  return (int)std::min<int64_t>(std::min<int64_t>(MAX_SPLIT, n_ntiles), std::max<int64_t>(1, (FILL_WGS + m_tiles - 1) / m_tiles));
+}
+
+}  // namespace

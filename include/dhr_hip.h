@@ -403,6 +403,50 @@ int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logi
                               const int16_t* tokens, int64_t ld_tokens, void* workspace, void* grad_logits, int64_t ld_grad_batch,
                               int64_t ld_grad_token, float* grad_weights, int64_t ld_grad_weights, void* stream);
 
+/* dhr_lexical_head_train / dhr_lexical_head_backward with the vocabulary projection fused in, as dhr_lexical_proj_head fuses it for encoding:
+ * the op starts from the projector's input and returns the gradients of hidden, weight, bias and the term weights; the logits
+ *   x[r][v] = hidden[r] . weight[v] + bias[v]      (fp32 products and sums)
+ * and their gradient exist only in registers and LDS, forward and backward, and masked tokens are never multiplied.  hidden is the model's
+ * [batch, skip_tokens + n_tokens, hidden_dim] tensor (value_dtype DHR_VAL_F16, strides ld_batch / ld_token / 1, hidden_dim a multiple of 8
+ * up to 1024); the first skip_tokens tokens take no part.  weight is [vocab, hidden_dim] fp16 (row stride ld_weight), bias [vocab]
+ * (DHR_VAL_F16 / DHR_VAL_F32) or NULL, term_weights and mask fp32 [batch, n_tokens], n_tokens <= 32767.
+ *   dhr_lexical_proj_train_workspace  bytes of device memory the two calls share, aligned to 16 bytes (0 for invalid sizes; at most
+ *                                     256 * batch * n_tokens + 65536 * hidden_dim + 65536): the list of unmasked token rows and their softmax
+ *                                     statistics, written by the forward and read by the backward, and what the backward needs itself.
+ *   dhr_lexical_proj_train            out_reps fp32 [batch, vocab], bit-identical to dhr_lexical_proj_head(DHR_LEX_RAW); out_tokens int16
+ *                                     [batch, vocab], the first token that attains the maximum (counted after the skipped ones; a masked token
+ *                                     that wins is named like any other); out_pwin fp32 [batch, vocab], the softmax value of that token (0 for a
+ *                                     masked one).
+ *   dhr_lexical_proj_backward         with grad_reps = dL/d reps (fp32 [batch, vocab]), the forward's arguments, tokens, pwin and workspace as it
+ *                                     left them, A[r] = sum over {v : tokens[b][v] == t} of grad_reps[b][v] * pwin[b][v] and
+ *                                     dx[r][v] = p * ([tokens[b][v] == t] * grad_reps[b][v] * w * mask - w * mask * A):
+ *                                     grad_term_weights[b][t] = mask * A                 fp32 [batch, n_tokens]
+ *                                     grad_hidden[r][k] = sum_v dx[r][v] weight[v][k]    the WHOLE [batch, skip_tokens + n_tokens, hidden_dim]
+ *                                                         tensor (strides ld_grad_batch / ld_grad_token / 1): skipped and masked tokens are zeros
+ *                                     grad_weight[v][k] = sum_r dx[r][v] hidden[r][k]    [vocab, hidden_dim], row stride ld_grad_weight
+ *                                     grad_bias[v]      = sum_r dx[r][v]
+ *                                     each DHR_VAL_F16 or DHR_VAL_F32 (its *_dtype), rounded once from fp32 accumulators.  Any output may be NULL
+ *                                     and is then not computed (no grad_weight and no grad_bias: the weight-gradient pass does not run; no
+ *                                     grad_hidden: nor does the other GEMM pass); all NULL: DHR_OK, nothing is launched.
+ * dx is rounded to fp16 once, as the operand of the second product.  Device memory only (DHR_ERR_UNSUPPORTED for DHR_MEM_HOST), nothing is
+ * allocated, the calls ENQUEUE on `stream` and return without waiting.  No atomics, every sum in a fixed order: two calls on the same
+ * arguments are bit-identical.  DHR_ERR_INVALID for NULL pointers, bad sizes / strides / dtypes, hidden_dim not a multiple of 8, a workspace
+ * that is too small or not aligned; DHR_ERR_UNSUPPORTED for fp32 operands, hidden_dim > 1024, n_tokens > 32767. */
+int64_t dhr_lexical_proj_train_workspace(int64_t batch, int32_t n_tokens, int32_t vocab, int32_t hidden_dim);
+int dhr_lexical_proj_train(int32_t device, int32_t mem_kind, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens,
+                           int32_t skip_tokens, int32_t hidden_dim, int64_t ld_batch, int64_t ld_token, const void* weight, int32_t vocab,
+                           int64_t ld_weight, const void* bias, int32_t bias_dtype, const float* term_weights, int64_t ld_weights,
+                           const float* mask, int64_t ld_mask, float* out_reps, int64_t ld_reps, int16_t* out_tokens, int64_t ld_tokens,
+                           float* out_pwin, int64_t ld_pwin, void* workspace, int64_t workspace_bytes, void* stream);
+int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens,
+                              int32_t skip_tokens, int32_t hidden_dim, int64_t ld_batch, int64_t ld_token, const void* weight, int32_t vocab,
+                              int64_t ld_weight, const void* bias, int32_t bias_dtype, const float* term_weights, int64_t ld_weights,
+                              const float* mask, int64_t ld_mask, const float* grad_reps, int64_t ld_grad_reps, const int16_t* tokens,
+                              int64_t ld_tokens, const float* pwin, int64_t ld_pwin, void* workspace, int64_t workspace_bytes, void* grad_hidden,
+                              int32_t grad_hidden_dtype, int64_t ld_grad_batch, int64_t ld_grad_token, void* grad_weight,
+                              int32_t grad_weight_dtype, int64_t ld_grad_weight, void* grad_bias, int32_t grad_bias_dtype,
+                              float* grad_term_weights, int64_t ld_grad_term_weights, void* stream);
+
 /* The Aggretriever TRAINING ops that follow the encoder, forward and backward: aggregate under autograd (tevatron/Aggretriever/utils.py:16-44 at
  * modeling.py:173-174) and the head without the MLM logits (--skip_mlm, modeling.py:279-284, 311-316), which the reference computes by
  * scattering the term weights into a zero [batch, L, 30522] tensor and taking the max over tokens.  Both are selections -- every output is an

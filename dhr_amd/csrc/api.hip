@@ -485,10 +485,9 @@ extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical
   if (mem_kind == DHR_MEM_DEVICE) {
     HIP_TRY(launch_densify(lexical, value_dtype == DHR_VAL_F32, ld, batch, remove_dims, dims, n_groups, out_value, out_value_dtype == DHR_VAL_F32,
                            ld_value, out_index, index_dtype == DHR_IDX_I16, ld_index, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DHR_OK;
+    return DHR_OK;                                        // enqueued: a training step stays asynchronous
   }
-  // host arrays: stage blocks of rows through the device
+  // host arrays: stage blocks of rows through the device (complete on return)
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * ies)));
   DevMem m_in, m_val, m_idx;
   void *&d_in = m_in.p, *&d_val = m_val.p, *&d_idx = m_idx.p;

@@ -1,6 +1,7 @@
 """Host mirror of the reference's `densify` (tevatron/DHR/utils.py:5-22) on the fused HIP op `dhr_densify`
 (SURVEY section 8f row 4).  Same name, arguments, return values and error messages; works on numpy arrays
-(host memory, staged through the device) and on torch tensors (CUDA tensors are processed in place on the device).
+(host memory, staged through the device, complete on return) and on torch tensors (CUDA tensors are processed in place on the device: the op
+is enqueued on torch's current stream and the call does not wait for it).
 There is no CPU implementation here: without the HIP library / a GPU the call raises."""
 from __future__ import annotations
 
@@ -26,8 +27,12 @@ def _run(lexical_reps, dims, remove_dims, out_value, out_index, device):
     if not (kind == kind_v == kind_i):
         raise _lib.DhrError("densify: input and outputs must live in the same memory kind")
     batch, vocab = int(lexical_reps.shape[0]), int(lexical_reps.shape[1])
+    stream = None
+    if kind == _lib.MEM_DEVICE:
+        import torch
+        stream = torch.cuda.current_stream(lexical_reps.device).cuda_stream
     _lib.check(lib.dhr_densify(device, kind, p_in, _lib._val_code(lexical_reps), ld_in, batch, vocab, remove_dims, dims, p_v,
-                               _lib._val_code(out_value), ld_v, p_i, _lib.idx_code(out_index.dtype), ld_i, None), "dhr_densify")
+                               _lib._val_code(out_value), ld_v, p_i, _lib.idx_code(out_index.dtype), ld_i, stream), "dhr_densify")
 
 
 def densify(lexical_reps, dims: int = 768, strategy: str = 'stride', remove_dims: int = 570):

@@ -30,7 +30,7 @@ def shard_bounds(n_docs: int, world: int, rank: int):
 
 def merge_topk(scores, rows, k: int):
     """Per query the k best of the concatenated (score,row) lists, (score desc, row asc); row<0 is
-    padding.  torch tensors [Q, n_in]; CUDA tensors use the device kernel, CPU tensors the host twin."""
+    padding.  torch tensors [Q, n_in]; CUDA tensors use the device kernel, enqueued on torch's current stream (the call does not wait for it); CPU tensors the host twin."""
     import torch
     lib = _lib.load()
     q, n_in = int(scores.shape[0]), int(scores.shape[1])
@@ -51,7 +51,8 @@ def merge_topk(scores, rows, k: int):
 def merge_sorted_lists(scores, rows, k: int):
     """scores/rows: [n_lists, Q, L] tensors, every list sorted (score desc, row asc), padding (row < 0) at
     its tail -- the layout all_gather_into_tensor leaves the per-shard results in.  -> ([Q,k], [Q,k]).
-    rows may be None (scores only; returns (scores, None)).  No sort, no transpose copy: dhr_merge_topk_lists."""
+    rows may be None (scores only; returns (scores, None)).  No sort, no transpose copy: dhr_merge_topk_lists, for CUDA tensors enqueued on
+    torch's current stream (the call does not wait for it)."""
     import torch
     lib = _lib.load()
     n_lists, q, ll = (int(x) for x in scores.shape)

@@ -19,8 +19,8 @@ reference's `psg['attention_mask'][:, 1:]`).  Each contribution is (p * w) * mas
 its weight, and ties keep the first token and the first group, like torch.max on the device.  Finite logits and -inf are in scope; NaN and
 +inf are not, and every unmasked token needs one finite logit.
 
-Torch CUDA tensors are processed on their device; numpy arrays are staged through device 0.  There is no CPU implementation: without the HIP
-library / a GPU the calls raise."""
+Torch CUDA tensors are processed on their device and on torch's current stream; the calls wait for that stream, so the outputs are complete
+on return.  numpy arrays are staged through device 0.  There is no CPU implementation: without the HIP library / a GPU the calls raise."""
 from __future__ import annotations
 
 import numpy as np
@@ -102,6 +102,14 @@ def _ptr(a):
     return a.ctypes.data if _is_np(a) else a.data_ptr()
 
 
+def _stream(a):
+    """torch's current stream on the tensor's device: the op must run behind the model that produced the tensor"""
+    if _is_np(a) or not a.is_cuda:
+        return None
+    import torch
+    return torch.cuda.current_stream(a.device).cuda_stream
+
+
 def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps):
     lib = _lib.load()
     lg, p_lg, ldb, ldt, w, m, B, T, V, kind = _inputs(logits, term_weights, attention_mask)
@@ -134,7 +142,7 @@ def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims,
     if B:
         _lib.check(lib.dhr_lexical_head(_device_of(lg), kind, mode, p_lg, _lib._val_code(lg), B, T, V, ldb, ldt, _ptr(w), T, _ptr(m), T, dims,
                                         remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim,
-                                        None if ws is None else ws.data_ptr(), None), "dhr_lexical_head")
+                                        None if ws is None else ws.data_ptr(), _stream(lg)), "dhr_lexical_head")
     del keep
     return B, V
 
@@ -184,7 +192,7 @@ def aggregate_lexical_into(logits, term_weights, attention_mask, value_out, agg_
 def aggregate(lexical_reps, dims: int = 640, remove_dims: int = -198, full: bool = True):
     """tevatron/Aggretriever/utils.py:16-44 on the HIP kernel: [B, V] reps -> [B, dims] in the input dtype.  As in the reference,
     full=True takes remove = cal_remove_dim(2 * dims) and ignores `remove_dims`; full=False removes cal_remove_dim(dims) columns.
-    numpy in -> numpy out; torch in -> torch out (same device)."""
+    numpy in -> numpy out; torch in -> torch out (same device, torch's current stream, complete on return)."""
     del remove_dims                                     # (the reference overwrites it in both branches)
     if len(lexical_reps.shape) != 2:
         raise ValueError('Input lexical representation shape should be 2 (batch, vocab), but the input shape is {}'.format(len(lexical_reps.shape)))
@@ -207,7 +215,7 @@ def aggregate(lexical_reps, dims: int = 640, remove_dims: int = -198, full: bool
     p_in, ld_in, kind = _lib._ptr_ld(src)
     p_o, ld_o, _ = _lib._ptr_ld(out)
     _lib.check(lib.dhr_aggregate(dev, kind, p_in, _lib._val_code(src), ld_in, B, V, dims, remove, 1 if full else 0, p_o, _lib._val_code(out), ld_o,
-                                 None), "dhr_aggregate")
+                                 _stream(src)), "dhr_aggregate")
     if _is_np(lexical_reps):
         return out.astype(lexical_reps.dtype, copy=False)
     return out.to(lexical_reps.dtype)

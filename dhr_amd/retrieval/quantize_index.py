@@ -33,8 +33,15 @@ def _f16_values(values):
     return values if values.dtype == torch.float16 else values.half()
 
 
+def _stream(t):
+    """torch's current stream on the tensor's device.  The three wrappers below wait for it: their results are complete on return."""
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
 def train_and_encode(values, M: int = 64, n_bits: int = 8, iters: int = 25, max_points: int = 65536, device: int = 0):
-    """values: fp16 [N, d] numpy array (or a torch CUDA tensor).  -> (codebooks float32 [M, 2^n_bits, d/M], codes uint8 [N,M], mse).
+    """values: fp16 [N, d] numpy array (or a torch CUDA tensor: trained and encoded on torch's current stream, complete on return).
+    -> (codebooks float32 [M, 2^n_bits, d/M], codes uint8 [N,M], mse).
     `--n_bits` as in quantize_index.py:22,29 (faiss.IndexPQ(d, M, nbits)): 1..8; codes are one byte per sub-quantiser here, the
     bit-packed rows of faiss exist in the index file only (pack_codes / unpack_codes)."""
     if not 1 <= int(n_bits) <= 8:
@@ -47,6 +54,7 @@ def train_and_encode(values, M: int = 64, n_bits: int = 8, iters: int = 25, max_
         raise ValueError(f"the vector width {d} is not a multiple of --qauntized_dim {M}")
     p, ld, kind = _lib._ptr_ld(values)
     err = C.c_double()
+    stream = None
     if kind == _lib.MEM_HOST:
         cb = np.empty((M, ksub, d // M), np.float32)
         codes = np.empty((n, M), np.uint8)
@@ -56,19 +64,22 @@ def train_and_encode(values, M: int = 64, n_bits: int = 8, iters: int = 25, max_
         cb = torch.empty((M, ksub, d // M), dtype=torch.float32, device=values.device)
         codes = torch.empty((n, M), dtype=torch.uint8, device=values.device)
         pcb, pcodes = cb.data_ptr(), codes.data_ptr()
-    _lib.check(lib.dhr_pq_train_nbits(device, kind, p, ld, n, d, M, int(n_bits), iters, max(max_points, ksub), pcb, C.byref(err), None), "dhr_pq_train")
-    _lib.check(lib.dhr_pq_encode_nbits(device, kind, p, ld, n, d, M, int(n_bits), pcb, pcodes, None), "dhr_pq_encode")
+        stream = _stream(values)
+    _lib.check(lib.dhr_pq_train_nbits(device, kind, p, ld, n, d, M, int(n_bits), iters, max(max_points, ksub), pcb, C.byref(err), stream), "dhr_pq_train")
+    _lib.check(lib.dhr_pq_encode_nbits(device, kind, p, ld, n, d, M, int(n_bits), pcb, pcodes, stream), "dhr_pq_encode")
     return cb, codes, float(err.value)
 
 
 def encode(values, codebooks, n_bits: int = 8, device: int = 0):
     """Codes of `values` under GIVEN codebooks (dhr_pq_encode: nearest centroid per sub-quantiser): what a shard of a row-sharded
-    PQ index does with the corpus-wide codebooks.  values and codebooks live in the same memory kind.  -> codes uint8 [N, M]."""
+    PQ index does with the corpus-wide codebooks.  values and codebooks live in the same memory kind; torch CUDA tensors are encoded on torch's
+    current stream, complete on return.  -> codes uint8 [N, M]."""
     lib = _lib.load()
     values = _f16_values(values)
     n, d = int(values.shape[0]), int(values.shape[1])
     M = int(codebooks.shape[0])
     p, ld, kind = _lib._ptr_ld(values)
+    stream = None
     if kind == _lib.MEM_HOST:
         cb = np.ascontiguousarray(np.asarray(codebooks), np.float32)
         codes = np.empty((n, M), np.uint8)
@@ -78,12 +89,13 @@ def encode(values, codebooks, n_bits: int = 8, device: int = 0):
         cb = codebooks.contiguous()
         codes = torch.empty((n, M), dtype=torch.uint8, device=values.device)
         pcb, pcodes = cb.data_ptr(), codes.data_ptr()
-    _lib.check(lib.dhr_pq_encode_nbits(device, kind, p, ld, n, d, M, int(n_bits), pcb, pcodes, None), "dhr_pq_encode")
+        stream = _stream(values)
+    _lib.check(lib.dhr_pq_encode_nbits(device, kind, p, ld, n, d, M, int(n_bits), pcb, pcodes, stream), "dhr_pq_encode")
     return codes
 
 
 def decode(codebooks, codes, device: int = 0):
-    """-> fp16 [N, d] reconstruction, same memory kind as the inputs."""
+    """-> fp16 [N, d] reconstruction, same memory kind as the inputs (torch CUDA tensors: on torch's current stream, complete on return)."""
     lib = _lib.load()
     M, ksub, dsub = int(codebooks.shape[0]), int(codebooks.shape[1]), int(codebooks.shape[2])
     nbits = ksub.bit_length() - 1
@@ -97,7 +109,8 @@ def decode(codebooks, codes, device: int = 0):
     import torch
     out = torch.empty((n, d), dtype=torch.float16, device=codes.device)
     codes, cb = codes.to(torch.uint8).contiguous(), codebooks.to(torch.float32).contiguous()
-    _lib.check(lib.dhr_pq_decode_nbits(device, _lib.MEM_DEVICE, codes.data_ptr(), n, d, M, nbits, cb.data_ptr(), out.data_ptr(), d, None), "dhr_pq_decode")
+    _lib.check(lib.dhr_pq_decode_nbits(device, _lib.MEM_DEVICE, codes.data_ptr(), n, d, M, nbits, cb.data_ptr(), out.data_ptr(), d, _stream(codes)),
+               "dhr_pq_decode")
     return out
 
 

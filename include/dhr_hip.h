@@ -266,7 +266,8 @@ int dhr_score_rows(dhr_index* index, const dhr_query_batch* queries, int32_t m, 
  * the k_out best of n_lists*k_in (score, row) pairs, best first (score desc, row asc); entries with
  * row < 0 are padding.  in_scores/in_rows are [n_queries, n_lists*k_in] (each query's lists
  * concatenated).  All four pointers are DEVICE pointers on `device`.  Any n_in (up to 16 384 entries per query in one workgroup's LDS,
- * beyond that two stable segmented sorts through global memory; n_queries * n_in < 2^31). */
+ * beyond that two stable segmented sorts through global memory; n_queries * n_in < 2^31).  The call ENQUEUES on `stream` and returns without
+ * waiting (the scratch of the sorted path is allocated and freed in stream order). */
 int dhr_merge_topk(int32_t device, int32_t n_queries, int32_t n_in, const float* in_scores,
                    const int64_t* in_rows, int32_t k_out, float* out_scores, int64_t* out_rows, void* stream);
 /* Same reduce on HOST pointers (no GPU needed; used by the CPU/gloo tests of the sharded path). */
@@ -279,7 +280,7 @@ int dhr_merge_topk_host(int32_t n_queries, int32_t n_in, const float* in_scores,
  * No sort is run: every entry finds its output rank by binary searches in the other lists.  in_rows may be
  * NULL (scores only, e.g. the shards' sample scores of dhr_search_begin; ties keep list order; out_rows is
  * ignored).  (n_lists*list_len + k_out)*12 B (4 B without rows) must fit 160 KiB, n_lists <= 64.  DEVICE pointers
- * on `device`. */
+ * on `device`.  The call ENQUEUES on `stream` and returns without waiting. */
 int dhr_merge_topk_lists(int32_t device, int32_t n_queries, int32_t n_lists, int32_t list_len, const float* in_scores,
                          const int64_t* in_rows, int32_t k_out, float* out_scores, int64_t* out_rows, void* stream);
 /* Host twin (no sortedness needed: it sorts). */
@@ -292,7 +293,8 @@ int dhr_merge_topk_lists_host(int32_t n_queries, int32_t n_lists, int32_t list_l
  *   out_index[b][j] = the FIRST g attaining it                        (index_dtype DHR_IDX_U8, needs n_groups <= 256, or DHR_IDX_I16)
  * written with row strides ld_value / ld_index, i.e. directly into the value / index arrays of an index record (the
  * CLS columns follow at out_value + dims).  DHR_ERR_INVALID when (vocab - remove_dims) is not a multiple of dims
- * (the reference raises ValueError).  All three arrays live in mem_kind memory. */
+ * (the reference raises ValueError).  All three arrays live in mem_kind memory.  Device arrays: the call ENQUEUES on `stream` and returns
+ * without waiting, like the training ops below; host arrays are staged through the device and are complete on return. */
 int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
                 int32_t remove_dims, int32_t dims, void* out_value, int32_t out_value_dtype, int64_t ld_value, void* out_index,
                 int32_t index_dtype, int64_t ld_index, void* stream);
@@ -312,7 +314,8 @@ int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t v
  * out_value_dtype DHR_VAL_F16 rounds to fp16.  cls_dim > 0 copies cls [batch, cls_dim] (row stride ld_cls) into the record columns that follow
  * (vocab or dims), so ld_value >= those + cls_dim.  workspace: NULL, or batch * n_tokens * 16 bytes of device memory on `device` (device
  * arrays only).  All arrays live in mem_kind memory; host arrays are staged through the device in blocks of rows.  NaN and +inf logits
- * are out of scope; every unmasked row needs a finite logit.  DHR_ERR_INVALID when the vocabulary does not split into whole groups. */
+ * are out of scope; every unmasked row needs a finite logit.  DHR_ERR_INVALID when the vocabulary does not split into whole groups.
+ * The call runs on `stream` and WAITS for it (with workspace == NULL it frees its own allocation): the outputs are complete on return. */
 typedef enum dhr_lexical_mode { DHR_LEX_RAW = 0, DHR_LEX_DENSIFY = 1, DHR_LEX_AGG_FULL = 2, DHR_LEX_AGG_SEMI = 3 } dhr_lexical_mode;
 int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void* logits, int32_t value_dtype, int64_t batch, int32_t n_tokens,
                      int32_t vocab, int64_t ld_batch, int64_t ld_token, const float* term_weights, int64_t ld_weights, const float* mask,
@@ -321,7 +324,7 @@ int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, const void*
                      void* workspace, void* stream);
 /* aggregate of already computed lexical reps [batch, vocab] (tevatron/Aggretriever/utils.py:16-44) on the same kernel: full != 0 is
  * DHR_LEX_AGG_FULL, else DHR_LEX_AGG_SEMI; out [batch, dims] (row stride ld_out).  The caller passes remove_dims as the reference computes it
- * (cal_remove_dim). */
+ * (cal_remove_dim).  Runs on `stream` and waits for it: out is complete on return. */
 int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
                   int32_t dims, int32_t remove_dims, int32_t full, void* out, int32_t out_dtype, int64_t ld_out, void* stream);
 
@@ -526,7 +529,8 @@ int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, const void* q, 
  *                  receives the mean squared quantisation error per training row after the last assignment.
  *   dhr_pq_encode: nearest centroid per subspace (first minimum).
  *   dhr_pq_decode: fp16 reconstruction [n][ld_out]; an exact inner-product search over it (dhr_index_create with index = NULL,
- *                  then dhr_search) returns exactly the ADC ranking, on the matrix cores. */
+ *                  then dhr_search) returns exactly the ADC ranking, on the matrix cores.
+ * All three run on `stream` and wait for it: their outputs are complete on return. */
 int dhr_pq_train(int32_t device, int32_t mem_kind, const void* values_f16, int64_t ld, int64_t n, int32_t d, int32_t M, int32_t iters,
                  int64_t max_points, float* codebooks, double* out_error, void* stream);
 int dhr_pq_encode(int32_t device, int32_t mem_kind, const void* values_f16, int64_t ld, int64_t n, int32_t d, int32_t M,

@@ -519,6 +519,32 @@ int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, const void* q, 
                                int32_t group, const int16_t* arg, const float* grad_out, int64_t ld_grad, void* dq, void* dp, int32_t grad_dtype,
                                void* stream);
 
+/* The loss of a training step with its gradient with respect to the score matrices (the tail of tevatron/DHR/modeling.py:170-197,
+ * Aggretriever/modeling.py:184-213, ColBERT/modeling.py:146-160, Dense/modeling.py:134-140).  lexical, semantic (may be NULL) and teacher (may be
+ * NULL) are [rows, cols] matrices, each DHR_VAL_F16 or DHR_VAL_F32 on its own, with row strides ld_* in elements (a [:, 1:] view is read in
+ * place).  fused = lexical + lamb * semantic (lexical alone without semantic).  With a teacher the target of term k is
+ * P_k = softmax(teacher * temperature * teacher_split[k]); without one it is the one-hot at column r * label_stride of row r (the reference's
+ * hard_label_scores; CrossEntropyLoss(mean) is the same quantity).  With KL_r(s, P) = sum_c P[r][c] (log P[r][c] - log_softmax(s)[r][c]), a zero
+ * P entry contributing exactly 0 as in KLDivLoss:
+ *   loss = (1 / rows) sum_r [ weights[0] KL_r(fused, P_0) + weights[1] KL_r(semantic, P_1) + weights[2] KL_r(lexical, P_2) ]
+ * weights and teacher_split are HOST arrays of 3 floats whatever mem_kind (teacher_split is read only with a teacher); a term whose weight is 0
+ * is not computed.  Outputs (mem_kind memory): loss, one fp32; scores_out (may be NULL), fp32 [rows, cols] holding fused; grad_lexical and
+ * grad_semantic (either may be NULL), dloss / dlexical and dloss / dsemantic in the dtype of the input each belongs to:
+ * weights[k] / rows * (softmax(s) - P_k) per term, the fused term reaching lexical with factor 1 and semantic with factor lamb.
+ * exp and log are fp32 with the row maximum subtracted first; the inputs must be finite.  No atomics: every sum has a fixed order and two calls
+ * on the same arguments are bit-identical.  Device arrays need dhr_train_loss_workspace(rows) bytes of device workspace; the library then
+ * allocates nothing, ENQUEUES two kernels on `stream` and returns without waiting.  Host arrays are staged through the device and are complete on
+ * return.  rows == 0 or cols == 0: loss = 0 and nothing else is touched.  DHR_ERR_INVALID for a NULL lexical / loss / weights, negative sizes,
+ * unknown dtypes, a stride shorter than cols, temperature <= 0 or a teacher_split[k] <= 0 with a teacher (the three targets share the
+ * teacher's row maximum, which needs positive scales), a label column (rows - 1) * label_stride >= cols or label_stride < 0 without one,
+ * weights[1] != 0 or a grad_semantic without semantic, a missing or short workspace; DHR_ERR_UNSUPPORTED from 2^31 rows or beyond 2^30 columns. */
+int64_t dhr_train_loss_workspace(int64_t rows);
+int dhr_train_loss(int32_t device, int32_t mem_kind, const void* lexical, int32_t lexical_dtype, int64_t ld_lexical, const void* semantic,
+                   int32_t semantic_dtype, int64_t ld_semantic, const void* teacher, int32_t teacher_dtype, int64_t ld_teacher, int64_t rows,
+                   int64_t cols, int64_t label_stride, float lamb, float temperature, const float* weights, const float* teacher_split, float* loss,
+                   float* scores_out, int64_t ld_scores, void* grad_lexical, int64_t ld_grad_lexical, void* grad_semantic,
+                   int64_t ld_grad_semantic, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Product quantiser for the first stage of --PQIP.  The reference calls faiss
  * IndexPQ(d, M = 64, nbits = 8, METRIC_INNER_PRODUCT) (retrieval/quantize_index.py:27-37, gip_retrieval.py:167-231); faiss is not
  * part of the reference tree, so these restate its published algorithm (per-subspace Lloyd k-means, nearest-centroid codes, ADC

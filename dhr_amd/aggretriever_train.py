@@ -23,25 +23,10 @@ There is no CPU implementation: without a GPU the calls raise."""
 from __future__ import annotations
 
 from . import _lib
+from . import _marshal as M
 from .lexical import VOCAB_SIZE, _agg_geometry
 
 MAX_TOKENS, MAX_GROUPS = 32767, 16383
-
-
-def _stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _rows(t, cols):
-    """a [rows, cols] tensor as the kernels read it: last dimension contiguous, rows not overlapping"""
-    if cols == 0 or (t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= cols)):
-        return t
-    return t.contiguous()
-
-
-def _ld(t, cols):
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
 
 
 def _check_aggregate(lexical_reps, dims, full):
@@ -104,12 +89,12 @@ def _functions():
         def forward(ctx, reps, dims, full):
             B, V, remove = _check_aggregate(reps, dims, full)
             lib = _lib.load()
-            x = _rows(reps.detach(), V)
+            x, (ld_x,) = M.as_read(reps.detach())
             out = torch.empty((B, dims), dtype=x.dtype, device=x.device)
             route = torch.empty((B, dims), dtype=torch.int16, device=x.device)
             code = _lib._val_code(x)
-            _lib.check(lib.dhr_aggregate_train(x.device.index or 0, _lib.MEM_DEVICE, x.data_ptr(), code, _ld(x, V), B, V, dims, remove, 1 if full else 0,
-                                               out.data_ptr(), code, dims, route.data_ptr(), dims, _stream(x)), "dhr_aggregate_train")
+            _lib.check(lib.dhr_aggregate_train(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), code, ld_x, B, V, dims, remove, 1 if full else 0,
+                                               out.data_ptr(), code, dims, route.data_ptr(), dims, M.stream(x)), "dhr_aggregate_train")
             ctx.save_for_backward(route)
             ctx.geom = (B, V, dims, remove, full, x.dtype)
             ctx.mark_non_differentiable(route)
@@ -123,13 +108,10 @@ def _functions():
             if not ctx.needs_input_grad[0]:
                 return None, None, None
             lib = _lib.load()
-            g = grad.detach().reshape(B, dims)
-            if g.dtype != dtype:
-                g = g.to(dtype)
-            g = _rows(g, dims)
+            g, ld_g = M.grad_rows(grad, B, dims, dtype)
             dx = torch.empty((B, V), dtype=dtype, device=route.device)
-            _lib.check(lib.dhr_aggregate_backward(route.device.index or 0, _lib.MEM_DEVICE, g.data_ptr(), _lib._val_code(g), _ld(g, dims),
-                                                  route.data_ptr(), dims, B, V, dims, remove, 1 if full else 0, dx.data_ptr(), V, _stream(dx)),
+            _lib.check(lib.dhr_aggregate_backward(M.device(route), _lib.MEM_DEVICE, g.data_ptr(), _lib._val_code(g), ld_g,
+                                                  route.data_ptr(), dims, B, V, dims, remove, 1 if full else 0, dx.data_ptr(), V, M.stream(dx)),
                        "dhr_aggregate_backward")
             return dx, None, None
 
@@ -138,14 +120,14 @@ def _functions():
         def forward(ctx, input_ids, term_weights, vocab, skip_tokens):
             B, L, T = _check_term_weights(input_ids, term_weights, vocab, skip_tokens)
             lib = _lib.load()
-            ids = _rows(input_ids.detach(), L)
-            w = _rows(term_weights.detach().reshape(B, T), T)
+            ids, (ld_ids,) = M.as_read(input_ids.detach())
+            w, (ld_w,) = M.as_read(term_weights.detach().reshape(B, T))
             reps = torch.empty((B, vocab), dtype=torch.float32, device=w.device)
             tok = torch.empty((B, vocab), dtype=torch.int16, device=w.device)
             if B:
-                _lib.check(lib.dhr_term_weight_head(w.device.index or 0, _lib.MEM_DEVICE, ids.data_ptr(), ids.element_size(), _ld(ids, L), w.data_ptr(),
-                                                    _lib._val_code(w), _ld(w, T), B, T, skip_tokens, vocab, reps.data_ptr(), vocab, tok.data_ptr(),
-                                                    vocab, _stream(w)), "dhr_term_weight_head")
+                _lib.check(lib.dhr_term_weight_head(M.device(w), _lib.MEM_DEVICE, ids.data_ptr(), ids.element_size(), ld_ids, w.data_ptr(),
+                                                    _lib._val_code(w), ld_w, B, T, skip_tokens, vocab, reps.data_ptr(), vocab, tok.data_ptr(),
+                                                    vocab, M.stream(w)), "dhr_term_weight_head")
             ctx.save_for_backward(ids, tok)
             ctx.geom = (B, L, T, vocab, skip_tokens, tuple(term_weights.shape), term_weights.dtype)
             ctx.mark_non_differentiable(tok)
@@ -159,15 +141,12 @@ def _functions():
             if not ctx.needs_input_grad[1]:
                 return None, None, None, None
             lib = _lib.load()
-            g = grad.detach().reshape(B, vocab)
-            if g.dtype != torch.float32:
-                g = g.float()
-            g = _rows(g, vocab)
+            g, ld_g = M.grad_rows(grad, B, vocab)
             dw = torch.empty((B, T), dtype=w_dtype, device=tok.device)
             if B:
-                _lib.check(lib.dhr_term_weight_head_backward(tok.device.index or 0, _lib.MEM_DEVICE, ids.data_ptr(), ids.element_size(), _ld(ids, L), B, T,
-                                                             skip_tokens, vocab, g.data_ptr(), _ld(g, vocab), tok.data_ptr(), vocab, dw.data_ptr(),
-                                                             _lib._val_code(dw), T, _stream(dw)), "dhr_term_weight_head_backward")
+                _lib.check(lib.dhr_term_weight_head_backward(M.device(tok), _lib.MEM_DEVICE, ids.data_ptr(), ids.element_size(), M.lds(ids)[0], B, T,
+                                                             skip_tokens, vocab, g.data_ptr(), ld_g, tok.data_ptr(), vocab, dw.data_ptr(),
+                                                             _lib._val_code(dw), T, M.stream(dw)), "dhr_term_weight_head_backward")
             return None, dw.reshape(w_shape), None, None
 
     _FNS = (Aggregate, TermWeightReps)

@@ -18,6 +18,7 @@
 //                                     block and are never used as an index.
 //   term_weight_head_backward_kernel  the gather: dw[b][t] = grad[b][v] where tok[b][v] == t (v = ids[b][t] inside the vocabulary), else zero.
 // Everything is enqueued on the caller's stream; nothing is allocated.
+#include "host_stage.h"
 #include "lexical_common.h"
 
 namespace {
@@ -185,8 +186,6 @@ __global__ void __launch_bounds__(256) term_weight_head_backward_kernel(const TI
     dw[b * ld_dw + t] = (TW)val;
   }
 }
-
-int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
 
 // the checks the two aggregate entry points share
 int check_aggregate(int32_t mem_kind, int64_t batch, int32_t vocab, int32_t dims, int32_t remove_dims, int32_t full, const char* what, Geometry& geo) {

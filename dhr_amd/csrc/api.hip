@@ -1,7 +1,7 @@
 // Search entry points of the C ABI (include/dhr_hip.h): dhr_search, dhr_search_rerank, the staged calls of the sharded search, dhr_score_rows;
 // densify, PQ training / encoding, debug hooks, shard reduce.  The handle and its build: index_build.hip; the controller (search_core): search_core.hip;
 // the sharded control flow: sharded.hip; error record, exception classifier: abi.cpp.
-#include "dhr_state.h"
+#include "host_stage.h"
 
 extern "C" int dhr_search(dhr_index* ix, const dhr_query_batch* qb, int32_t k, float* out_scores, int64_t* out_rows,
                           int32_t out_mem_kind, void* stream) try {
@@ -472,8 +472,7 @@ extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical
     return set_error(DHR_ERR_INVALID, "bad sizes / strides");
   if ((vocab - remove_dims) % dims != 0)
     return set_error(DHR_ERR_INVALID, "Input lexical representation cannot be densified, please fix dims or remove_dims");
-  if ((value_dtype != DHR_VAL_F16 && value_dtype != DHR_VAL_F32) || (out_value_dtype != DHR_VAL_F16 && out_value_dtype != DHR_VAL_F32))
-    return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (!val_ok(value_dtype) || !val_ok(out_value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
   const int n_groups = (vocab - remove_dims) / dims;
   if (index_dtype != DHR_IDX_U8 && index_dtype != DHR_IDX_I16) return set_error(DHR_ERR_INVALID, "index dtype must be uint8 or int16");
   if (index_dtype == DHR_IDX_U8 && n_groups > 256) return set_error(DHR_ERR_UNSUPPORTED, "more than 256 groups need the int16 index dtype");
@@ -481,7 +480,7 @@ extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical
   if (batch == 0) return DHR_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  const int ies = value_dtype == DHR_VAL_F32 ? 4 : 2, oes = out_value_dtype == DHR_VAL_F32 ? 4 : 2, xes = index_dtype == DHR_IDX_I16 ? 2 : 1;
+  const int ies = val_esize(value_dtype), oes = val_esize(out_value_dtype), xes = index_dtype == DHR_IDX_I16 ? 2 : 1;
   if (mem_kind == DHR_MEM_DEVICE) {
     HIP_TRY(launch_densify(lexical, value_dtype == DHR_VAL_F32, ld, batch, remove_dims, dims, n_groups, out_value, out_value_dtype == DHR_VAL_F32,
                            ld_value, out_index, index_dtype == DHR_IDX_I16, ld_index, s));
@@ -492,21 +491,17 @@ extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical
   DevMem m_in, m_val, m_idx;
   void *&d_in = m_in.p, *&d_val = m_val.p, *&d_idx = m_idx.p;
   auto done = [&](int code) { return code; };       // (the three DevMem release the staging buffers)
-  if (hipMalloc(&d_in, (size_t)block * vocab * ies) != hipSuccess || hipMalloc(&d_val, (size_t)block * dims * oes) != hipSuccess ||
-      hipMalloc(&d_idx, (size_t)block * dims * xes) != hipSuccess)
+  if (dev_alloc(m_in, block * vocab * ies) != hipSuccess || dev_alloc(m_val, block * dims * oes) != hipSuccess ||
+      dev_alloc(m_idx, block * dims * xes) != hipSuccess)
     return done(set_error(DHR_ERR_HIP, "hipMalloc failed"));
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
-    if (hipMemcpy2DAsync(d_in, (size_t)vocab * ies, (const char*)lexical + lo * ld * ies, (size_t)ld * ies, (size_t)vocab * ies, (size_t)rows,
-                         hipMemcpyHostToDevice, s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "H2D failed"));
+    if (copy_in(d_in, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "H2D failed"));
     if (launch_densify(d_in, value_dtype == DHR_VAL_F32, vocab, rows, remove_dims, dims, n_groups, d_val, out_value_dtype == DHR_VAL_F32, dims, d_idx,
                        index_dtype == DHR_IDX_I16, dims, s) != hipSuccess)
       return done(set_error(DHR_ERR_HIP, "densify launch failed"));
-    if (hipMemcpy2DAsync((char*)out_value + lo * ld_value * oes, (size_t)ld_value * oes, d_val, (size_t)dims * oes, (size_t)dims * oes, (size_t)rows,
-                         hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpy2DAsync((char*)out_index + lo * ld_index * xes, (size_t)ld_index * xes, d_idx, (size_t)dims * xes, (size_t)dims * xes, (size_t)rows,
-                         hipMemcpyDeviceToHost, s) != hipSuccess)
+    if (stage_out((char*)out_value + lo * ld_value * oes, ld_value, d_val, rows, dims, oes, s) != hipSuccess ||
+        stage_out((char*)out_index + lo * ld_index * xes, ld_index, d_idx, rows, dims, xes, s) != hipSuccess)
       return done(set_error(DHR_ERR_HIP, "D2H failed"));
     if (hipStreamSynchronize(s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "densify failed on the device"));
   }

@@ -10,7 +10,7 @@
 //                         are added in wave order.  gip_pair_bwd_kernel: the same over the query's own block, one wave.
 //   densify_bwd_kernel    the whole [batch, vocab] gradient row of densify in one pass: dv at the group the index names, zero elsewhere.
 // Every sum has a fixed order (no atomics): two runs on the same inputs are bit-identical.  Products and sums are fp32.
-#include "dhr_state.h"
+#include "host_stage.h"
 
 namespace {
 
@@ -206,9 +206,6 @@ __global__ void __launch_bounds__(256) densify_bwd_kernel(const float* __restric
   }
 }
 
-int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
-int idx_ok(int dt) { return dt == DHR_IDX_U8 || dt == DHR_IDX_I8 || dt == DHR_IDX_I16; }
-
 // how the forward tiles a listwise problem: thread tile, dims per slice, slices
 struct FwdPlan {
   int small, chunk, slices;
@@ -320,17 +317,6 @@ hipError_t launch_densify_bwd(const float* dv, int64_t ld_dv, const void* idx, i
   return hipGetLastError();
 }
 
-// a host array [rows, cols] of es-byte elements copied into a packed device buffer (row stride cols)
-hipError_t stage_in(DevMem& m, const void* host, int64_t ld, int64_t rows, int64_t cols, int es, hipStream_t s) {
-  hipError_t e = hipMalloc(&m.p, (size_t)std::max<int64_t>(1, rows * cols * es));
-  if (e != hipSuccess || rows == 0) return e;
-  return hipMemcpy2DAsync(m.p, (size_t)cols * es, host, (size_t)ld * es, (size_t)cols * es, (size_t)rows, hipMemcpyHostToDevice, s);
-}
-hipError_t stage_out(void* host, int64_t ld, const void* dev, int64_t rows, int64_t cols, int es, hipStream_t s) {
-  if (rows == 0) return hipSuccess;
-  return hipMemcpy2DAsync(host, (size_t)ld * es, dev, (size_t)cols * es, (size_t)cols * es, (size_t)rows, hipMemcpyDeviceToHost, s);
-}
-
 // the checks the forward and the backward share; fills x
 int check_sides(const void* qv, int64_t ld_qv, const void* qi, int64_t ld_qi, int64_t n_q, const void* pv, int64_t ld_pv, const void* pi,
                 int64_t ld_pi, int64_t n_p, int32_t dims, int32_t value_dtype, int32_t index_dtype, int32_t group, int32_t mem_kind, Sides& x) {
@@ -389,9 +375,9 @@ extern "C" int dhr_gip_scores(int32_t device, int32_t mem_kind, const void* q_va
   }
   DevMem m[4], m_out, m_ws;
   HIP_TRY(stage_sides(x, m, s));
-  HIP_TRY(hipMalloc(&m_out.p, (size_t)(n_q * out_cols * 4)));
+  HIP_TRY(dev_alloc(m_out, n_q * out_cols * 4));
   const int64_t ws_bytes = dhr_gip_scores_workspace(n_q, n_p, dims, group);
-  if (ws_bytes) HIP_TRY(hipMalloc(&m_ws.p, (size_t)ws_bytes));
+  if (ws_bytes) HIP_TRY(dev_alloc(m_ws, ws_bytes));
   HIP_TRY(launch_scores(x, (float*)m_out.p, out_cols, m_ws.p, ws_bytes, s));
   HIP_TRY(stage_out(out, ld_out, m_out.p, n_q, out_cols, 4, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -421,8 +407,8 @@ extern "C" int dhr_gip_scores_backward(int32_t device, int32_t mem_kind, const v
   DevMem m[4], m_g, m_dq, m_dp;
   HIP_TRY(stage_sides(x, m, s));
   HIP_TRY(stage_in(m_g, grad_out, ld_grad, n_q, g_cols, 4, s));
-  if (grad_q && n_q) HIP_TRY(hipMalloc(&m_dq.p, (size_t)(n_q * dims * 4)));
-  if (grad_p && n_p) HIP_TRY(hipMalloc(&m_dp.p, (size_t)(n_p * dims * 4)));
+  if (grad_q && n_q) HIP_TRY(dev_alloc(m_dq, n_q * dims * 4));
+  if (grad_p && n_p) HIP_TRY(dev_alloc(m_dp, n_p * dims * 4));
   HIP_TRY(launch_scores_bwd(x, (const float*)m_g.p, g_cols, (float*)m_dq.p, dims, (float*)m_dp.p, dims, s));
   if (m_dq.p) HIP_TRY(stage_out(grad_q, ld_grad_q, m_dq.p, n_q, dims, 4, s));
   if (m_dp.p) HIP_TRY(stage_out(grad_p, ld_grad_p, m_dp.p, n_p, dims, 4, s));
@@ -452,10 +438,10 @@ extern "C" int dhr_densify_backward(int32_t device, int32_t mem_kind, const floa
     return DHR_OK;
   }
   // host arrays: stage blocks of rows through the device
-  const int oes = grad_dtype == DHR_VAL_F32 ? 4 : 2, xes = idx_esize(index_dtype);
+  const int oes = val_esize(grad_dtype), xes = idx_esize(index_dtype);
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * oes)));
   DevMem m_out;
-  HIP_TRY(hipMalloc(&m_out.p, (size_t)(block * vocab * oes)));
+  HIP_TRY(dev_alloc(m_out, block * vocab * oes));
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
     DevMem m_dv, m_idx;

@@ -13,6 +13,7 @@
 // Semantics kept literally: every contribution is (p * w) * mask in fp32 (a masked token folds in a zero with the sign of w), ties keep the
 // first token and the first group (torch.max on the device), aggregate(full) is pos * (pos > neg) - neg * (pos <= neg) with its signs of zero.
 // NaN and +inf logits are out of scope (an unmasked row must hold a finite value).
+#include "host_stage.h"
 #include "lexical_common.h"
 
 namespace {
@@ -159,8 +160,6 @@ hipError_t launch_fold(const void* logits, int in_f32, int mode, const FoldArgs&
   return hipGetLastError();
 }
 
-int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
-
 }  // namespace
 
 // declared in lexical_common.h: the epilogues above on fp32 reps that another translation unit computed (lexical_proj.hip)
@@ -208,8 +207,7 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   if (batch == 0) return DHR_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  const int ies = logits_dtype == DHR_VAL_F32 ? 4 : 2, oes = out_value_dtype == DHR_VAL_F32 ? 4 : 2, xes = index_dtype == DHR_IDX_I16 ? 2 : 1;
-  const int ces = cls_dtype == DHR_VAL_F32 ? 4 : 2;
+  const int ies = val_esize(logits_dtype), oes = val_esize(out_value_dtype), xes = index_dtype == DHR_IDX_I16 ? 2 : 1, ces = val_esize(cls_dtype);
   const int T = n_tokens;
   FoldArgs a{};
   a.T = T; a.V = vocab; a.remove = geo.remove; a.W = geo.W; a.n_groups = geo.n_groups;
@@ -239,7 +237,7 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   if (mem_kind == DHR_MEM_DEVICE) {
     DevMem ws_mem;
     void* ws = workspace;
-    if (!ws) HIP_TRY(hipMalloc(&ws_mem.p, (size_t)batch * T * sizeof(float4)));
+    if (!ws) HIP_TRY(dev_alloc(ws_mem, batch * T * (int64_t)sizeof(float4)));
     if (!ws) ws = ws_mem.p;
     HIP_TRY(run(logits, ld_batch, ld_token, term_weights, ld_weights, mask, ld_mask, batch, (float4*)ws, out_value, ld_value, out_index, ld_index, cls,
                 ld_cls));
@@ -251,33 +249,25 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / per_row));
   const int64_t ldv = geo.out_cols + cls_dim;
   DevMem m_in, m_w, m_m, m_st, m_val, m_idx, m_cls;
-  if (hipMalloc(&m_in.p, (size_t)(block * per_row)) != hipSuccess || hipMalloc(&m_w.p, (size_t)block * T * 4) != hipSuccess ||
-      hipMalloc(&m_m.p, (size_t)block * T * 4) != hipSuccess || hipMalloc(&m_st.p, (size_t)block * T * sizeof(float4)) != hipSuccess ||
-      hipMalloc(&m_val.p, (size_t)(block * ldv * oes)) != hipSuccess ||
-      (mode == MODE_DENSIFY && hipMalloc(&m_idx.p, (size_t)block * geo.out_cols * xes) != hipSuccess) ||
-      (cls_dim > 0 && hipMalloc(&m_cls.p, (size_t)block * cls_dim * ces) != hipSuccess))
+  if (dev_alloc(m_in, block * per_row) != hipSuccess || dev_alloc(m_w, block * T * 4) != hipSuccess || dev_alloc(m_m, block * T * 4) != hipSuccess ||
+      dev_alloc(m_st, block * T * (int64_t)sizeof(float4)) != hipSuccess || dev_alloc(m_val, block * ldv * oes) != hipSuccess ||
+      (mode == MODE_DENSIFY && dev_alloc(m_idx, block * geo.out_cols * xes) != hipSuccess) ||
+      (cls_dim > 0 && dev_alloc(m_cls, block * cls_dim * ces) != hipSuccess))
     return set_error(DHR_ERR_HIP, "hipMalloc failed");
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
     for (int64_t r = 0; r < rows; ++r)
-      if (hipMemcpy2DAsync((char*)m_in.p + r * per_row, (size_t)vocab * ies, (const char*)logits + (lo + r) * ld_batch * ies, (size_t)ld_token * ies,
-                           (size_t)vocab * ies, (size_t)T, hipMemcpyHostToDevice, s) != hipSuccess)
+      if (copy_in((char*)m_in.p + r * per_row, (const char*)logits + (lo + r) * ld_batch * ies, ld_token, T, vocab, ies, s) != hipSuccess)
         return set_error(DHR_ERR_HIP, "H2D failed");
-    if (hipMemcpy2DAsync(m_w.p, (size_t)T * 4, term_weights + lo * ld_weights, (size_t)ld_weights * 4, (size_t)T * 4, (size_t)rows,
-                         hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpy2DAsync(m_m.p, (size_t)T * 4, mask + lo * ld_mask, (size_t)ld_mask * 4, (size_t)T * 4, (size_t)rows, hipMemcpyHostToDevice, s) !=
-            hipSuccess ||
-        (cls_dim > 0 && hipMemcpy2DAsync(m_cls.p, (size_t)cls_dim * ces, (const char*)cls + lo * ld_cls * ces, (size_t)ld_cls * ces,
-                                         (size_t)cls_dim * ces, (size_t)rows, hipMemcpyHostToDevice, s) != hipSuccess))
+    if (copy_in(m_w.p, term_weights + lo * ld_weights, ld_weights, rows, T, 4, s) != hipSuccess ||
+        copy_in(m_m.p, mask + lo * ld_mask, ld_mask, rows, T, 4, s) != hipSuccess ||
+        (cls_dim > 0 && copy_in(m_cls.p, (const char*)cls + lo * ld_cls * ces, ld_cls, rows, cls_dim, ces, s) != hipSuccess))
       return set_error(DHR_ERR_HIP, "H2D failed");
     if (run(m_in.p, (int64_t)T * vocab, vocab, (const float*)m_w.p, T, (const float*)m_m.p, T, rows, (float4*)m_st.p, m_val.p, ldv, m_idx.p,
             geo.out_cols, m_cls.p, cls_dim) != hipSuccess)
       return set_error(DHR_ERR_HIP, "lexical head launch failed");
-    if (hipMemcpy2DAsync((char*)out_value + lo * ld_value * oes, (size_t)ld_value * oes, m_val.p, (size_t)ldv * oes, (size_t)ldv * oes, (size_t)rows,
-                         hipMemcpyDeviceToHost, s) != hipSuccess ||
-        (mode == MODE_DENSIFY &&
-         hipMemcpy2DAsync((char*)out_index + lo * ld_index * xes, (size_t)ld_index * xes, m_idx.p, (size_t)geo.out_cols * xes,
-                          (size_t)geo.out_cols * xes, (size_t)rows, hipMemcpyDeviceToHost, s) != hipSuccess))
+    if (stage_out((char*)out_value + lo * ld_value * oes, ld_value, m_val.p, rows, ldv, oes, s) != hipSuccess ||
+        (mode == MODE_DENSIFY && stage_out((char*)out_index + lo * ld_index * xes, ld_index, m_idx.p, rows, geo.out_cols, xes, s) != hipSuccess))
       return set_error(DHR_ERR_HIP, "D2H failed");
     if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "lexical head failed on the device");
   }
@@ -298,7 +288,7 @@ extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexic
   if (batch == 0) return DHR_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  const int ies = value_dtype == DHR_VAL_F32 ? 4 : 2, oes = out_dtype == DHR_VAL_F32 ? 4 : 2;
+  const int ies = val_esize(value_dtype), oes = val_esize(out_dtype);
   FoldArgs a{};
   a.ld_batch = ld; a.ld_token = vocab; a.T = 1; a.V = vocab; a.stats = nullptr;
   a.remove = geo.remove; a.W = geo.W; a.n_groups = geo.n_groups; a.val_f32 = out_dtype == DHR_VAL_F32;
@@ -310,19 +300,15 @@ extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexic
   }
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * ies)));
   DevMem m_in, m_out;
-  if (hipMalloc(&m_in.p, (size_t)block * vocab * ies) != hipSuccess || hipMalloc(&m_out.p, (size_t)block * dims * oes) != hipSuccess)
+  if (dev_alloc(m_in, block * vocab * ies) != hipSuccess || dev_alloc(m_out, block * dims * oes) != hipSuccess)
     return set_error(DHR_ERR_HIP, "hipMalloc failed");
   a.ld_batch = vocab; a.out_val = m_out.p; a.ld_val = dims;
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
     a.batch = rows;
-    if (hipMemcpy2DAsync(m_in.p, (size_t)vocab * ies, (const char*)lexical + lo * ld * ies, (size_t)ld * ies, (size_t)vocab * ies, (size_t)rows,
-                         hipMemcpyHostToDevice, s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "H2D failed");
+    if (copy_in(m_in.p, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
     if (launch_fold(m_in.p, value_dtype == DHR_VAL_F32, mode, a, s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate launch failed");
-    if (hipMemcpy2DAsync((char*)out + lo * ld_out * oes, (size_t)ld_out * oes, m_out.p, (size_t)dims * oes, (size_t)dims * oes, (size_t)rows,
-                         hipMemcpyDeviceToHost, s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "D2H failed");
+    if (stage_out((char*)out + lo * ld_out * oes, ld_out, m_out.p, rows, dims, oes, s) != hipSuccess) return set_error(DHR_ERR_HIP, "D2H failed");
     if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate failed on the device");
   }
   return DHR_OK;

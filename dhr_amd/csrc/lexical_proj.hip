@@ -19,6 +19,7 @@
 // matter, and it is folded in at its place in token order (before the first unmasked token that follows it, or after the passage's last).
 // The record epilogues (raw / densify / aggregate, [CLS] columns) are those of lexical.hip on the fp32 reps (lexical_record_from_reps).
 // Every reduction has a fixed order: two calls on the same arguments are bit-identical.  NaN / inf inputs are out of scope.
+#include "host_stage.h"
 #include "lexical_proj_common.h"
 
 namespace {
@@ -46,8 +47,6 @@ Layout layout(int64_t B, int T, int V, int mode) {
   l.total = at;
   return l;
 }
-
-int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
 
 }  // namespace
 

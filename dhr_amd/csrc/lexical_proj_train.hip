@@ -22,6 +22,7 @@
 // (16 per 64 columns of H: 192 at H = 768; a wider H is cut into two slabs, each of which computes x again).  One workgroup owns its rows of the output: no atomics, no float atomics
 // anywhere, every sum in a fixed order -- two runs are bit-identical.  dbias is the fp32 sum of the unrounded dx.
 // Everything is enqueued on the caller's stream; nothing is allocated.  NaN / inf inputs are out of scope.
+#include "host_stage.h"
 #include "lexical_proj_common.h"
 
 namespace {
@@ -346,8 +347,6 @@ Layout layout(int64_t B, int T, int V, int H) {
   l.total = at;
   return l;
 }
-
-int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
 
 // the checks the forward and the backward share, before anything is dereferenced.  n_tokens counts the tokens after the skipped ones.
 int check_common(const char* what, int32_t mem_kind, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens, int32_t skip_tokens,

@@ -19,6 +19,7 @@
 //                             zeros without being read.  Rows that are not 4-byte aligned (fp16 with an odd stride) take element-wise accesses.
 // Both passes take the model's full [B, L, V] logits and skip_tokens (the reference drops token 0): the gradient of the whole tensor is
 // written, so autograd never pads the gradient of a [:, 1:] view.  Everything is enqueued on the caller's stream; nothing is allocated.
+#include "host_stage.h"
 #include "lexical_common.h"
 
 namespace {
@@ -177,8 +178,6 @@ __global__ void __launch_bounds__(256) lexical_dx_kernel(const TIN* __restrict__
     }
   }
 }
-
-int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
 
 // the checks the forward and the backward share: n_tokens counts the tokens after the skipped ones
 int check_head(const void* logits, int32_t mem_kind, int32_t value_dtype, int64_t batch, int32_t n_tokens, int32_t skip_tokens, int32_t vocab,

@@ -15,7 +15,7 @@
 //                         adds G * q[a][i] into row arg - first token, and writes the whole block once.
 // Every sum has a fixed order that depends on the shape alone (no atomics): two runs are bit-identical, and a pair's score does not depend on
 // which other pairs are scored.  Products and sums are fp32.
-#include "dhr_state.h"
+#include "host_stage.h"
 
 namespace {
 
@@ -413,7 +413,7 @@ int check_problem(int32_t mem_kind, const void* q, int64_t ld_q_tok, int64_t ld_
                   int64_t ld_p_batch, int64_t B, int64_t Lp, int32_t D, int32_t value_dtype, int32_t group, Problem& x) {
   if (!q || !p) return set_error(DHR_ERR_INVALID, "null pointer");
   if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
-  if (value_dtype != DHR_VAL_F16 && value_dtype != DHR_VAL_F32) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (!val_ok(value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
   if (A < 0 || B < 0 || Lq <= 0 || Lp <= 0 || D <= 0 || group < 0) return set_error(DHR_ERR_INVALID, "bad sizes");
   if (ld_q_tok < D || ld_p_tok < D || ld_q_batch < D || ld_p_batch < D) return set_error(DHR_ERR_INVALID, "a stride is shorter than a row of D values");
   if (group > 0 && B != A * group)
@@ -433,18 +433,11 @@ int check_problem(int32_t mem_kind, const void* q, int64_t ld_q_tok, int64_t ld_
 
 // a host [n][len][D] array with two strides -> a packed device copy
 hipError_t stage_side(DevMem& m, Side& sd, int D, int es, hipStream_t s) {
-  hipError_t e = hipMalloc(&m.p, (size_t)std::max<int64_t>(1, sd.n * sd.len * D * es));
+  hipError_t e = dev_alloc(m, sd.n * sd.len * D * es);
   for (int64_t k = 0; k < sd.n && e == hipSuccess; ++k)
-    e = hipMemcpy2DAsync((char*)m.p + k * sd.len * D * es, (size_t)D * es, (const char*)sd.x + k * sd.ld_batch * es, (size_t)sd.ld_tok * es,
-                         (size_t)D * es, (size_t)sd.len, hipMemcpyHostToDevice, s);
+    e = copy_in((char*)m.p + k * sd.len * D * es, (const char*)sd.x + k * sd.ld_batch * es, sd.ld_tok, sd.len, D, es, s);
   sd = make_side(m.p, D, (int64_t)sd.len * D, sd.n, sd.len, es);
   return e;
-}
-
-hipError_t stage_rows(DevMem& m, const void* host, int64_t ld, int64_t rows, int64_t cols, int es, hipStream_t s) {
-  hipError_t e = hipMalloc(&m.p, (size_t)std::max<int64_t>(1, rows * cols * es));
-  if (e != hipSuccess || rows == 0 || cols == 0) return e;
-  return hipMemcpy2DAsync(m.p, (size_t)cols * es, host, (size_t)ld * es, (size_t)cols * es, (size_t)rows, hipMemcpyHostToDevice, s);
 }
 
 }  // namespace
@@ -469,10 +462,10 @@ extern "C" int dhr_maxsim_scores(int32_t device, int32_t mem_kind, const void* q
   DevMem m_q, m_p, m_out, m_arg;
   HIP_TRY(stage_side(m_q, x.q, D, es, s));
   HIP_TRY(stage_side(m_p, x.p, D, es, s));
-  HIP_TRY(hipMalloc(&m_out.p, (size_t)(A * x.cols * 4)));
-  if (arg) HIP_TRY(hipMalloc(&m_arg.p, (size_t)(A * x.cols * Lq * 2)));
+  HIP_TRY(dev_alloc(m_out, A * x.cols * 4));
+  if (arg) HIP_TRY(dev_alloc(m_arg, A * x.cols * Lq * 2));
   HIP_TRY(launch_fwd(x, (float*)m_out.p, x.cols, (int16_t*)m_arg.p, s));
-  HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld_out * 4, m_out.p, (size_t)x.cols * 4, (size_t)x.cols * 4, (size_t)A, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stage_out(out, ld_out, m_out.p, A, x.cols, 4, s));
   if (arg) HIP_TRY(hipMemcpyAsync(arg, m_arg.p, (size_t)(A * x.cols * Lq * 2), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
@@ -485,7 +478,7 @@ extern "C" int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, cons
   dhr::alloc_checkpoint();
   Problem x;
   if (!arg || !grad_out) return set_error(DHR_ERR_INVALID, "null pointer");
-  if (grad_dtype != DHR_VAL_F16 && grad_dtype != DHR_VAL_F32) return set_error(DHR_ERR_INVALID, "bad gradient dtype");
+  if (!val_ok(grad_dtype)) return set_error(DHR_ERR_INVALID, "bad gradient dtype");
   int rc = check_problem(mem_kind, q, ld_q_tok, ld_q_batch, A, Lq, p, ld_p_tok, ld_p_batch, B, Lp, D, value_dtype, group, x);
   if (rc) return rc;
   if (ld_grad < x.cols) return set_error(DHR_ERR_INVALID, "ld_grad is shorter than a row of scores");
@@ -511,10 +504,10 @@ extern "C" int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, cons
   DevMem m_q, m_p, m_arg, m_g, m_dq, m_dp;
   HIP_TRY(stage_side(m_q, x.q, D, es, s));
   HIP_TRY(stage_side(m_p, x.p, D, es, s));
-  HIP_TRY(stage_rows(m_arg, arg, x.cols * Lq, A, x.cols * Lq, 2, s));
-  HIP_TRY(stage_rows(m_g, grad_out, ld_grad, A, x.cols, 4, s));
-  if (dq) HIP_TRY(hipMalloc(&m_dq.p, dq_bytes));
-  if (dp) HIP_TRY(hipMalloc(&m_dp.p, dp_bytes));
+  HIP_TRY(stage_in(m_arg, arg, x.cols * Lq, A, x.cols * Lq, 2, s));
+  HIP_TRY(stage_in(m_g, grad_out, ld_grad, A, x.cols, 4, s));
+  if (dq) HIP_TRY(dev_alloc(m_dq, (int64_t)dq_bytes));
+  if (dp) HIP_TRY(dev_alloc(m_dp, (int64_t)dp_bytes));
   HIP_TRY(launch_bwd(x, (const int16_t*)m_arg.p, (const float*)m_g.p, x.cols, m_dq.p, m_dp.p, gf32, s));
   if (dq) HIP_TRY(hipMemcpyAsync(dq, m_dq.p, dq_bytes, hipMemcpyDeviceToHost, s));
   if (dp) HIP_TRY(hipMemcpyAsync(dp, m_dp.p, dp_bytes, hipMemcpyDeviceToHost, s));

@@ -13,7 +13,7 @@
 //   train_loss_sum_kernel  one workgroup adds the R row losses in index order and writes loss = sum / R.
 // exp and log are fp32, every exp has its maximum subtracted first (scores of magnitude 1e4 neither overflow nor give NaN).  Reductions are wave
 // butterflies followed by the four wave results in wave order: no atomics, two runs on the same inputs are bit-identical.  Inputs must be finite.
-#include "dhr_state.h"
+#include "host_stage.h"
 
 namespace {
 
@@ -258,12 +258,9 @@ hipError_t launch(const LossArgs& a, int64_t R, float* loss, hipStream_t s) {
 }
 
 // a host [rows][cols] matrix with a row stride -> a packed device copy
-hipError_t stage_in(DevMem& m, Mat& a, int64_t rows, int64_t cols, hipStream_t s) {
+hipError_t stage_mat(DevMem& m, Mat& a, int64_t rows, int64_t cols, hipStream_t s) {
   if (!a.x) return hipSuccess;
-  const int es = a.f32 ? 4 : 2;
-  hipError_t e = hipMalloc(&m.p, (size_t)(rows * cols * es));
-  if (e != hipSuccess) return e;
-  e = hipMemcpy2DAsync(m.p, (size_t)cols * es, a.x, (size_t)a.ld * es, (size_t)cols * es, (size_t)rows, hipMemcpyHostToDevice, s);
+  const hipError_t e = stage_in(m, a.x, a.ld, rows, cols, a.f32 ? 4 : 2, s);
   a = Mat{m.p, cols, a.f32, vec_ok(m.p, cols, a.f32)};
   return e;
 }
@@ -284,8 +281,7 @@ extern "C" int dhr_train_loss(int32_t device, int32_t mem_kind, const void* lexi
   if (!lexical || !loss || !weights) return set_error(DHR_ERR_INVALID, "null pointer");
   if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
   if (rows < 0 || cols < 0) return set_error(DHR_ERR_INVALID, "bad sizes");
-  const auto dtype_ok = [](int32_t d) { return d == DHR_VAL_F16 || d == DHR_VAL_F32; };
-  if (!dtype_ok(lexical_dtype) || (semantic && !dtype_ok(semantic_dtype)) || (teacher && !dtype_ok(teacher_dtype)))
+  if (!val_ok(lexical_dtype) || (semantic && !val_ok(semantic_dtype)) || (teacher && !val_ok(teacher_dtype)))
     return set_error(DHR_ERR_INVALID, "bad value dtype");
   if (ld_lexical < cols || (semantic && ld_semantic < cols) || (teacher && ld_teacher < cols) || (scores_out && ld_scores < cols) ||
       (grad_lexical && ld_grad_lexical < cols) || (grad_semantic && ld_grad_semantic < cols))
@@ -343,14 +339,14 @@ extern "C" int dhr_train_loss(int32_t device, int32_t mem_kind, const void* lexi
     return DHR_OK;
   }
   DevMem m_lex, m_sem, m_tea, m_scores, m_glex, m_gsem, m_ws;
-  HIP_TRY(stage_in(m_lex, a.lex, rows, cols, s));
-  HIP_TRY(stage_in(m_sem, a.sem, rows, cols, s));
-  HIP_TRY(stage_in(m_tea, a.tea, rows, cols, s));
+  HIP_TRY(stage_mat(m_lex, a.lex, rows, cols, s));
+  HIP_TRY(stage_mat(m_sem, a.sem, rows, cols, s));
+  HIP_TRY(stage_mat(m_tea, a.tea, rows, cols, s));
   const int les = a.lex.f32 ? 4 : 2, ses = a.sem.f32 ? 4 : 2;
-  if (scores_out) HIP_TRY(hipMalloc(&m_scores.p, (size_t)(rows * cols * 4)));
-  if (grad_lexical) HIP_TRY(hipMalloc(&m_glex.p, (size_t)(rows * cols * les)));
-  if (grad_semantic) HIP_TRY(hipMalloc(&m_gsem.p, (size_t)(rows * cols * ses)));
-  HIP_TRY(hipMalloc(&m_ws.p, (size_t)(rows * 4 + 4)));
+  if (scores_out) HIP_TRY(dev_alloc(m_scores, rows * cols * 4));
+  if (grad_lexical) HIP_TRY(dev_alloc(m_glex, rows * cols * les));
+  if (grad_semantic) HIP_TRY(dev_alloc(m_gsem, rows * cols * ses));
+  HIP_TRY(dev_alloc(m_ws, rows * 4 + 4));
   a.scores = make_out(m_scores.p, cols, 1);
   a.glex = make_out(m_glex.p, cols, a.lex.f32);
   a.gsem = make_out(m_gsem.p, cols, a.sem.f32);
@@ -358,14 +354,9 @@ extern "C" int dhr_train_loss(int32_t device, int32_t mem_kind, const void* lexi
   float* d_loss = (float*)m_ws.p + rows;
   HIP_TRY(launch(a, rows, d_loss, s));
   HIP_TRY(hipMemcpyAsync(loss, d_loss, 4, hipMemcpyDeviceToHost, s));
-  if (scores_out)
-    HIP_TRY(hipMemcpy2DAsync(scores_out, (size_t)ld_scores * 4, m_scores.p, (size_t)cols * 4, (size_t)cols * 4, (size_t)rows, hipMemcpyDeviceToHost, s));
-  if (grad_lexical)
-    HIP_TRY(hipMemcpy2DAsync(grad_lexical, (size_t)ld_grad_lexical * les, m_glex.p, (size_t)cols * les, (size_t)cols * les, (size_t)rows,
-                             hipMemcpyDeviceToHost, s));
-  if (grad_semantic)
-    HIP_TRY(hipMemcpy2DAsync(grad_semantic, (size_t)ld_grad_semantic * ses, m_gsem.p, (size_t)cols * ses, (size_t)cols * ses, (size_t)rows,
-                             hipMemcpyDeviceToHost, s));
+  if (scores_out) HIP_TRY(stage_out(scores_out, ld_scores, m_scores.p, rows, cols, 4, s));
+  if (grad_lexical) HIP_TRY(stage_out(grad_lexical, ld_grad_lexical, m_glex.p, rows, cols, les, s));
+  if (grad_semantic) HIP_TRY(stage_out(grad_semantic, ld_grad_semantic, m_gsem.p, rows, cols, ses, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
 } DHR_CATCH_STATUS

@@ -8,6 +8,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from . import _marshal as M
 
 
 def _check(lexical_reps, dims, remove_dims):
@@ -19,7 +20,7 @@ def _check(lexical_reps, dims, remove_dims):
     return int(lexical_reps.shape[0]), orig_dims
 
 
-def _run(lexical_reps, dims, remove_dims, out_value, out_index, device):
+def _run(lexical_reps, dims, remove_dims, out_value, out_index):
     lib = _lib.load()
     p_in, ld_in, kind = _lib._ptr_ld(lexical_reps)
     p_v, ld_v, kind_v = _lib._ptr_ld(out_value)
@@ -27,12 +28,8 @@ def _run(lexical_reps, dims, remove_dims, out_value, out_index, device):
     if not (kind == kind_v == kind_i):
         raise _lib.DhrError("densify: input and outputs must live in the same memory kind")
     batch, vocab = int(lexical_reps.shape[0]), int(lexical_reps.shape[1])
-    stream = None
-    if kind == _lib.MEM_DEVICE:
-        import torch
-        stream = torch.cuda.current_stream(lexical_reps.device).cuda_stream
-    _lib.check(lib.dhr_densify(device, kind, p_in, _lib._val_code(lexical_reps), ld_in, batch, vocab, remove_dims, dims, p_v,
-                               _lib._val_code(out_value), ld_v, p_i, _lib.idx_code(out_index.dtype), ld_i, stream), "dhr_densify")
+    _lib.check(lib.dhr_densify(M.device(lexical_reps), kind, p_in, _lib._val_code(lexical_reps), ld_in, batch, vocab, remove_dims, dims, p_v,
+                               _lib._val_code(out_value), ld_v, p_i, _lib.idx_code(out_index.dtype), ld_i, M.stream(lexical_reps)), "dhr_densify")
 
 
 def densify(lexical_reps, dims: int = 768, strategy: str = 'stride', remove_dims: int = 570):
@@ -41,23 +38,18 @@ def densify(lexical_reps, dims: int = 768, strategy: str = 'stride', remove_dims
     batch, vocab = _check(lexical_reps, dims, remove_dims)
     n_groups = (vocab - remove_dims) // dims
     if isinstance(lexical_reps, np.ndarray):
-        src = np.ascontiguousarray(lexical_reps)
-        if src.dtype not in (np.float16, np.float32):
-            src = src.astype(np.float32)
+        src = M.values(np.ascontiguousarray(lexical_reps))
         val = np.empty((batch, dims), src.dtype)
         idx = np.empty((batch, dims), np.int16 if n_groups > 256 else np.uint8)
         if batch:
-            _run(src, dims, remove_dims, val, idx, 0)
+            _run(src, dims, remove_dims, val, idx)
         return val.astype(lexical_reps.dtype, copy=False), idx.astype(np.int64)
     import torch
-    src = lexical_reps.detach()
-    if src.dtype not in (torch.float16, torch.float32):
-        src = src.float()
-    src = src.contiguous()
+    src = M.values(lexical_reps.detach()).contiguous()
     val = torch.empty((batch, dims), dtype=src.dtype, device=src.device)
     idx = torch.empty((batch, dims), dtype=torch.int16 if n_groups > 256 else torch.uint8, device=src.device)
     if batch:
-        _run(src, dims, remove_dims, val, idx, src.device.index or 0 if src.is_cuda else 0)
+        _run(src, dims, remove_dims, val, idx)
     return val.to(lexical_reps.dtype), idx.long()
 
 
@@ -68,8 +60,5 @@ def densify_into(lexical_reps, value_out, index_out, dims: int = 768, remove_dim
     if int(value_out.shape[0]) != batch or int(index_out.shape[0]) != batch or int(value_out.shape[1]) < dims or int(index_out.shape[1]) < dims:
         raise ValueError("output arrays do not match the batch / dims")
     if batch:
-        dev = 0
-        if not isinstance(lexical_reps, np.ndarray) and lexical_reps.is_cuda:
-            dev = lexical_reps.device.index or 0
-        _run(lexical_reps, dims, remove_dims, value_out, index_out, dev)
+        _run(lexical_reps, dims, remove_dims, value_out, index_out)
     return value_out, index_out

@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
 
 
 def shard_bounds(n_docs: int, world: int, rank: int):
@@ -39,7 +39,7 @@ def merge_topk(scores, rows, k: int):
     out_s = torch.empty((q, k), dtype=torch.float32, device=scores.device)
     out_r = torch.empty((q, k), dtype=torch.int64, device=scores.device)
     if scores.is_cuda:
-        stream = torch.cuda.current_stream(scores.device).cuda_stream
+        stream = _marshal.stream(scores)
         _lib.check(lib.dhr_merge_topk(scores.device.index, q, n_in, scores.data_ptr(), rows.data_ptr(), k,
                                       out_s.data_ptr(), out_r.data_ptr(), stream), "dhr_merge_topk")
     else:
@@ -69,7 +69,7 @@ def merge_sorted_lists(scores, rows, k: int):
     pr = rows.data_ptr() if rows is not None else None
     po = out_r.data_ptr() if rows is not None else None
     if scores.is_cuda:
-        stream = torch.cuda.current_stream(scores.device).cuda_stream
+        stream = _marshal.stream(scores)
         _lib.check(lib.dhr_merge_topk_lists(scores.device.index, q, n_lists, ll, scores.data_ptr(), pr, k,
                                             out_s.data_ptr(), po, stream), "dhr_merge_topk_lists")
     else:
@@ -344,7 +344,7 @@ def search_sharded_local(shards, q_value, q_index, k: int):
     rows = torch.empty((qb.n_queries, k), dtype=torch.int64, device=dev)
     arr = (C.c_void_p * len(shards))(*[s._h for s in shards])
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _marshal.stream(scores)
         _lib.check(lib.dhr_search_sharded_local(arr, len(shards), C.byref(qb), int(k), scores.data_ptr(), rows.data_ptr(), _lib.MEM_DEVICE, stream),
                    "dhr_search_sharded_local")
     return scores, rows
@@ -362,7 +362,7 @@ def sharded_search(index, q_value, q_index, k: int, group=None, comm=None):
     scores = torch.empty((qb.n_queries, k), dtype=torch.float32, device=dev)
     rows = torch.empty((qb.n_queries, k), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _marshal.stream(scores)
         _lib.check(lib.dhr_search_sharded(index._h, comm._h, C.byref(qb), int(k), scores.data_ptr(), rows.data_ptr(), _lib.MEM_DEVICE, stream),
                    "dhr_search_sharded")
     return scores, rows

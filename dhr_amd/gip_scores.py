@@ -24,44 +24,16 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from . import _marshal as M
 from .densify import _check as _densify_check
-
-_NARROW = ("uint8", "int8", "int16")
-
-
-def _is_np(a):
-    return isinstance(a, np.ndarray)
-
-
-def _dtype_name(a):
-    return str(a.dtype).replace("torch.", "")
-
-
-def _stream(t):
-    if _is_np(t) or not t.is_cuda:
-        return None
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _device(t):
-    return 0 if _is_np(t) or not t.is_cuda else (t.device.index or 0)
-
-
-def _rows2d(a, what):
-    if len(a.shape) != 2:
-        raise ValueError('{} must be [rows, dims], got {} dimensions'.format(what, len(a.shape)))
-    if _is_np(a):
-        return a if a.strides[1] == a.itemsize and a.strides[0] % a.itemsize == 0 and a.strides[0] >= a.shape[1] * a.itemsize else np.ascontiguousarray(a)
-    return a if a.stride(1) == 1 and a.stride(0) >= a.shape[1] else a.contiguous()
 
 
 def _prepare(q_value, q_index, p_value, p_index, group):
     """Common dtypes and row-strided 2-D views of the four arrays; shape checks.  -> (qv, qi, pv, pi, n_q, n_p, dims)."""
     arrays = (q_value, q_index, p_value, p_index)
-    if len({_is_np(a) for a in arrays}) != 1:
+    if len({M.is_np(a) for a in arrays}) != 1:
         raise TypeError("gip_scores: numpy arrays and torch tensors cannot be mixed")
-    if not _is_np(q_value):
+    if not M.is_np(q_value):
         q_value, q_index, p_value, p_index = (a.detach() for a in arrays)
         if len({a.device for a in (q_value, q_index, p_value, p_index)}) != 1:
             raise _lib.DhrError("gip_scores: all four tensors must live on one device")
@@ -74,37 +46,21 @@ def _prepare(q_value, q_index, p_value, p_index, group):
         raise RuntimeError("gip_scores: queries have {} dims, passages {}".format(dims, int(p_value.shape[1])))
     if group < 0 or (group > 0 and n_p != n_q * group):
         raise RuntimeError("gip_scores: {} passage rows for {} queries x {} passages per query".format(n_p, n_q, group))
-    vname = _dtype_name(q_value) if _dtype_name(q_value) == _dtype_name(p_value) and _dtype_name(q_value) in ("float16", "float32") else "float32"
-    iname = _dtype_name(q_index) if _dtype_name(q_index) == _dtype_name(p_index) and _dtype_name(q_index) in _NARROW else "int16"
-    if _is_np(q_value):
-        cast = lambda a, name: a if a.dtype == np.dtype(name) else a.astype(name)          # noqa: E731
-    else:
-        import torch
-        cast = lambda a, name: a if a.dtype == getattr(torch, name) else a.to(getattr(torch, name))   # noqa: E731
-    qv, pv = _rows2d(cast(q_value, vname), "q_value"), _rows2d(cast(p_value, vname), "p_value")
-    qi, pi = _rows2d(cast(q_index, iname), "q_index"), _rows2d(cast(p_index, iname), "p_index")     # (int64 of densify() is narrowed: groups < 32768)
+    vname = M.common_dtype(q_value, p_value, M.FLOATS, "float32")
+    iname = M.common_dtype(q_index, p_index, M.NARROW, "int16")                # (int64 of densify() is narrowed: groups < 32768)
+    qv, qi, pv, pi = (M.as_read(M.cast(a, name))[0] for a, name in ((q_value, vname), (q_index, iname), (p_value, vname), (p_index, iname)))
     return qv, qi, pv, pi, n_q, n_p, dims
 
 
-def _empty(like, shape, dtype_name):
-    if _is_np(like):
-        return np.empty(shape, dtype_name)
-    import torch
-    return torch.empty(shape, dtype=getattr(torch, dtype_name), device=like.device)
-
-
 def _sides(qv, qi, pv, pi, n_q, n_p):
-    p_qv, ld_qv, kind = _lib._ptr_ld(qv)
-    p_qi, ld_qi, _ = _lib._ptr_ld(qi)
-    p_pv, ld_pv, _ = _lib._ptr_ld(pv)
-    p_pi, ld_pi, _ = _lib._ptr_ld(pi)
-    return kind, (p_qv, ld_qv, p_qi, ld_qi, n_q, p_pv, ld_pv, p_pi, ld_pi, n_p)
+    (ld_qv,), (ld_qi,), (ld_pv,), (ld_pi,) = (M.lds(a) for a in (qv, qi, pv, pi))
+    return M.mem_kind(qv), (M.data_ptr(qv), ld_qv, M.data_ptr(qi), ld_qi, n_q, M.data_ptr(pv), ld_pv, M.data_ptr(pi), ld_pi, n_p)
 
 
 def _forward(qv, qi, pv, pi, n_q, n_p, dims, group):
     """prepared arrays -> fp32 scores [n_q, n_p] (listwise) / [n_q, group]."""
     lib = _lib.load()
-    out = _empty(qv, (n_q, group if group > 0 else n_p), "float32")
+    out = M.empty(qv, (n_q, group if group > 0 else n_p), "float32")
     if n_q == 0 or n_p == 0:
         return out
     kind, sides = _sides(qv, qi, pv, pi, n_q, n_p)
@@ -112,38 +68,29 @@ def _forward(qv, qi, pv, pi, n_q, n_p, dims, group):
     if kind == _lib.MEM_DEVICE:                       # the workspace of a split over dims comes from torch's allocator
         ws_bytes = int(lib.dhr_gip_scores_workspace(n_q, n_p, dims, group))
         if ws_bytes:
-            ws = _empty(qv, (ws_bytes,), "uint8")
+            ws = M.empty(qv, (ws_bytes,), "uint8")
     p_out, ld_out, _ = _lib._ptr_ld(out)
-    _lib.check(lib.dhr_gip_scores(_device(qv), kind, *sides, dims, _lib._val_code(qv), _lib.idx_code(qi.dtype), group, p_out, ld_out,
-                                  None if ws is None else ws.data_ptr(), ws_bytes, _stream(qv)), "dhr_gip_scores")
+    _lib.check(lib.dhr_gip_scores(M.device(qv), kind, *sides, dims, _lib._val_code(qv), _lib.idx_code(qi.dtype), group, p_out, ld_out,
+                                  None if ws is None else ws.data_ptr(), ws_bytes, M.stream(qv)), "dhr_gip_scores")
     return out
 
 
 def _backward(qv, qi, pv, pi, n_q, n_p, dims, group, grad, need_q, need_p):
-    """-> (dL/dq_value, dL/dp_value) fp32, None where not needed.  grad: fp32 [n_q, cols], last dimension contiguous."""
+    """-> (dL/dq_value, dL/dp_value) fp32, None where not needed.  grad: (fp32 [n_q, cols], row stride) as M.grad_rows returns it."""
     lib = _lib.load()
-    dq = _empty(qv, (n_q, dims), "float32") if need_q else None
-    dp = _empty(qv, (n_p, dims), "float32") if need_p else None
+    dq = M.empty(qv, (n_q, dims), "float32") if need_q else None
+    dp = M.empty(qv, (n_p, dims), "float32") if need_p else None
     if not (need_q or need_p):
         return dq, dp
     kind, sides = _sides(qv, qi, pv, pi, n_q, n_p)
-    p_g, ld_g, kind_g = _lib._ptr_ld(grad)
-    if kind_g != kind:
+    grad, ld_g = grad
+    if M.mem_kind(grad) != kind:
         raise _lib.DhrError("gip_scores backward: the gradient must live in the same memory kind as the inputs")
     p_dq, ld_dq = (None, 0) if dq is None else _lib._ptr_ld(dq)[:2]
     p_dp, ld_dp = (None, 0) if dp is None else _lib._ptr_ld(dp)[:2]
-    _lib.check(lib.dhr_gip_scores_backward(_device(qv), kind, *sides, dims, _lib._val_code(qv), _lib.idx_code(qi.dtype), group, p_g, ld_g,
-                                           p_dq, ld_dq, p_dp, ld_dp, _stream(qv)), "dhr_gip_scores_backward")
+    _lib.check(lib.dhr_gip_scores_backward(M.device(qv), kind, *sides, dims, _lib._val_code(qv), _lib.idx_code(qi.dtype), group, M.data_ptr(grad), ld_g,
+                                           p_dq, ld_dq, p_dp, ld_dp, M.stream(qv)), "dhr_gip_scores_backward")
     return dq, dp
-
-
-def _grad2d(grad, n_q, cols):
-    """dL/dS as the kernels read it: fp32 [n_q, cols] with a contiguous last dimension (a transposed or expanded gradient is copied)."""
-    import torch
-    g = grad.detach().reshape(n_q, cols)
-    if g.dtype != torch.float32:
-        g = g.float()
-    return g if cols == 0 or (g.stride(1) == 1 and g.stride(0) >= cols) else g.contiguous()
 
 
 def _densify_fwd(reps, dims, remove_dims):
@@ -151,16 +98,12 @@ def _densify_fwd(reps, dims, remove_dims):
     import torch
     lib = _lib.load()
     B, V = int(reps.shape[0]), int(reps.shape[1])
-    src = reps.detach()
-    if src.dtype not in (torch.float16, torch.float32):
-        src = src.float()
-    src = _rows2d(src, "lexical reps")
+    src, (ld_in,) = M.as_read(M.values(reps.detach()))
     val = torch.empty((B, dims), dtype=torch.float32, device=src.device)
     idx = torch.empty((B, dims), dtype=torch.int16 if (V - remove_dims) // dims > 256 else torch.uint8, device=src.device)
     if B:
-        p_in, ld_in, kind = _lib._ptr_ld(src)
-        _lib.check(lib.dhr_densify(_device(src), kind, p_in, _lib._val_code(src), ld_in, B, V, remove_dims, dims, val.data_ptr(), _lib.VAL_F32, dims,
-                                   idx.data_ptr(), _lib.idx_code(idx.dtype), dims, _stream(src)), "dhr_densify")
+        _lib.check(lib.dhr_densify(M.device(src), M.mem_kind(src), src.data_ptr(), _lib._val_code(src), ld_in, B, V, remove_dims, dims, val.data_ptr(),
+                                   _lib.VAL_F32, dims, idx.data_ptr(), _lib.idx_code(idx.dtype), dims, M.stream(src)), "dhr_densify")
     return val, idx
 
 
@@ -172,9 +115,8 @@ def _densify_bwd(dval, idx, vocab, dims, remove_dims, dtype):
     out_dtype = dtype if dtype in (torch.float16, torch.float32) else torch.float32
     out = torch.empty((B, vocab), dtype=out_dtype, device=dval.device)
     if B:
-        kind = _lib.MEM_DEVICE if dval.is_cuda else _lib.MEM_HOST
-        _lib.check(lib.dhr_densify_backward(_device(dval), kind, dval.data_ptr(), dval.stride(0), idx.data_ptr(), _lib.idx_code(idx.dtype),
-                                            idx.stride(0), B, vocab, remove_dims, dims, out.data_ptr(), _lib._val_code(out), vocab, _stream(dval)),
+        _lib.check(lib.dhr_densify_backward(M.device(dval), M.mem_kind(dval), dval.data_ptr(), dval.stride(0), idx.data_ptr(), _lib.idx_code(idx.dtype),
+                                            idx.stride(0), B, vocab, remove_dims, dims, out.data_ptr(), _lib._val_code(out), vocab, M.stream(dval)),
                    "dhr_densify_backward")
     return out if out_dtype == dtype else out.to(dtype)
 
@@ -199,7 +141,7 @@ def _autograd_fns():
         def backward(ctx, grad):
             qv, qi, pv, pi = ctx.saved_tensors
             n_q, n_p, dims, group, q_dtype, p_dtype = ctx.geom
-            dq, dp = _backward(qv, qi, pv, pi, n_q, n_p, dims, group, _grad2d(grad, n_q, group if group > 0 else n_p), ctx.needs_input_grad[0],
+            dq, dp = _backward(qv, qi, pv, pi, n_q, n_p, dims, group, M.grad_rows(grad, n_q, group if group > 0 else n_p), ctx.needs_input_grad[0],
                                ctx.needs_input_grad[2])
             return (None if dq is None else dq.to(q_dtype)), None, (None if dp is None else dp.to(p_dtype)), None, None
 
@@ -218,7 +160,7 @@ def _autograd_fns():
         def backward(ctx, grad):
             qv, qi, pv, pi = ctx.saved_tensors
             n_q, n_p, dims, remove_dims, group, q_vocab, p_vocab, q_dtype, p_dtype = ctx.geom
-            dq, dp = _backward(qv, qi, pv, pi, n_q, n_p, dims, group, _grad2d(grad, n_q, group if group > 0 else n_p), ctx.needs_input_grad[0],
+            dq, dp = _backward(qv, qi, pv, pi, n_q, n_p, dims, group, M.grad_rows(grad, n_q, group if group > 0 else n_p), ctx.needs_input_grad[0],
                                ctx.needs_input_grad[1])
             gq = None if dq is None else _densify_bwd(dq, qi, q_vocab, dims, remove_dims, q_dtype)
             del dq
@@ -238,14 +180,14 @@ def gip_scores(q_value, q_index, p_value, p_index, group: int = 0):
     -> fp32 [n_q, n_p]; group = n > 0: passage row b * n + j belongs to query b, -> fp32 [n_q, n].  numpy in -> numpy out; torch in -> torch
     out on the same device, differentiable with respect to the two value tensors."""
     group = int(group)
-    if _is_np(q_value):
+    if M.is_np(q_value):
         qv, qi, pv, pi, n_q, n_p, dims = _prepare(q_value, q_index, p_value, p_index, group)
         return _forward(qv, qi, pv, pi, n_q, n_p, dims, group)
     return _autograd_fns()[0].apply(q_value, q_index, p_value, p_index, group)
 
 
 def _fused(q_reps, p_reps, dims, remove_dims, group):
-    if _is_np(q_reps) or _is_np(p_reps):
+    if M.is_np(q_reps) or M.is_np(p_reps):
         from .densify import densify
         qv, qi = densify(np.asarray(q_reps), dims, remove_dims=remove_dims)
         pv, pi = densify(np.asarray(p_reps), dims, remove_dims=remove_dims)
@@ -256,7 +198,7 @@ def _fused(q_reps, p_reps, dims, remove_dims, group):
 
 
 def _squeeze(scores):
-    return np.squeeze(scores) if _is_np(scores) else scores.squeeze()
+    return np.squeeze(scores) if M.is_np(scores) else scores.squeeze()
 
 
 def listwise_gip_scores(q_reps, p_reps, effective_bsz: int, dims: int = 768, remove_dims: int = 570):

@@ -26,6 +26,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from . import _marshal as M
 
 VOCAB_SIZE = 30522
 
@@ -61,58 +62,31 @@ def _densify_check(vocab, dims, remove_dims):
         raise ValueError('Input lexical representation cannot be densified, please fix dims or remove_dims')
 
 
-def _is_np(a):
-    return isinstance(a, np.ndarray)
-
-
-def _device_of(a):
-    return 0 if _is_np(a) or not a.is_cuda else (a.device.index or 0)
-
-
 def _inputs(logits, term_weights, attention_mask):
-    """-> (logits view, pointer, batch / token strides, w fp32 [B, T], mask fp32 [B, T], B, T, V, mem_kind)."""
+    """-> (logits view, batch / token strides, w fp32 [B, T], mask fp32 [B, T], B, T, V)."""
     if len(logits.shape) != 3:
         raise ValueError('logits must be [batch, tokens, vocab], got {} dimensions'.format(len(logits.shape)))
     B, T, V = (int(d) for d in logits.shape)
     if T == 0:
         raise ValueError('no tokens: the maximum over tokens of an empty sequence is undefined')
-    if _is_np(logits):
-        if logits.dtype not in (np.float16, np.float32):
-            raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
-        es = logits.itemsize
-        if logits.strides[2] != es or any(s % es or s < 0 for s in logits.strides[:2]) or logits.strides[1] < V * es or logits.strides[0] < (T - 1) * logits.strides[1] + V * es:
-            logits = np.ascontiguousarray(logits)
-        ldb, ldt = logits.strides[0] // es, logits.strides[1] // es
+    if M.dtype_name(logits) not in M.FLOATS:
+        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
+    if M.is_np(logits):
         w = np.ascontiguousarray(np.asarray(term_weights).reshape(B, T), dtype=np.float32)
         m = np.ascontiguousarray(np.asarray(attention_mask).reshape(B, T), dtype=np.float32)
-        return logits, logits.ctypes.data, ldb, ldt, w, m, B, T, V, _lib.MEM_HOST
-    import torch
-    if logits.dtype not in (torch.float16, torch.float32):
-        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
-    logits = logits.detach()
-    if logits.stride(2) != 1 or logits.stride(1) < V or logits.stride(0) < (T - 1) * logits.stride(1) + V:
-        logits = logits.contiguous()
-    w = term_weights.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
-    m = attention_mask.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
-    kind = _lib.MEM_DEVICE if logits.is_cuda else _lib.MEM_HOST
-    return logits, logits.data_ptr(), logits.stride(0), logits.stride(1), w, m, B, T, V, kind
-
-
-def _ptr(a):
-    return a.ctypes.data if _is_np(a) else a.data_ptr()
-
-
-def _stream(a):
-    """torch's current stream on the tensor's device: the op must run behind the model that produced the tensor"""
-    if _is_np(a) or not a.is_cuda:
-        return None
-    import torch
-    return torch.cuda.current_stream(a.device).cuda_stream
+    else:
+        import torch
+        logits = logits.detach()
+        w = term_weights.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
+        m = attention_mask.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
+    logits, (ldb, ldt) = M.as_read(logits)
+    return logits, ldb, ldt, w, m, B, T, V
 
 
 def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps):
     lib = _lib.load()
-    lg, p_lg, ldb, ldt, w, m, B, T, V, kind = _inputs(logits, term_weights, attention_mask)
+    lg, ldb, ldt, w, m, B, T, V = _inputs(logits, term_weights, attention_mask)
+    kind = M.mem_kind(lg)
     p_v, ld_v, kind_v = _lib._ptr_ld(value_out)
     if kind_v != kind:
         raise _lib.DhrError("lexical head: inputs and outputs must live in the same memory kind")
@@ -124,25 +98,18 @@ def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims,
         idx_dt = _lib.idx_code(index_out.dtype)
     p_c, ld_c, c_dt, c_dim, keep = None, 0, _lib.VAL_F16, 0, None
     if semantic_reps is not None:
-        c = semantic_reps if _is_np(semantic_reps) else semantic_reps.detach()
-        if _is_np(c) and c.dtype not in (np.float16, np.float32):
-            c = c.astype(np.float32)
-        elif not _is_np(c) and str(c.dtype) not in ("torch.float16", "torch.float32"):
-            c = c.float()
+        c = M.values(semantic_reps if M.is_np(semantic_reps) else semantic_reps.detach())
         p_c, ld_c, kind_c = _lib._ptr_ld(c)
         if kind_c != kind:
             raise _lib.DhrError("lexical head: semantic reps must live in the same memory kind as the logits")
         if int(c.shape[0]) != B:
             raise ValueError("semantic reps do not match the batch")
         c_dt, c_dim, keep = _lib._val_code(c), int(c.shape[1]), c
-    ws = None
-    if kind == _lib.MEM_DEVICE and B:
-        import torch
-        ws = torch.empty(B * T * 16, dtype=torch.uint8, device=lg.device)
     if B:
-        _lib.check(lib.dhr_lexical_head(_device_of(lg), kind, mode, p_lg, _lib._val_code(lg), B, T, V, ldb, ldt, _ptr(w), T, _ptr(m), T, dims,
-                                        remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim,
-                                        None if ws is None else ws.data_ptr(), _stream(lg)), "dhr_lexical_head")
+        ws = M.empty(lg, B * T * 16, "uint8") if kind == _lib.MEM_DEVICE else None
+        _lib.check(lib.dhr_lexical_head(M.device(lg), kind, mode, M.data_ptr(lg), _lib._val_code(lg), B, T, V, ldb, ldt, M.data_ptr(w), T,
+                                        M.data_ptr(m), T, dims, remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt,
+                                        ld_c, c_dim, M.data_ptr(ws), M.stream(lg)), "dhr_lexical_head")
     del keep
     return B, V
 
@@ -151,11 +118,7 @@ def lexical_reps(logits, term_weights, attention_mask):
     """-> [B, V] fp32 lexical reps, torch.max((softmax(logits) * term_weights) * attention_mask, dim=-2).values.
     numpy in -> numpy out; torch in -> torch out (same device)."""
     B, V = int(logits.shape[0]), int(logits.shape[-1])
-    if _is_np(logits):
-        out = np.empty((B, V), np.float32)
-    else:
-        import torch
-        out = torch.empty((B, V), dtype=torch.float32, device=logits.device)
+    out = M.empty(logits, (B, V), "float32")
     _run(_lib.LEX_RAW, logits, term_weights, attention_mask, out, None, 0, 0, None)
     return out
 
@@ -199,23 +162,9 @@ def aggregate(lexical_reps, dims: int = 640, remove_dims: int = -198, full: bool
     B, V = int(lexical_reps.shape[0]), int(lexical_reps.shape[1])
     remove, _ = _agg_geometry(B, V, dims, full)
     lib = _lib.load()
-    if _is_np(lexical_reps):
-        src = lexical_reps if lexical_reps.dtype in (np.float16, np.float32) else lexical_reps.astype(np.float32)
-        src = np.ascontiguousarray(src)
-        out = np.empty((B, dims), src.dtype)
-        dev = 0
-    else:
-        import torch
-        src = lexical_reps.detach()
-        if src.dtype not in (torch.float16, torch.float32):
-            src = src.float()
-        src = src.contiguous()
-        out = torch.empty((B, dims), dtype=src.dtype, device=src.device)
-        dev = _device_of(src)
-    p_in, ld_in, kind = _lib._ptr_ld(src)
-    p_o, ld_o, _ = _lib._ptr_ld(out)
-    _lib.check(lib.dhr_aggregate(dev, kind, p_in, _lib._val_code(src), ld_in, B, V, dims, remove, 1 if full else 0, p_o, _lib._val_code(out), ld_o,
-                                 _stream(src)), "dhr_aggregate")
-    if _is_np(lexical_reps):
-        return out.astype(lexical_reps.dtype, copy=False)
-    return out.to(lexical_reps.dtype)
+    src = M.values(lexical_reps if M.is_np(lexical_reps) else lexical_reps.detach())
+    src = np.ascontiguousarray(src) if M.is_np(src) else src.contiguous()
+    out = M.empty(src, (B, dims), src.dtype)
+    _lib.check(lib.dhr_aggregate(M.device(src), M.mem_kind(src), M.data_ptr(src), _lib._val_code(src), V, B, V, dims, remove, 1 if full else 0,
+                                 M.data_ptr(out), _lib._val_code(out), dims, M.stream(src)), "dhr_aggregate")
+    return M.cast(out, lexical_reps.dtype)

@@ -19,6 +19,7 @@ DhrError: there is no staged host path and no CPU implementation."""
 from __future__ import annotations
 
 from . import _lib
+from . import _marshal as M
 from .lexical import _agg_geometry, _check_out, _densify_check
 
 
@@ -45,14 +46,10 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
         raise _lib.DhrError(f"lexical projection head: the hidden size {H} is not a multiple of 8")
     lib = _lib.load()
     dev = hidden.device
-    hidden = hidden.detach()
-    if hidden.stride(2) != 1 or hidden.stride(1) < H or hidden.stride(0) < (T - 1) * hidden.stride(1) + H:
-        hidden = hidden.contiguous()
-    weight = weight.detach()
+    hidden, (ld_batch, ld_token) = M.as_read(hidden.detach())
     if weight.device != dev:
         raise _lib.DhrError("lexical projection head: hidden and weight must live on the same GPU")
-    if weight.stride(1) != 1 or weight.stride(0) < H:
-        weight = weight.contiguous()
+    weight, (ld_weight,) = M.as_read(weight.detach())
     p_b, b_dt = None, _lib.VAL_F32
     if bias is not None:
         _on_gpu("bias", bias)
@@ -73,9 +70,7 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
     p_c, ld_c, c_dt, c_dim, c = None, 0, _lib.VAL_F16, 0, None
     if semantic_reps is not None:
         _on_gpu("semantic_reps", semantic_reps)
-        c = semantic_reps.detach()
-        if c.dtype not in (torch.float16, torch.float32):
-            c = c.float()
+        c = M.values(semantic_reps.detach())
         p_c, ld_c, _ = _lib._ptr_ld(c)
         if int(c.shape[0]) != B:
             raise ValueError("semantic reps do not match the batch")
@@ -83,11 +78,10 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
     if B:
         n_ws = int(lib.dhr_lexical_proj_workspace(B, T, V, mode))
         ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.dhr_lexical_proj_head(dev.index or 0, _lib.MEM_DEVICE, mode, hidden.data_ptr(), _lib.VAL_F16, B, T, H, hidden.stride(0),
-                                             hidden.stride(1), weight.data_ptr(), V, weight.stride(0), p_b, b_dt, w.data_ptr(), T, m.data_ptr(), T,
-                                             dims, remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim,
-                                             ws.data_ptr(), n_ws, stream), "dhr_lexical_proj_head")
+        _lib.check(lib.dhr_lexical_proj_head(M.device(hidden), _lib.MEM_DEVICE, mode, hidden.data_ptr(), _lib.VAL_F16, B, T, H, ld_batch, ld_token,
+                                             weight.data_ptr(), V, ld_weight, p_b, b_dt, w.data_ptr(), T, m.data_ptr(), T, dims, remove_dims, p_v,
+                                             _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim, ws.data_ptr(), n_ws,
+                                             M.stream(hidden)), "dhr_lexical_proj_head")
         # (the call is asynchronous; the temporaries were allocated on the stream it runs on, so the allocator reuses them only behind it)
     return B, V
 

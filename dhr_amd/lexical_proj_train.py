@@ -29,6 +29,7 @@ tensors that autograd hands back, so saved-tensor hooks (`save_on_cpu`, non-reen
 from __future__ import annotations
 
 from . import _lib
+from . import _marshal as M
 
 MAX_TOKENS = 32767
 MAX_HIDDEN = 1024
@@ -77,30 +78,16 @@ def _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens):
     return B, L, T, H, V
 
 
-def _fp16_rows(a, inner):
+def _fp16_rows(a):
     """the fp16 operand as the kernels read it: rounded once if fp32, the last dimension contiguous, rows (and batches) not overlapping"""
-    import torch
-    a = a.detach()
-    if a.dtype != torch.float16:
-        return a.half().contiguous()
-    if a.dim() == 3:
-        n = int(a.shape[1])
-        fine = a.stride(2) == 1 and a.stride(1) >= inner and a.stride(0) >= (n - 1) * a.stride(1) + inner
-    else:
-        fine = a.stride(1) == 1 and a.stride(0) >= inner
-    return a if fine else a.contiguous()
+    return M.as_read(M.cast(a.detach(), "float16"))[0]
 
 
 def _head_args(h, W, b, w, m, B, T, skip_tokens, H, V):
     """the arguments that dhr_lexical_proj_train and dhr_lexical_proj_backward share, from the tensors as they are NOW
     (h, W: as _fp16_rows returns them; b, w [B, T], m [B, T]: contiguous)"""
-    return (h.device.index or 0, _lib.MEM_DEVICE, h.data_ptr(), _lib.VAL_F16, B, T, skip_tokens, H, h.stride(0), h.stride(1), W.data_ptr(), V,
-            W.stride(0), None if b is None else b.data_ptr(), _lib.VAL_F32 if b is None else _lib._val_code(b), w.data_ptr(), T, m.data_ptr(), T)
-
-
-def _stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return (M.device(h), _lib.MEM_DEVICE, h.data_ptr(), _lib.VAL_F16, B, T, skip_tokens, H, *M.lds(h), W.data_ptr(), V, *M.lds(W), M.data_ptr(b),
+            _lib.VAL_F32 if b is None else _lib._val_code(b), w.data_ptr(), T, m.data_ptr(), T)
 
 
 def _function():
@@ -116,7 +103,7 @@ def _function():
             B, L, T, H, V = _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens)
             lib = _lib.load()
             dev = hidden.device
-            h, W = _fp16_rows(hidden, H), _fp16_rows(weight, H)
+            h, W = _fp16_rows(hidden), _fp16_rows(weight)
             b = None if bias is None else bias.detach().contiguous()
             w = term_weights.detach().reshape(B, T).to(torch.float32).contiguous()
             m = attention_mask.detach().reshape(B, T).to(torch.float32).contiguous()
@@ -127,7 +114,7 @@ def _function():
             ws = torch.empty((max(n_ws, 16),), dtype=torch.uint8, device=dev)
             if B:
                 _lib.check(lib.dhr_lexical_proj_train(*_head_args(h, W, b, w, m, B, T, skip_tokens, H, V), reps.data_ptr(), V, tok.data_ptr(), V,
-                                                      pwin.data_ptr(), V, ws.data_ptr(), n_ws, _stream(h)), "dhr_lexical_proj_train")
+                                                      pwin.data_ptr(), V, ws.data_ptr(), n_ws, M.stream(h)), "dhr_lexical_proj_train")
             ctx.save_for_backward(h, W, b, w, m, tok, pwin, ws)
             ctx.geom = (B, L, T, H, V, skip_tokens, n_ws, hidden.dtype, weight.dtype, None if bias is None else bias.dtype,
                         tuple(term_weights.shape), term_weights.dtype)
@@ -139,7 +126,7 @@ def _function():
         def backward(ctx, grad, _grad_tok):
             # ctx keeps scalars only: saved-tensor hooks (save_on_cpu, checkpointing) may hand back the tensors at other addresses
             h, W, b, w, m, tok, pwin, ws = ctx.saved_tensors
-            h, W = _fp16_rows(h, h.shape[-1]), _fp16_rows(W, W.shape[-1])          # (no copies unless a hook changed the layout)
+            h, W = _fp16_rows(h), _fp16_rows(W)          # (no copies unless a hook changed the layout)
             b, w, m, tok, pwin, ws = (None if t is None else t.contiguous() for t in (b, w, m, tok, pwin, ws))
             B, L, T, H, V, skip_tokens, n_ws, h_dtype, W_dtype, b_dtype, w_shape, w_dtype = ctx.geom
             need_h, need_W, need_b, need_w = ctx.needs_input_grad[:4]
@@ -148,21 +135,16 @@ def _function():
                 return None, None, None, None, None, None
             lib = _lib.load()
             dev = h.device
-            g = grad.detach().reshape(B, V)
-            if g.dtype != torch.float32:
-                g = g.float()
-            if not (g.stride(1) == 1 and g.stride(0) >= V):
-                g = g.contiguous()
+            g, ld_g = M.grad_rows(grad, B, V)
             dh = torch.empty((B, L, H), dtype=h_dtype, device=dev) if need_h else None
             dW = torch.empty((V, H), dtype=W_dtype, device=dev) if need_W else None
             db = torch.empty((V,), dtype=b_dtype, device=dev) if need_b else None
             dw = torch.empty((B, T), dtype=torch.float32, device=dev) if need_w else None
             if B:
-                ptr = lambda t: None if t is None else t.data_ptr()
-                code = lambda t: _lib.VAL_F32 if t is None else _lib._val_code(t)
-                _lib.check(lib.dhr_lexical_proj_backward(*_head_args(h, W, b, w, m, B, T, skip_tokens, H, V), g.data_ptr(), g.stride(0),
+                ptr, code = M.data_ptr, lambda t: _lib.VAL_F32 if t is None else _lib._val_code(t)
+                _lib.check(lib.dhr_lexical_proj_backward(*_head_args(h, W, b, w, m, B, T, skip_tokens, H, V), g.data_ptr(), ld_g,
                                                          tok.data_ptr(), V, pwin.data_ptr(), V, ws.data_ptr(), n_ws, ptr(dh), code(dh), L * H, H,
-                                                         ptr(dW), code(dW), H, ptr(db), code(db), ptr(dw), T, _stream(h)),
+                                                         ptr(dW), code(dW), H, ptr(db), code(db), ptr(dw), T, M.stream(h)),
                            "dhr_lexical_proj_backward")
             else:
                 for t in (dW, db):

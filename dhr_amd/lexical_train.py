@@ -28,6 +28,7 @@ device, without a host synchronisation; buffers come from torch's allocator.  Th
 from __future__ import annotations
 
 from . import _lib
+from . import _marshal as M
 
 MAX_TOKENS = 32767
 
@@ -63,18 +64,6 @@ def _check(logits, term_weights, attention_mask, skip_tokens):
     return B, L, T, V
 
 
-def _strided(logits, L, V):
-    """the tensor as the kernels read it: last dimension contiguous, rows and batches not overlapping"""
-    if logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) >= (L - 1) * logits.stride(1) + V:
-        return logits
-    return logits.contiguous()
-
-
-def _stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _function():
     """The torch.autograd.Function (built on first use, like dhr_amd.gip_scores)."""
     global _FN
@@ -87,16 +76,16 @@ def _function():
         def forward(ctx, logits, term_weights, attention_mask, skip_tokens):
             B, L, T, V = _check(logits, term_weights, attention_mask, skip_tokens)
             lib = _lib.load()
-            x = _strided(logits.detach(), L, V)
+            x, (ld_batch, ld_token) = M.as_read(logits.detach())
             w = term_weights.detach().reshape(B, T).to(torch.float32).contiguous()
             m = attention_mask.detach().reshape(B, T).to(torch.float32).contiguous()
             reps = torch.empty((B, V), dtype=torch.float32, device=x.device)
             tok = torch.empty((B, V), dtype=torch.int16, device=x.device)
             ws = torch.empty((int(lib.dhr_lexical_head_train_workspace(B, T)) if B else 0,), dtype=torch.uint8, device=x.device)
             if B:
-                _lib.check(lib.dhr_lexical_head_train(x.device.index or 0, _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x), B, T, skip_tokens, V,
-                                                      x.stride(0), x.stride(1), w.data_ptr(), T, m.data_ptr(), T, reps.data_ptr(), V, tok.data_ptr(), V,
-                                                      ws.data_ptr(), _stream(x)), "dhr_lexical_head_train")
+                _lib.check(lib.dhr_lexical_head_train(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x), B, T, skip_tokens, V, ld_batch,
+                                                      ld_token, w.data_ptr(), T, m.data_ptr(), T, reps.data_ptr(), V, tok.data_ptr(), V, ws.data_ptr(),
+                                                      M.stream(x)), "dhr_lexical_head_train")
             ctx.save_for_backward(x, tok, ws)
             ctx.geom = (B, L, T, V, skip_tokens, tuple(term_weights.shape), term_weights.dtype)
             ctx.mark_non_differentiable(tok)
@@ -111,18 +100,14 @@ def _function():
             if not (need_x or need_w):
                 return None, None, None, None
             lib = _lib.load()
-            g = grad.detach().reshape(B, V)
-            if g.dtype != torch.float32:
-                g = g.float()
-            if V and not (g.stride(1) == 1 and g.stride(0) >= V):
-                g = g.contiguous()
+            g, ld_g = M.grad_rows(grad, B, V)
+            ld_batch, ld_token = M.lds(x)
             dx = torch.empty((B, L, V), dtype=x.dtype, device=x.device) if need_x else None
             dw = torch.empty((B, T), dtype=torch.float32, device=x.device) if need_w else None
             if B:
-                _lib.check(lib.dhr_lexical_head_backward(x.device.index or 0, _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x), B, T, skip_tokens, V,
-                                                         x.stride(0), x.stride(1), g.data_ptr(), g.stride(0), tok.data_ptr(), V, ws.data_ptr(),
-                                                         None if dx is None else dx.data_ptr(), L * V, V, None if dw is None else dw.data_ptr(), T,
-                                                         _stream(x)), "dhr_lexical_head_backward")
+                _lib.check(lib.dhr_lexical_head_backward(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x), B, T, skip_tokens, V, ld_batch,
+                                                         ld_token, g.data_ptr(), ld_g, tok.data_ptr(), V, ws.data_ptr(), M.data_ptr(dx), L * V, V,
+                                                         M.data_ptr(dw), T, M.stream(x)), "dhr_lexical_head_backward")
             return dx, (None if dw is None else dw.to(w_dtype).reshape(w_shape)), None, None
 
     _FN = LexicalReps

@@ -27,60 +27,20 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from . import _marshal as M
 
 MAX_DIMS, MAX_PASSAGE_TOKENS = 1024, 32767
 
 
-def _is_np(a):
-    return isinstance(a, np.ndarray)
-
-
-def _dtype_name(a):
-    return str(a.dtype).replace("torch.", "")
-
-
-def _stream(t):
-    if _is_np(t) or not t.is_cuda:
-        return None
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _device(t):
-    return 0 if _is_np(t) or not t.is_cuda else (t.device.index or 0)
-
-
-def _strides(a):
-    return tuple(s // a.itemsize for s in a.strides) if _is_np(a) else tuple(a.stride())
-
-
-def _tokens3d(a, name):
-    """a [n, L, D] array in one of the kernel dtypes whose strides the library reads in place; anything else is copied once"""
-    n, L, D = (int(d) for d in a.shape)
-    if n == 0 or L == 0:
-        return a
-    sb, st, sd = _strides(a)
-    ok = (sd == 1 or D == 1) and (L == 1 or st >= D) and (n == 1 or sb >= D)
-    if _is_np(a):
-        ok = ok and all(s % a.itemsize == 0 for s in a.strides)
-        return a if ok else np.ascontiguousarray(a)
-    return a if ok else a.contiguous()
-
-
-def _ptr_lds(a):
-    """(pointer, token stride, batch stride, mem_kind); the stride of a dimension of size 1 is free, so it is normalised"""
-    n, L, D = (int(d) for d in a.shape)
-    sb, st, _ = _strides(a)
-    st = D if L == 1 else st
-    sb = L * st if n == 1 else sb
-    if _is_np(a):
-        return a.ctypes.data, st, sb, _lib.MEM_HOST
-    return a.data_ptr(), st, sb, (_lib.MEM_DEVICE if a.is_cuda else _lib.MEM_HOST)
+def _side(a):
+    """(pointer, token stride, batch stride) of a prepared [n, L, D] operand"""
+    st, sb = M.lds(a)[::-1]
+    return M.data_ptr(a), st, sb
 
 
 def _prepare(q, p, group):
     """Shape checks, one common kernel dtype, strided 3-D views.  -> (q, p, A, B, Lq, Lp, D, cols)"""
-    if _is_np(q) != _is_np(p):
+    if M.is_np(q) != M.is_np(p):
         raise TypeError("maxsim_scores: numpy arrays and torch tensors cannot be mixed")
     if len(q.shape) != 3 or len(p.shape) != 3:
         raise ValueError("maxsim_scores: token vectors must be [batch, tokens, dims], got {} and {}".format(tuple(q.shape), tuple(p.shape)))
@@ -95,48 +55,34 @@ def _prepare(q, p, group):
     if D > MAX_DIMS or Lp > MAX_PASSAGE_TOKENS:
         raise _lib.DhrError("maxsim_scores: at most {} dims and {} passage tokens are supported, got {} and {}".format(MAX_DIMS, MAX_PASSAGE_TOKENS, D, Lp),
                             status=_lib.ERR_UNSUPPORTED)
-    if not _is_np(q):
+    if not M.is_np(q):
         q, p = q.detach(), p.detach()
         if q.device != p.device:
             raise _lib.DhrError("maxsim_scores: query and passage vectors must live on one device")
-    name = _dtype_name(q) if _dtype_name(q) == _dtype_name(p) and _dtype_name(q) in ("float16", "float32") else "float32"
-    if _is_np(q):
-        cast = lambda a: a if a.dtype == np.dtype(name) else a.astype(name)          # noqa: E731
-    else:
-        import torch
-        cast = lambda a: a if a.dtype == getattr(torch, name) else a.to(getattr(torch, name))   # noqa: E731
-    return _tokens3d(cast(q), "q"), _tokens3d(cast(p), "p"), A, B, Lq, Lp, D, (group if group > 0 else B)
-
-
-def _empty(like, shape, dtype_name):
-    if _is_np(like):
-        return np.empty(shape, dtype_name)
-    import torch
-    return torch.empty(shape, dtype=getattr(torch, dtype_name), device=like.device)
-
-
-def _data_ptr(a):
-    return a.ctypes.data if _is_np(a) else a.data_ptr()
+    name = M.common_dtype(q, p, M.FLOATS, "float32")
+    # the library reads any token and batch stride >= D in place (batches may overlap); anything else is copied once
+    q, p = (M.as_read(M.cast(a, name), disjoint=False)[0] for a in (q, p))
+    return q, p, A, B, Lq, Lp, D, (group if group > 0 else B)
 
 
 def _forward(q, p, A, B, Lq, Lp, D, cols, group, want_arg):
     """prepared arrays -> (fp32 scores [A, cols], int16 winners [A, cols, Lq] or None)"""
-    out = _empty(q, (A, cols), "float32")
-    arg = _empty(q, (A, cols, Lq), "int16") if want_arg else None
+    out = M.empty(q, (A, cols), "float32")
+    arg = M.empty(q, (A, cols, Lq), "int16") if want_arg else None
     if A == 0 or B == 0:
         return out, arg
     lib = _lib.load()
-    pq, q_tok, q_batch, kind = _ptr_lds(q)
-    pp, p_tok, p_batch, kind_p = _ptr_lds(p)
-    if kind != kind_p:
+    (pq, q_tok, q_batch), (pp, p_tok, p_batch), kind = _side(q), _side(p), M.mem_kind(q)
+    if kind != M.mem_kind(p):
         raise _lib.DhrError("maxsim_scores: query and passage vectors must live in the same memory kind")
-    _lib.check(lib.dhr_maxsim_scores(_device(q), kind, pq, q_tok, q_batch, A, Lq, pp, p_tok, p_batch, B, Lp, D, _lib._val_code(q), group,
-                                     _data_ptr(out), cols, None if arg is None else _data_ptr(arg), _stream(q)), "dhr_maxsim_scores")
+    _lib.check(lib.dhr_maxsim_scores(M.device(q), kind, pq, q_tok, q_batch, A, Lq, pp, p_tok, p_batch, B, Lp, D, _lib._val_code(q), group,
+                                     M.data_ptr(out), cols, M.data_ptr(arg), M.stream(q)), "dhr_maxsim_scores")
     return out, arg
 
 
 def _backward(q, p, A, B, Lq, Lp, D, cols, group, arg, grad, need_q, need_p, q_dtype, p_dtype):
-    """-> (dL/dq [A, Lq, D], dL/dp [B, Lp, D]) in the inputs' own dtypes, None where not needed.  grad: fp32 [A, cols], rows contiguous."""
+    """-> (dL/dq [A, Lq, D], dL/dp [B, Lp, D]) in the inputs' own dtypes, None where not needed.
+    grad: (fp32 [A, cols], row stride) as M.grad_rows returns it."""
     import torch
     lib = _lib.load()
     # the kernels write fp32, or fp16 rounded once; any other input dtype gets its gradient converted from fp32
@@ -144,22 +90,11 @@ def _backward(q, p, A, B, Lq, Lp, D, cols, group, arg, grad, need_q, need_p, q_d
     dq = torch.empty((A, Lq, D), dtype=q.dtype, device=q.device) if need_q else None
     dp = torch.empty((B, Lp, D), dtype=q.dtype, device=q.device) if need_p else None
     if need_q or need_p:
-        pq, q_tok, q_batch, kind = _ptr_lds(q)
-        pp, p_tok, p_batch, _ = _ptr_lds(p)
-        _lib.check(lib.dhr_maxsim_scores_backward(_device(q), kind, pq, q_tok, q_batch, A, Lq, pp, p_tok, p_batch, B, Lp, D, _lib._val_code(q), group,
-                                                  arg.data_ptr(), grad.data_ptr(), grad.stride(0) if A > 1 else cols,
-                                                  None if dq is None else dq.data_ptr(), None if dp is None else dp.data_ptr(), code, _stream(q)),
+        (pq, q_tok, q_batch), (pp, p_tok, p_batch), kind = _side(q), _side(p), M.mem_kind(q)
+        _lib.check(lib.dhr_maxsim_scores_backward(M.device(q), kind, pq, q_tok, q_batch, A, Lq, pp, p_tok, p_batch, B, Lp, D, _lib._val_code(q), group,
+                                                  arg.data_ptr(), grad[0].data_ptr(), grad[1], M.data_ptr(dq), M.data_ptr(dp), code, M.stream(q)),
                    "dhr_maxsim_scores_backward")
     return (None if dq is None else dq.to(q_dtype)), (None if dp is None else dp.to(p_dtype))
-
-
-def _grad2d(grad, rows, cols):
-    """dL/dS as the kernels read it: fp32 [rows, cols] with a contiguous last dimension (a transposed or expanded gradient is copied)."""
-    import torch
-    g = grad.detach().reshape(rows, cols)
-    if g.dtype != torch.float32:
-        g = g.float()
-    return g if cols == 0 or rows == 0 or (g.stride(1) == 1 and g.stride(0) >= cols) or (cols == 1 and g.stride(0) >= 1) else g.contiguous()
 
 
 def _autograd_fn():
@@ -186,7 +121,7 @@ def _autograd_fn():
             if A == 0 or B == 0:
                 z = lambda n, L, dt, need: torch.zeros((n, L, D), dtype=dt, device=qq.device) if need else None   # noqa: E731
                 return z(A, Lq, q_dtype, ctx.needs_input_grad[0]), z(B, Lp, p_dtype, ctx.needs_input_grad[1]), None
-            dq, dp = _backward(qq, pp, A, B, Lq, Lp, D, cols, group, arg, _grad2d(grad, A, cols), ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+            dq, dp = _backward(qq, pp, A, B, Lq, Lp, D, cols, group, arg, M.grad_rows(grad, A, cols), ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                q_dtype, p_dtype)
             return dq, dp, None
 
@@ -203,7 +138,7 @@ def maxsim_scores(q, p, group: int = 0):
     row a * n + j belongs to query a, -> fp32 [A, n].  numpy in -> numpy out (forward only); torch in -> torch out on the same device,
     differentiable with respect to both."""
     group = int(group)
-    if not (_is_np(q) or _is_np(p)):
+    if not (M.is_np(q) or M.is_np(p)):
         import torch
         if torch.is_grad_enabled() and (q.requires_grad or p.requires_grad):
             return _autograd_fn().apply(q, p, group)
@@ -219,7 +154,7 @@ def _check3d(q, p, what):
 
 
 def _squeeze(scores):
-    return np.squeeze(scores) if _is_np(scores) else scores.squeeze()
+    return np.squeeze(scores) if M.is_np(scores) else scores.squeeze()
 
 
 def listwise_maxsim(q_seq_reps, p_seq_reps):

@@ -19,7 +19,7 @@ import pickle
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _marshal
 
 PQ_FORMAT = "dhr-pq"
 
@@ -31,12 +31,6 @@ def _f16_values(values):
         return values if values.dtype == np.float16 else values.astype(np.float16)
     import torch
     return values if values.dtype == torch.float16 else values.half()
-
-
-def _stream(t):
-    """torch's current stream on the tensor's device.  The three wrappers below wait for it: their results are complete on return."""
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def train_and_encode(values, M: int = 64, n_bits: int = 8, iters: int = 25, max_points: int = 65536, device: int = 0):
@@ -64,7 +58,7 @@ def train_and_encode(values, M: int = 64, n_bits: int = 8, iters: int = 25, max_
         cb = torch.empty((M, ksub, d // M), dtype=torch.float32, device=values.device)
         codes = torch.empty((n, M), dtype=torch.uint8, device=values.device)
         pcb, pcodes = cb.data_ptr(), codes.data_ptr()
-        stream = _stream(values)
+        stream = _marshal.stream(values)
     _lib.check(lib.dhr_pq_train_nbits(device, kind, p, ld, n, d, M, int(n_bits), iters, max(max_points, ksub), pcb, C.byref(err), stream), "dhr_pq_train")
     _lib.check(lib.dhr_pq_encode_nbits(device, kind, p, ld, n, d, M, int(n_bits), pcb, pcodes, stream), "dhr_pq_encode")
     return cb, codes, float(err.value)
@@ -89,7 +83,7 @@ def encode(values, codebooks, n_bits: int = 8, device: int = 0):
         cb = codebooks.contiguous()
         codes = torch.empty((n, M), dtype=torch.uint8, device=values.device)
         pcb, pcodes = cb.data_ptr(), codes.data_ptr()
-        stream = _stream(values)
+        stream = _marshal.stream(values)
     _lib.check(lib.dhr_pq_encode_nbits(device, kind, p, ld, n, d, M, int(n_bits), pcb, pcodes, stream), "dhr_pq_encode")
     return codes
 
@@ -109,7 +103,7 @@ def decode(codebooks, codes, device: int = 0):
     import torch
     out = torch.empty((n, d), dtype=torch.float16, device=codes.device)
     codes, cb = codes.to(torch.uint8).contiguous(), codebooks.to(torch.float32).contiguous()
-    _lib.check(lib.dhr_pq_decode_nbits(device, _lib.MEM_DEVICE, codes.data_ptr(), n, d, M, nbits, cb.data_ptr(), out.data_ptr(), d, _stream(codes)),
+    _lib.check(lib.dhr_pq_decode_nbits(device, _lib.MEM_DEVICE, codes.data_ptr(), n, d, M, nbits, cb.data_ptr(), out.data_ptr(), d, _marshal.stream(codes)),
                "dhr_pq_decode")
     return out
 

@@ -30,39 +30,22 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _lib
+from . import _marshal as M
 
 DHR_WEIGHTS, DHR_SPLIT = (1.0, 0.5, 0.5), (1.0, 0.75, 0.25)       # modeling.py:184-187: fused, semantic at 3/4, lexical at 1/4
 FUSED_ONLY = (1.0, 0.0, 0.0)
 
 
-def _stream(t):
-    if not t.is_cuda:
-        return None
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _device(t):
-    return (t.device.index or 0) if t.is_cuda else 0
-
-
-def _matrix(t):
-    """a [R, C] tensor as the kernel reads it: fp16 / fp32 with a contiguous last dimension and a row stride of at least C"""
-    import torch
-    t = t.detach()
-    if t.dtype not in (torch.float16, torch.float32):
-        t = t.float()
-    R, C_ = (int(d) for d in t.shape)
-    if R == 0 or C_ == 0 or ((t.stride(1) == 1 or C_ == 1) and (R == 1 or t.stride(0) >= C_)):
-        return t
-    return t.contiguous()
+def _read(t):
+    """a [R, C] tensor, or None, as the kernel reads it: fp16 / fp32, row-strided views in place"""
+    return None if t is None else M.as_read(M.values(t.detach()))[0]
 
 
 def _arg(t):
     """(pointer, dtype code, row stride) of a prepared matrix, or of an absent one"""
     if t is None:
         return None, _lib.VAL_F32, 0
-    return t.data_ptr(), _lib._val_code(t), (int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]))
+    return t.data_ptr(), _lib._val_code(t), M.lds(t)[0]
 
 
 def _check(lexical, semantic, teacher, train_n_passages, lamb, temperature, weights, teacher_split):
@@ -107,15 +90,15 @@ def _launch(lexical, semantic, teacher, R, C_, label_stride, lamb, temperature, 
     loss = torch.empty((), dtype=torch.float32, device=dev)
     g_lex = torch.empty((R, C_), dtype=lexical.dtype, device=dev) if need_lex else None
     g_sem = torch.empty((R, C_), dtype=semantic.dtype, device=dev) if need_sem and semantic is not None else None
-    kind = _lib.MEM_DEVICE if lexical.is_cuda else _lib.MEM_HOST
+    kind = M.mem_kind(lexical)
     ws, ws_bytes = None, 0
     if kind == _lib.MEM_DEVICE:                       # the row losses come from torch's allocator: the library allocates nothing
         ws_bytes = int(lib.dhr_train_loss_workspace(R))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    _lib.check(lib.dhr_train_loss(_device(lexical), kind, *_arg(lexical), *_arg(semantic), *_arg(teacher), R, C_, label_stride, float(lamb),
+    ptr = M.data_ptr
+    _lib.check(lib.dhr_train_loss(M.device(lexical), kind, *_arg(lexical), *_arg(semantic), *_arg(teacher), R, C_, label_stride, float(lamb),
                                   float(temperature), (C.c_float * 3)(*weights), (C.c_float * 3)(*teacher_split), loss.data_ptr(), scores.data_ptr(), C_,
-                                  ptr(g_lex), C_, ptr(g_sem), C_, ptr(ws), ws_bytes, _stream(lexical)), "dhr_train_loss")
+                                  ptr(g_lex), C_, ptr(g_sem), C_, ptr(ws), ws_bytes, M.stream(lexical)), "dhr_train_loss")
     return loss, scores, g_lex, g_sem
 
 
@@ -132,8 +115,7 @@ def _autograd_fn():
             R, C_, label_stride, lamb, temperature, weights, teacher_split = cfg
             need_lex = ctx.needs_input_grad[0]
             need_sem = semantic is not None and ctx.needs_input_grad[1]
-            loss, scores, g_lex, g_sem = _launch(_matrix(lexical), None if semantic is None else _matrix(semantic),
-                                                 None if teacher is None else _matrix(teacher), R, C_, label_stride, lamb, temperature, weights,
+            loss, scores, g_lex, g_sem = _launch(_read(lexical), _read(semantic), _read(teacher), R, C_, label_stride, lamb, temperature, weights,
                                                  teacher_split, need_lex, need_sem)
             ctx.save_for_backward(*(g for g in (g_lex, g_sem) if g is not None))
             ctx.have = (g_lex is not None, g_sem is not None)
@@ -180,9 +162,8 @@ def hybrid_loss(lexical_scores, semantic_scores=None, teacher_scores=None, *, tr
         return _autograd_fn().apply(lexical_scores, semantic_scores, teacher_scores, (R, C_, label_stride, float(lamb), float(temperature), weights,
                                                                                      teacher_split))
     # nothing to differentiate: null gradient pointers
-    loss, scores, _, _ = _launch(_matrix(lexical_scores), None if semantic_scores is None else _matrix(semantic_scores),
-                                 None if teacher_scores is None else _matrix(teacher_scores), R, C_, label_stride, lamb, temperature, weights,
-                                 teacher_split, False, False)
+    loss, scores, _, _ = _launch(_read(lexical_scores), _read(semantic_scores), _read(teacher_scores), R, C_, label_stride, lamb, temperature,
+                                 weights, teacher_split, False, False)
     return loss, scores
 
 

@@ -481,3 +481,38 @@ def test_timing_printout():
               " / ".join(f"{t:.3f}" for t in e) + f" ms, {np.median(e) / np.median(f):.1f}x")
         del q, p, G
         torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group,n_p", [(0, 4), (2, 6)])
+def test_host_arrays_with_row_strides_match_the_device_path(group, n_p):
+    """n_q = 3, dims = 8, every operand of the three entry points a host array cut from a wider base (row stride > row): staged through the
+    device, complete on return, and the bits of the same views processed on the device.  The columns beside an output stay untouched."""
+    import torch
+    from dhr_amd import gip_scores as GS
+    lib = _lib.load()
+    n_q, dims, W = 3, 8, 12
+    cols = group or n_p
+    rng = np.random.default_rng(5)
+    bqv, bpv = (rng.uniform(-2, 2, (n, W)).astype(np.float32) for n in (n_q, n_p))
+    bqi, bpi = (rng.integers(0, 4, (n, W)).astype(np.uint8) for n in (n_q, n_p))
+    bG = rng.uniform(-1, 1, (n_q, cols + 3)).astype(np.float32)
+    out, dq, dp = (np.full((n, c + 2), 7, np.float32) for n, c in ((n_q, cols), (n_q, dims), (n_p, dims)))
+    sides = (bqv.ctypes.data, W, bqi.ctypes.data, W, n_q, bpv.ctypes.data, W, bpi.ctypes.data, W, n_p, dims, _lib.VAL_F32, _lib.IDX_U8, group)
+    assert lib.dhr_gip_scores(0, _lib.MEM_HOST, *sides, out.ctypes.data, cols + 2, None, 0, None) == _lib.DHR_OK, lib.dhr_last_error()
+    assert lib.dhr_gip_scores_backward(0, _lib.MEM_HOST, *sides, bG.ctypes.data, cols + 3, dq.ctypes.data, dims + 2, dp.ctypes.data, dims + 2,
+                                       None) == _lib.DHR_OK, lib.dhr_last_error()
+    dev = lambda a, n: torch.from_numpy(a).cuda()[:, :n]   # noqa: E731
+    tq, tp = dev(bqv, dims).requires_grad_(True), dev(bpv, dims).requires_grad_(True)
+    s = GS.gip_scores(tq, dev(bqi, dims), tp, dev(bpi, dims), group)
+    s.backward(dev(bG, cols))
+    for host, n, t in ((out, cols, s.detach()), (dq, dims, tq.grad), (dp, dims, tp.grad)):
+        assert np.array_equal(host[:, :n], t.cpu().numpy()) and (host[:, n:] == 7).all()
+    # dhr_densify_backward: dL/dvalue [n_q, 8] and the groups of the query side -> dL/dreps [n_q, 42] (10 removed columns, 4 groups of 8)
+    vocab, remove = 42, 10
+    bdv = rng.uniform(-1, 1, (n_q, W)).astype(np.float32)
+    grad = np.full((n_q, vocab + 2), 7, np.float32)
+    assert lib.dhr_densify_backward(0, _lib.MEM_HOST, bdv.ctypes.data, W, bqi.ctypes.data, _lib.IDX_U8, W, n_q, vocab, remove, dims, grad.ctypes.data,
+                                    _lib.VAL_F32, vocab + 2, None) == _lib.DHR_OK, lib.dhr_last_error()
+    want = GS._densify_bwd(dev(bdv, dims), dev(bqi, dims), vocab, dims, remove, torch.float32)
+    assert np.array_equal(grad[:, :vocab], want.cpu().numpy()) and (grad[:, vocab:] == 7).all()

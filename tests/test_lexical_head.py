@@ -406,3 +406,40 @@ def test_timing_printout():
               f"torch {res['torch']:.3f} ms ({nbytes / res['torch'] / 1e9:.2f} TB/s), {res['torch'] / res['fused']:.2f}x")
         del full
         torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_host_arrays_with_strides_match_the_device_path():
+    """B = 2, T = 3, V = 32 logits as base[:, 1:, :32] of a [2, 4, 40] base (token stride > V), records and reps in wider rows: the staged host
+    paths of dhr_lexical_head (all modes) and dhr_aggregate give the bits of the same views on the device."""
+    import torch
+    lib = _lib.load()
+    rng = np.random.default_rng(11)
+    base = (rng.standard_normal((2, 4, 40)) * 3).astype(np.float16)
+    w, mk = rng.uniform(0.5, 2, (2, 3)).astype(np.float32), np.array([[1, 1, 0], [1, 1, 1]], np.int64)
+    cls = rng.standard_normal((2, 7)).astype(np.float32)[:, :4]
+    h_in = (base[:, 1:, :32], w, mk)
+    d_in = (torch.from_numpy(base).cuda()[:, 1:, :32], torch.from_numpy(w).cuda(), torch.from_numpy(mk).cuda())
+    reps = LX.lexical_reps(*h_in)
+    assert np.array_equal(reps, LX.lexical_reps(*d_in).cpu().numpy())
+    hv, hi = np.full((2, 15), 7, np.float16), np.full((2, 11), 99, np.uint8)
+    dv, di = torch.from_numpy(hv).cuda(), torch.from_numpy(hi).cuda()
+    LX.densify_lexical_into(*h_in, hv[:, :12], hi[:, :8], 8, 0, semantic_reps=cls)
+    LX.densify_lexical_into(*d_in, dv[:, :12], di[:, :8], 8, 0, semantic_reps=torch.from_numpy(cls).cuda())
+    assert np.array_equal(hv.view(np.uint16), dv.cpu().numpy().view(np.uint16)) and np.array_equal(hi, di.cpu().numpy())
+    assert (hv[:, 12:] == 7).all() and (hi[:, 8:] == 99).all() and not (hv[:, :12] == 7).all()
+    for agg, full in ((1, True), (2, False)):                              # cal_remove_dim(2 * 1) = cal_remove_dim(2) = 0: 32 columns fold whole
+        ha = np.full((2, agg + 6), 7, np.float32)
+        da = torch.from_numpy(ha).cuda()
+        LX.aggregate_lexical_into(*h_in, ha[:, :agg + 4], agg, full=full, semantic_reps=cls)
+        LX.aggregate_lexical_into(*d_in, da[:, :agg + 4], agg, full=full, semantic_reps=torch.from_numpy(cls).cuda())
+        assert np.array_equal(ha.view(np.uint32), da.cpu().numpy().view(np.uint32)) and (ha[:, agg + 4:] == 7).all()
+        # dhr_aggregate on reps cut from a 40-column base, into a wider output
+        wide, out = np.zeros((2, 40), np.float32), np.full((2, agg + 3), 7, np.float32)
+        wide[:, :32] = reps
+        d_wide, d_out = torch.from_numpy(wide).cuda(), torch.from_numpy(out).cuda()
+        for kind, src, dst in ((_lib.MEM_HOST, wide.ctypes.data, out.ctypes.data), (_lib.MEM_DEVICE, d_wide.data_ptr(), d_out.data_ptr())):
+            assert lib.dhr_aggregate(0, kind, src, _lib.VAL_F32, 40, 2, 32, agg, 0, int(full), dst, _lib.VAL_F32, agg + 3,
+                                     torch.cuda.current_stream().cuda_stream if kind == _lib.MEM_DEVICE else None) == _lib.DHR_OK, lib.dhr_last_error()
+        assert np.array_equal(out.view(np.uint32), d_out.cpu().numpy().view(np.uint32)) and (out[:, agg:] == 7).all()
+        assert np.array_equal(out[:, :agg], LX.aggregate(reps, agg, full=full))

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import pytest
 
-from dhr_amd import _lib
+from dhr_amd import _lib, _marshal
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "maxsim_golden.npz")
@@ -477,8 +477,8 @@ def test_runs_are_bit_identical_and_forms_agree(monkeypatch):
         spy = _Spy(_lib.load())
         monkeypatch.setattr(_lib, "load", lambda: spy)
         made = []
-        real_empty = MS._empty
-        monkeypatch.setattr(MS, "_empty", lambda like, shape, name: made.append(name) or real_empty(like, shape, name))
+        real_empty = _marshal.empty
+        monkeypatch.setattr(_marshal, "empty", lambda like, shape, name: made.append(name) or real_empty(like, shape, name))
         with torch.no_grad():
             s0 = MS.maxsim_scores(tq, tp)
         s1 = MS.maxsim_scores(q, p)
@@ -560,3 +560,28 @@ def test_timing_printout():
               " / ".join(f"{t:.3f}" for t in e) + f" ms, {np.median(e) / np.median(f):.1f}x")
         del q, p, G
         torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_host_arrays_with_strides_match_the_device_path():
+    """A = 2, B = 3, Lq = 2, Lp = 3, D = 5 as base[:, 1:, :5] of bases with D padded to 8, scores and the upstream gradient in wider rows:
+    both entry points on host pointers (staged through the device, complete on return) give the bits of the same views on the device."""
+    import torch
+    from dhr_amd import maxsim_scores as MS
+    lib = _lib.load()
+    A, B, Lq, Lp, D = 2, 3, 2, 3, 5
+    rng = np.random.default_rng(9)
+    bq, bp = rng.uniform(-1, 1, (A, Lq + 1, 8)).astype(np.float32), rng.uniform(-1, 1, (B, Lp + 1, 8)).astype(np.float32)
+    bG = rng.uniform(-1, 1, (A, B + 2)).astype(np.float32)
+    out, arg = np.full((A, B + 1), 7, np.float32), np.zeros((A, B, Lq), np.int16)
+    dq, dp = np.zeros((A, Lq, D), np.float32), np.zeros((B, Lp, D), np.float32)
+    sides = (bq[:, 1:].ctypes.data, 8, (Lq + 1) * 8, A, Lq, bp[:, 1:].ctypes.data, 8, (Lp + 1) * 8, B, Lp, D, _lib.VAL_F32, 0)
+    assert lib.dhr_maxsim_scores(0, _lib.MEM_HOST, *sides, out.ctypes.data, B + 1, arg.ctypes.data, None) == _lib.DHR_OK, lib.dhr_last_error()
+    assert lib.dhr_maxsim_scores_backward(0, _lib.MEM_HOST, *sides, arg.ctypes.data, bG.ctypes.data, B + 2, dq.ctypes.data, dp.ctypes.data, _lib.VAL_F32,
+                                          None) == _lib.DHR_OK, lib.dhr_last_error()
+    tq, tp = (torch.from_numpy(b).cuda()[:, 1:, :D].requires_grad_(True) for b in (bq, bp))
+    s = MS.maxsim_scores(tq, tp)
+    s.backward(torch.from_numpy(bG).cuda()[:, :B])
+    assert np.array_equal(out[:, :B], s.detach().cpu().numpy()) and (out[:, B:] == 7).all()
+    assert np.array_equal(dq, tq.grad.cpu().numpy()) and np.array_equal(dp, tp.grad.cpu().numpy())
+    assert np.array_equal(MS.maxsim_scores(bq[:, 1:, :D], bp[:, 1:, :D]), out[:, :B])          # numpy in -> numpy out, the same bits

@@ -13,7 +13,7 @@ DHR_OK = 0
 ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_INTERNAL, ERR_NOMEM, ERR_PEER = -1, -2, -3, -4, -5, -6
 ABI_INDEX_DESC, ABI_QUERY_BATCH, ABI_SEARCH_STATS, ABI_FILE_INFO, ABI_HOST_SHARD = 0, 1, 2, 3, 4
 IDX_NONE, IDX_U8, IDX_I8, IDX_I16 = 0, 1, 2, 3
-VAL_F16, VAL_F32 = 0, 1
+VAL_F16, VAL_F32, VAL_BF16 = 0, 1, 2     # VAL_BF16: the lexical heads alone take it (dhr_hip.h), every other entry point answers DHR_ERR_INVALID
 MEM_HOST, MEM_DEVICE = 0, 1
 LEX_RAW, LEX_DENSIFY, LEX_AGG_FULL, LEX_AGG_SEMI = 0, 1, 2, 3
 PARAM_CAND_CAP, PARAM_FIRST_ROWS, PARAM_PROFILE, PARAM_MAX_GROWTH, PARAM_SAMPLE_PERIOD, PARAM_GEMM_VARIANT, PARAM_MAIN_CHUNKS, PARAM_PROGRESSIVE_THR, PARAM_AUX_CUS, PARAM_GEMM_EXCLUSIVE, PARAM_OVERLAP_AUX, PARAM_SAMPLE_SHARE, PARAM_ASYNC_CONTROLLER, PARAM_LIST_STRIDE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14
@@ -296,13 +296,17 @@ def _ptr_ld(a):
     return a.data_ptr(), a.stride(0), (MEM_DEVICE if a.is_cuda else MEM_HOST)
 
 
-def _val_code(a) -> int:
+def _val_code(a, bf16: bool = False) -> int:
+    """dhr_val_dtype of an array or tensor.  bf16=True: the arguments of the lexical heads that take DHR_VAL_BF16; for every other argument
+    bfloat16 is refused here, as the library would refuse it."""
     name = str(a.dtype).replace("torch.", "")
     if name == "float16":
         return VAL_F16
     if name == "float32":
         return VAL_F32
-    raise DhrError(f"unsupported value dtype {a.dtype} (float16 / float32)")
+    if name == "bfloat16" and bf16:
+        return VAL_BF16
+    raise DhrError(f"unsupported value dtype {a.dtype} ({'float16 / bfloat16 / float32' if bf16 else 'float16 / float32'})")
 
 
 def make_query_batch(value, index):

@@ -5,6 +5,8 @@
 #include "dhr_state.h"
 
 static inline int val_ok(int dt) { return dt == DHR_VAL_F16 || dt == DHR_VAL_F32; }
+// the lexical heads alone: their logits / operands, the projection's bias and the gradients of their backward calls may also be bf16
+static inline int val_ok_bf16(int dt) { return val_ok(dt) || dt == DHR_VAL_BF16; }
 static inline int idx_ok(int dt) { return dt == DHR_IDX_U8 || dt == DHR_IDX_I8 || dt == DHR_IDX_I16; }
 static inline int val_esize(int dt) { return dt == DHR_VAL_F32 ? 4 : 2; }
 

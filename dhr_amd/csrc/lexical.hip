@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) lexical_cls_kernel(const void* __restrict
   }
 }
 
-hipError_t launch_fold(const void* logits, int in_f32, int mode, const FoldArgs& a0, hipStream_t s) {
+hipError_t launch_fold(const void* logits, int in_dtype, int mode, const FoldArgs& a0, hipStream_t s) {
   FoldArgs a = a0;
   a.GS = a.n_groups >= 8 ? 8 : a.n_groups >= 4 ? 4 : a.n_groups >= 2 ? 2 : 1;
   a.PB = 256 / a.GS;
@@ -154,7 +154,7 @@ hipError_t launch_fold(const void* logits, int in_f32, int mode, const FoldArgs&
     case MODE_AGG_FULL: DHR_FOLD(T_, MODE_AGG_FULL); break; \
     default: DHR_FOLD(T_, MODE_AGG_SEMI); break;           \
   }
-  if (in_f32) { DHR_FOLD_MODES(float) } else { DHR_FOLD_MODES(_Float16) }
+  if (in_dtype == DHR_VAL_F32) { DHR_FOLD_MODES(float) } else if (in_dtype == DHR_VAL_BF16) { DHR_FOLD_MODES(__bf16) } else { DHR_FOLD_MODES(_Float16) }
 #undef DHR_FOLD_MODES
 #undef DHR_FOLD
   return hipGetLastError();
@@ -171,7 +171,7 @@ hipError_t dhr::lexical_record_from_reps(const float* reps, int64_t ld_reps, int
     a.ld_batch = ld_reps; a.ld_token = vocab; a.T = 1; a.V = vocab; a.stats = nullptr;
     a.remove = remove; a.W = W; a.n_groups = n_groups; a.batch = batch;
     a.out_val = out_val; a.val_f32 = val_f32; a.ld_val = ld_val; a.out_idx = out_idx; a.idx_i16 = idx_i16; a.ld_idx = ld_idx;
-    const hipError_t e = launch_fold(reps, 1, mode, a, s);
+    const hipError_t e = launch_fold(reps, DHR_VAL_F32, mode, a, s);
     if (e != hipSuccess) return e;
   }
   if (cls_dim > 0) {
@@ -189,7 +189,7 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   dhr::alloc_checkpoint();
   if (!logits || !term_weights || !mask || !out_value) return set_error(DHR_ERR_INVALID, "null pointer");
   if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
-  if (!val_ok(logits_dtype) || !val_ok(out_value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (!val_ok_bf16(logits_dtype) || !val_ok(out_value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
   if (batch < 0 || n_tokens <= 0 || vocab <= 0 || ld_token < vocab || ld_batch < (int64_t)(n_tokens - 1) * ld_token + vocab ||
       ld_weights < n_tokens || ld_mask < n_tokens || cls_dim < 0 || (int64_t)batch * n_tokens > ((int64_t)1 << 31) - 1)
     return set_error(DHR_ERR_INVALID, "bad sizes / strides");
@@ -217,6 +217,9 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
     if (logits_dtype == DHR_VAL_F32)
       hipLaunchKernelGGL(lexical_stats_kernel<float>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const float*)lg, ldb, ldt, T, vocab, w, ldw, m,
                          ldm, stats);
+    else if (logits_dtype == DHR_VAL_BF16)
+      hipLaunchKernelGGL(lexical_stats_kernel<__bf16>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const __bf16*)lg, ldb, ldt, T, vocab, w, ldw,
+                         m, ldm, stats);
     else
       hipLaunchKernelGGL(lexical_stats_kernel<_Float16>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const _Float16*)lg, ldb, ldt, T, vocab, w,
                          ldw, m, ldm, stats);
@@ -225,7 +228,7 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
     FoldArgs f = a;
     f.ld_batch = ldb; f.ld_token = ldt; f.stats = stats; f.batch = rows;
     f.out_val = val; f.ld_val = ldv; f.out_idx = idx; f.ld_idx = ldi;
-    if ((e = launch_fold(lg, logits_dtype == DHR_VAL_F32, mode, f, s)) != hipSuccess) return e;
+    if ((e = launch_fold(lg, logits_dtype, mode, f, s)) != hipSuccess) return e;
     if (cls_dim > 0) {
       const unsigned blocks = (unsigned)std::min<int64_t>((rows * cls_dim + 255) / 256, 4096);
       hipLaunchKernelGGL(lexical_cls_kernel, dim3(blocks), dim3(256), 0, s, c, cls_dtype == DHR_VAL_F32, ldc, cls_dim, rows, val,
@@ -294,7 +297,7 @@ extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexic
   a.remove = geo.remove; a.W = geo.W; a.n_groups = geo.n_groups; a.val_f32 = out_dtype == DHR_VAL_F32;
   if (mem_kind == DHR_MEM_DEVICE) {
     a.batch = batch; a.out_val = out; a.ld_val = ld_out;
-    HIP_TRY(launch_fold(lexical, value_dtype == DHR_VAL_F32, mode, a, s));
+    HIP_TRY(launch_fold(lexical, value_dtype, mode, a, s));
     HIP_TRY(hipStreamSynchronize(s));
     return DHR_OK;
   }
@@ -307,7 +310,7 @@ extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexic
     const int64_t rows = std::min(block, batch - lo);
     a.batch = rows;
     if (copy_in(m_in.p, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
-    if (launch_fold(m_in.p, value_dtype == DHR_VAL_F32, mode, a, s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate launch failed");
+    if (launch_fold(m_in.p, value_dtype, mode, a, s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate launch failed");
     if (stage_out((char*)out + lo * ld_out * oes, ld_out, m_out.p, rows, dims, oes, s) != hipSuccess) return set_error(DHR_ERR_HIP, "D2H failed");
     if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate failed on the device");
   }

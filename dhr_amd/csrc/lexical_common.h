@@ -17,9 +17,11 @@ hipError_t lexical_record_from_reps(const float* reps, int64_t ld_reps, int mode
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 template <typename TIN> struct Vec;
 template <> struct Vec<_Float16> { typedef half8 type; static constexpr int n = 8; };
+template <> struct Vec<__bf16> { typedef bf16x8 type; static constexpr int n = 8; };
 template <> struct Vec<float> { typedef float4 type; static constexpr int n = 4; };
 
 // f(v) for every element of x[0, n): a scalar head up to the first 16-byte boundary, 16-byte vector loads, a scalar tail
@@ -54,10 +56,12 @@ __device__ __forceinline__ double wave_sum(double v) {
 // two adjacent columns of a row as one load
 template <typename TIN> struct Pair;
 template <> struct Pair<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(2))); };
+template <> struct Pair<__bf16> { typedef __bf16 type __attribute__((ext_vector_type(2))); };
 template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
 
 template <typename T_, int N> struct VecA4;     // N elements, aligned to 4 bytes (what a multi-dword global access needs)
 template <int N> struct VecA4<_Float16, N> { typedef _Float16 type __attribute__((ext_vector_type(N), aligned(4))); };
+template <int N> struct VecA4<__bf16, N> { typedef __bf16 type __attribute__((ext_vector_type(N), aligned(4))); };
 template <int N> struct VecA4<float, N> { typedef float type __attribute__((ext_vector_type(N), aligned(4))); };
 template <int N> struct VecA4<int16_t, N> { typedef int16_t type __attribute__((ext_vector_type(N), aligned(4))); };
 

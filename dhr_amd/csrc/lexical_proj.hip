@@ -1,14 +1,14 @@
 // The lexical head of an ENCODING run with the vocabulary projection fused in.  The reference makes the MLM logits [B, T, V] with the last
 // linear layer of the MLM head and reads them back in encode_passage / encode_query (tevatron/DHR/modeling.py:291-300,322-331,
 // tevatron/Aggretriever/modeling.py:274-278); dhr_lexical_head (lexical.hip) starts from that tensor.  Here the op starts from the projector's
-// input: hidden [B, T, H] fp16, weight [V, H] fp16 and bias [V], and the logits
-//   x[b][t][v] = sum_k hidden[b][t][k] * weight[v][k] + bias[v]          (fp32 products and sums, never rounded to fp16)
+// input: hidden [B, T, H] and weight [V, H], both fp16 or both bf16, and bias [V], and the logits
+//   x[b][t][v] = sum_k hidden[b][t][k] * weight[v][k] + bias[v]          (fp32 products and sums, never rounded to 16 bits)
 // exist only as MFMA accumulators.  Masked tokens are compacted away first, so they are never multiplied:
 //   proj_count / proj_scan / proj_fill   the list of unmasked token rows in (passage, token) order, the first row of every passage in it, and
 //                                        the first masked token of every passage
 //   proj_stats_kernel     GEMM pass 1 over (64 token rows) x (a share of the vocabulary, 256 columns at a time), tokens on the lanes of
-//                         v_mfma_f32_32x32x16_f16: a lane keeps the running (max, sum exp) of its token across the tiles and the workgroup
-//                         writes one partial per (token, share)
+//                         v_mfma_f32_32x32x16_f16 (_bf16 for bf16 operands): a lane keeps the running (max, sum exp) of its token across the
+//                         tiles and the workgroup writes one partial per (token, share)
 //   proj_combine_kernel   the partials of a token in share order (fp64) -> (max, sum, w, mask) per row, the statistics lexical_fold_kernel reads
 //   proj_fold_kernel      GEMM pass 2: a workgroup owns (256 vocabulary columns, a group of passages) and walks the group's token rows 64 at a
 //                         time, in order, tokens in the accumulator registers.  The lane halves swap one of their two column tiles, so a lane
@@ -64,8 +64,10 @@ extern "C" int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t m
   dhr::alloc_checkpoint();
   if (!hidden || !weight || !term_weights || !mask || !out_value) return set_error(DHR_ERR_INVALID, "null pointer");
   if (mem_kind != DHR_MEM_DEVICE) return set_error(DHR_ERR_INVALID, "lexical projection head: device memory only");
-  if (!val_ok(value_dtype) || !val_ok(out_value_dtype) || (bias && !val_ok(bias_dtype))) return set_error(DHR_ERR_INVALID, "bad value dtype");
-  if (value_dtype != DHR_VAL_F16) return set_error(DHR_ERR_UNSUPPORTED, "lexical projection head: hidden states and weight must be fp16");
+  if (!val_ok_bf16(value_dtype) || !val_ok(out_value_dtype) || (bias && !val_ok_bf16(bias_dtype))) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (value_dtype == DHR_VAL_F32) return set_error(DHR_ERR_UNSUPPORTED, "lexical projection head: hidden states and weight must be fp16 or bf16");
+  if (bias && bias_dtype == DHR_VAL_BF16 && value_dtype == DHR_VAL_F16)
+    return set_error(DHR_ERR_UNSUPPORTED, "lexical projection head: a bf16 bias needs bf16 hidden states and weight (the fp16 kernels read fp32 or fp16)");
   if (batch < 0 || n_tokens <= 0 || vocab <= 0 || hidden_dim <= 0 || ld_token < hidden_dim ||
       ld_batch < (int64_t)(n_tokens - 1) * ld_token + hidden_dim || ld_weight < hidden_dim || ld_weights < n_tokens || ld_mask < n_tokens ||
       cls_dim < 0 || workspace_bytes < 0 || (int64_t)batch * n_tokens > ((int64_t)1 << 31) - 1)
@@ -94,7 +96,7 @@ extern "C" int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t m
   ProjArgs a{};
   a.hid = (const _Float16*)hidden; a.ld_hb = ld_batch; a.ld_ht = ld_token;
   a.wgt = (const _Float16*)weight; a.ld_w = ld_weight;
-  a.bias = bias; a.bias_f32 = bias_dtype == DHR_VAL_F32;
+  a.bias = bias; a.bias_f32 = bias_dtype == DHR_VAL_F32; a.bias_f16 = bias_dtype == DHR_VAL_F16;
   a.tw = term_weights; a.ld_tw = ld_weights; a.mask = mask; a.ld_mask = ld_mask;
   a.B = batch; a.T = n_tokens; a.H = hidden_dim; a.V = vocab;
   a.vec_h = (uintptr_t)hidden % 16 == 0 && ld_batch % 8 == 0 && ld_token % 8 == 0;
@@ -110,9 +112,12 @@ extern "C" int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t m
   hipLaunchKernelGGL(proj_count_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
   hipLaunchKernelGGL(proj_scan_kernel, dim3(1), dim3(256), 0, s, a);
   hipLaunchKernelGGL(proj_fill_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(proj_stats_kernel, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), dim3(256), 0, s, a);
+  const dim3 g_stats((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), g_fold((unsigned)l.n_ntiles, (unsigned)((batch + a.group - 1) / a.group));
+  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL(proj_stats_kernel<__bf16>, g_stats, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(proj_stats_kernel<_Float16>, g_stats, dim3(256), 0, s, a);
   hipLaunchKernelGGL(proj_combine_kernel, dim3((unsigned)((BT + 255) / 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(proj_fold_kernel<false>, dim3((unsigned)l.n_ntiles, (unsigned)((batch + a.group - 1) / a.group)), dim3(256), 0, s, a);
+  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL((proj_fold_kernel<__bf16, false>), g_fold, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((proj_fold_kernel<_Float16, false>), g_fold, dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(dhr::lexical_record_from_reps(direct ? nullptr : a.reps, vocab, mode, batch, vocab, geo.out_cols, geo.W, geo.n_groups, geo.remove, out_value,
                                         out_value_dtype == DHR_VAL_F32, ld_value, out_index, index_dtype == DHR_IDX_I16, ld_index, cls,

@@ -1,6 +1,7 @@
 // What lexical_proj.hip (encoding) and lexical_proj_train.hip (training) share: the arguments, the compaction of the unmasked token rows, the
 // staged MFMA tile product, the softmax statistics pass with its combine, and the fold.  One definition each, so the training forward is
-// bit-identical to the encoding one.
+// bit-identical to the encoding one.  The kernels that touch hidden / weight are templates on their 16-bit element type E (_Float16 or __bf16):
+// the staging moves bytes, the fragment layouts of v_mfma_f32_32x32x16_f16 and _bf16 are the same, so tiling, walk and reduction order are common.
 #pragma once
 #include "lexical_common.h"
 
@@ -19,12 +20,13 @@ constexpr int GROUP_ROWS = 1024;       // token rows (before masking) a fold wor
 typedef float float16v __attribute__((ext_vector_type(16)));
 
 struct ProjArgs {
-  const _Float16* hid;
+  const _Float16* hid;                 // of the kernel's element type E (read as const E*: a 16-bit type either way), strides in elements
   int64_t ld_hb, ld_ht;
   const _Float16* wgt;
   int64_t ld_w;
-  const void* bias;                    // NULL: none
+  const void* bias;                    // NULL: none; fp32, or E like hid and wgt, or ...
   int bias_f32;
+  int bias_f16;                        // ... fp16 next to bf16 operands (E = __bf16 alone; the fp16 kernels read fp32 or fp16, as they always did)
   const float* tw;
   int64_t ld_tw;
   const float* mask;
@@ -102,26 +104,31 @@ __global__ void __launch_bounds__(64) proj_fill_kernel(ProjArgs a) {
   }
 }
 
-__device__ __forceinline__ uint4 load16h(const _Float16* p, bool vec) {
+template <typename E>
+__device__ __forceinline__ uint4 load16h(const E* p, bool vec) {
   if (vec) return *reinterpret_cast<const uint4*>(p);
-  union { uint4 u; _Float16 t[8]; } r;
+  union { uint4 u; E t[8]; } r;
 #pragma unroll
   for (int e = 0; e < 8; ++e) r.t[e] = p[e];
   return r.u;
 }
 
+template <typename E>
 __device__ __forceinline__ float bias_at(const ProjArgs& a, int v) {
   if (!a.bias) return 0.f;
-  return a.bias_f32 ? ((const float*)a.bias)[v] : (float)((const _Float16*)a.bias)[v];
+  if constexpr (__is_same(E, __bf16))
+    if (a.bias_f16) return (float)((const _Float16*)a.bias)[v];
+  return a.bias_f32 ? ((const float*)a.bias)[v] : (float)((const E*)a.bias)[v];
 }
+
 
 // The product of 64 staged rows `hrow` (thread t stages 16-byte slot t & 7 of rows (t >> 3) + 32 u; LDS rows [0, TM)) and 256 staged rows
 // `wrow` (LDS rows [TM, TM + TN)) over all of H.  The caller clamps rows beyond the problem to a valid one (their results are never used);
 // columns beyond H are zeros.  W_REG: acc[i][j][k] holds w-row wave * 64 + 32 i + (8 (k >> 2) + 4 h + (k & 3)) against h-row 32 j + r;
 // otherwise h-row 32 i + (...) against w-row wave * 64 + 32 j + r (r = lane & 31, h = lane >> 5, k the accumulator register).
-template <bool W_REG>
-__device__ __forceinline__ void tile_product_rows(unsigned char* lds, int H, const _Float16* const (&hrow)[2], int vec_h,
-                                                  const _Float16* const (&wrow)[TN / 32], int vec_w, float16v (&acc)[2][2]) {
+template <typename E, bool W_REG>
+__device__ __forceinline__ void tile_product_rows(unsigned char* lds, int H, const E* const (&hrow)[2], int vec_h, const E* const (&wrow)[TN / 32],
+                                                  int vec_w, float16v (&acc)[2][2]) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -161,18 +168,25 @@ __device__ __forceinline__ void tile_product_rows(unsigned char* lds, int H, con
 #pragma unroll
     for (int s = 0; s < BK / 16; ++s) {
       if (s < k_steps) {                                   // (uniform)
-        half8 hf[2], wf[2];
+        typedef typename Vec<E>::type frag;
+        frag hf[2], wf[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          hf[i] = *reinterpret_cast<const half8*>(lds + (32 * i + r) * PITCH + s * 32 + h * 16);
-          wf[i] = *reinterpret_cast<const half8*>(lds + (TM + wave * 64 + 32 * i + r) * PITCH + s * 32 + h * 16);
+          hf[i] = *reinterpret_cast<const frag*>(lds + (32 * i + r) * PITCH + s * 32 + h * 16);
+          wf[i] = *reinterpret_cast<const frag*>(lds + (TM + wave * 64 + 32 * i + r) * PITCH + s * 32 + h * 16);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = W_REG ? __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i], hf[j], acc[i][j], 0, 0, 0)
-                              : __builtin_amdgcn_mfma_f32_32x32x16_f16(hf[i], wf[j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j) {
+            // the builtin is named here, not behind an overloaded helper: with one, the fp16 fold kernel took another register assignment
+            if constexpr (__is_same(E, __bf16))
+              acc[i][j] = W_REG ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], hf[j], acc[i][j], 0, 0, 0)
+                                : __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf[i], wf[j], acc[i][j], 0, 0, 0);
+            else
+              acc[i][j] = W_REG ? __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i], hf[j], acc[i][j], 0, 0, 0)
+                                : __builtin_amdgcn_mfma_f32_32x32x16_f16(hf[i], wf[j], acc[i][j], 0, 0, 0);
+          }
       }
     }
     __syncthreads();
@@ -182,13 +196,13 @@ __device__ __forceinline__ void tile_product_rows(unsigned char* lds, int H, con
 
 // tile_product_rows of the token rows hrow and the weight rows [n0, n0 + TN): TOK_LANE puts the token on the lane (weight rows in the
 // registers), otherwise the token rows are in the registers and the weight row is on the lane
-template <bool TOK_LANE>
-__device__ __forceinline__ void tile_product(unsigned char* lds, const ProjArgs& a, const _Float16* const (&hrow)[2], int n0, float16v (&acc)[2][2]) {
+template <typename E, bool TOK_LANE>
+__device__ __forceinline__ void tile_product(unsigned char* lds, const ProjArgs& a, const E* const (&hrow)[2], int n0, float16v (&acc)[2][2]) {
   const int rb = threadIdx.x >> 3;
-  const _Float16* wrow[TN / 32];
+  const E* wrow[TN / 32];
 #pragma unroll
-  for (int u = 0; u < TN / 32; ++u) wrow[u] = a.wgt + (int64_t)min(n0 + rb + 32 * u, a.V - 1) * a.ld_w;
-  tile_product_rows<TOK_LANE>(lds, a.H, hrow, a.vec_h, wrow, a.vec_w, acc);
+  for (int u = 0; u < TN / 32; ++u) wrow[u] = (const E*)a.wgt + (int64_t)min(n0 + rb + 32 * u, a.V - 1) * a.ld_w;
+  tile_product_rows<E, TOK_LANE>(lds, a.H, hrow, a.vec_h, wrow, a.vec_w, acc);
 }
 
 // (max, sum exp(x - max)) of two disjoint parts of a row -> of their union; a part without a column is (-inf, 0)
@@ -201,16 +215,18 @@ __device__ __forceinline__ void softmax_merge(float& m, float& s, float m2, floa
 }
 
 // the pointers of the two token rows a thread stages: rows row0 + (t >> 3) + 32 u of the list, clamped to [.., row_end)
-__device__ __forceinline__ void token_rows(const ProjArgs& a, int row0, int row_end, const _Float16* (&hrow)[2]) {
+template <typename E>
+__device__ __forceinline__ void token_rows(const ProjArgs& a, int row0, int row_end, const E* (&hrow)[2]) {
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int id = a.rows[min(row0 + (int)(threadIdx.x >> 3) + 32 * u, row_end - 1)];
     const int b = id / a.T, t = id - b * a.T;
-    hrow[u] = a.hid + (int64_t)b * a.ld_hb + (int64_t)t * a.ld_ht;
+    hrow[u] = (const E*)a.hid + (int64_t)b * a.ld_hb + (int64_t)t * a.ld_ht;
   }
 }
 
 // grid: (tiles of TM rows of the worst-case list, shares of the vocabulary)
+template <typename E>
 __global__ void __launch_bounds__(256) proj_stats_kernel(ProjArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[(TM + TN) * PITCH];
   __shared__ float sh_bias[TN];
@@ -219,15 +235,15 @@ __global__ void __launch_bounds__(256) proj_stats_kernel(ProjArgs a) {
   const int m0 = blockIdx.x * TM;
   if (m0 >= M) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const _Float16* hrow[2];
+  const E* hrow[2];
   token_rows(a, m0, M, hrow);
   const int nt_lo = (int)((int64_t)blockIdx.y * a.n_ntiles / a.n_split), nt_hi = (int)((int64_t)(blockIdx.y + 1) * a.n_ntiles / a.n_split);
   float m_run[2] = {-INFINITY, -INFINITY}, s_run[2] = {0.f, 0.f};
   for (int nt = nt_lo; nt < nt_hi; ++nt) {
     const int n0 = nt * TN;
-    sh_bias[tid] = n0 + tid < a.V ? bias_at(a, n0 + tid) : -INFINITY;      // a column beyond the vocabulary: x = -inf, exp = 0
+    sh_bias[tid] = n0 + tid < a.V ? bias_at<E>(a, n0 + tid) : -INFINITY;      // a column beyond the vocabulary: x = -inf, exp = 0
     float16v acc[2][2];
-    tile_product<true>(tile, a, hrow, n0, acc);
+    tile_product<E, true>(tile, a, hrow, n0, acc);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       float t_max = -INFINITY;
@@ -287,7 +303,7 @@ enum { ROW_LIVE = 1, ROW_FIRST = 2, ROW_LAST = 4, ROW_Z_BEFORE = 8, ROW_Z_AFTER 
 
 // grid: (blocks of TN vocabulary columns, groups of a.group passages).  TRAIN: also the first maximising token of every (passage, column),
 // counted like the mask's columns, and its p (a masked token that wins is named like any other, with p = 0: it is never multiplied)
-template <bool TRAIN>
+template <typename E, bool TRAIN>
 __global__ void __launch_bounds__(256) proj_fold_kernel(ProjArgs a) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) unsigned char tile[(TM + TN) * PITCH];
@@ -299,7 +315,7 @@ __global__ void __launch_bounds__(256) proj_fold_kernel(ProjArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
   const int n0 = blockIdx.x * TN, col = n0 + tid;        // after the swap a lane owns column wave * 64 + lane of the block
   const bool col_on = col < a.V;
-  const float bias = col_on ? bias_at(a, col) : 0.f;
+  const float bias = col_on ? bias_at<E>(a, col) : 0.f;
   const int64_t b_lo = (int64_t)blockIdx.y * a.group, b_hi = min(a.B, b_lo + a.group);
   const int row_lo = a.start[b_lo], row_hi = a.start[b_hi];
   if (col_on)
@@ -338,10 +354,10 @@ __global__ void __launch_bounds__(256) proj_fold_kernel(ProjArgs a) {
       sh_st[tid] = st; sh_flag[tid] = flag; sh_z[tid] = z; sh_b[tid] = bb;
       if (TRAIN) { sh_t[tid] = tt; sh_tm[tid] = tmm; }
     }
-    const _Float16* hrow[2];
+    const E* hrow[2];
     token_rows(a, m0, row_hi, hrow);
     float16v acc[2][2];
-    tile_product<false>(tile, a, hrow, n0, acc);          // (its first barrier publishes the row table)
+    tile_product<E, false>(tile, a, hrow, n0, acc);         // (its first barrier publishes the row table)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll

@@ -14,9 +14,11 @@
 //   proj_grad_kernel<2>     pass 2, dhidden: a workgroup owns 64 token rows and walks the vocabulary 256 columns at a time (a share of it when
 //                           there are few token rows; proj_grad_combine_kernel then adds the shares in order).
 //   proj_grad_kernel<3>     pass 3, dW and dbias: a workgroup owns 64 vocabulary columns and walks all token rows of the list, 256 at a time.
-// Both GEMM passes are one kernel with the roles of the two operands exchanged.  Per walked tile: (1) x on v_mfma_f32_32x32x16_f16 with the
+// Both GEMM passes are one kernel with the roles of the two operands exchanged.  Every kernel that reads hidden / weight is a
+// template on their element type E (_Float16 or __bf16), with the staging, the tiling and every order of summation in common.
+// Per walked tile: (1) x on v_mfma_f32_32x32x16_f16 (_bf16 where E is __bf16) with the
 // owned ("resident") row on the lane and the walked rows in the accumulator registers -- the token on the lane in pass 2, the vocabulary
-// column on the lane in pass 3; (2) dx in fp32 in those registers, rounded to fp16 once and passed through LDS once, as [resident][walked];
+// column on the lane in pass 3; (2) dx in fp32 in those registers, rounded to E once and passed through LDS once, as [resident][walked];
 // (3) a second MFMA chain out[resident][H] += dx . (walked operand), for which the walked operand's LDS image is staged again chunk by chunk
 // and read by columns; the four waves split each 64 x 64 block of the output, whose accumulators stay in registers for the whole walk
 // (16 per 64 columns of H: 192 at H = 768; a wider H is cut into two slabs, each of which computes x again).  One workgroup owns its rows of the output: no atomics, no float atomics
@@ -29,7 +31,7 @@ namespace {
 
 constexpr int RT_BIG = 16;             // tokens per workgroup of the route sums ...
 constexpr int RT_SMALL = 4;            // ... and where 16 would leave most of the chip without a workgroup
-constexpr int DXP = 2 * TN + 16;       // LDS pitch of a row of the dx image [resident 64][walked 256] fp16
+constexpr int DXP = 2 * TN + 16;       // LDS pitch of a row of the dx image [resident 64][walked 256] of E
 constexpr int MAX_TOKENS = 32767;      // tok is int16
 constexpr int MAX_H = 1024;
 constexpr int MAX_CHUNKS = 12;         // 64-column chunks of H whose output accumulators fit the registers: 16 registers per chunk
@@ -42,10 +44,10 @@ struct GradArgs {
   int64_t ld_tok;
   const float* D;                      // [B * T] w * m * A
   void* out;                           // pass 2: dhidden at the first unskipped token; pass 3: dW (NULL: dbias only)
-  int out_f32;
+  int out_f32, out_f16;                // the dtype of out: fp32, fp16 next to bf16 operands (E = __bf16 alone), else E
   int64_t ld_ob, ld_ot;                // pass 2: batch / token strides; pass 3: ld_ob is the row stride
   void* dbias;                         // pass 3, NULL: not wanted
-  int dbias_f32;
+  int dbias_f32, dbias_f16;
   float* partial;                      // pass 2 with shares: [n_split][B * T][H] fp32
   int n_split;
   int c_lo, c_n;                       // the slab of H this launch owns: 64-column chunks [c_lo, c_lo + c_n)
@@ -106,7 +108,7 @@ __global__ void __launch_bounds__(256) proj_zero_rows_kernel(ProjArgs a, void* o
   const int64_t at = b * ld_ob + (int64_t)l * ld_ot;
   for (int k = threadIdx.x; k < a.H; k += 256) {
     if (out_f32) ((float*)out)[at + k] = 0.f;
-    else ((_Float16*)out)[at + k] = (_Float16)0.f;
+    else ((unsigned short*)out)[at + k] = 0;             // +0 of fp16 and of bf16
   }
 }
 
@@ -121,15 +123,28 @@ __device__ __forceinline__ short4t lds_read_tr16(const unsigned char* p) {
 #endif
 }
 
-__device__ __forceinline__ void store_out(void* out, int f32, int64_t at, float v) {
-  if (f32) ((float*)out)[at] = v;
-  else ((_Float16*)out)[at] = (_Float16)v;
+// a gradient, rounded once (to nearest even): fp32, or of the operands' type E, or (f16: E = __bf16 alone) fp16 next to bf16 operands.  The
+// fp16 kernels keep the two-way store they always had; the bf16 kernels convert both ways and select, which keeps the stores two-way as well
+// (a branch per store on a third case costs the widest gradient kernel its registers: it spills).
+template <typename E>
+__device__ __forceinline__ void store_out(void* out, int f32, int f16, int64_t at, float v) {
+  if (f32) {
+    ((float*)out)[at] = v;
+  } else if constexpr (__is_same(E, __bf16)) {
+    union { _Float16 f; unsigned short u; } h;
+    union { __bf16 f; unsigned short u; } b;
+    h.f = (_Float16)v;
+    b.f = (__bf16)v;
+    ((unsigned short*)out)[at] = f16 ? h.u : b.u;
+  } else {
+    ((E*)out)[at] = (E)v;
+  }
 }
 
 // PASS 2: resident = 64 rows of the token list (grid x), walked = a share (grid y) of the vocabulary; out = dhidden.
 // PASS 3: resident = 64 vocabulary columns (grid x), walked = the token list; out = dW, and dbias.
 // NC: 64-column chunks of H the output registers hold (>= q.c_n, the chunks of the launch's slab of H).
-template <int PASS, int NC>
+template <typename E, int PASS, int NC>
 __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __shared__ __attribute__((aligned(16))) unsigned char tile[(TM + TN) * PITCH];
@@ -170,17 +185,18 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
       sh_off[tid] = (int64_t)b * a.ld_hb + (int64_t)t * a.ld_ht;
     }
   };
-  const _Float16* hrow[2];
+  const E* hrow[2];
   float bias_res[2] = {0.f, 0.f};
   if (PASS == 2) {
     token_rows(a, res0, M, hrow);
     if (tid < TM) token_slot(res0 + tid);
   } else {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) hrow[u] = a.wgt + (int64_t)min(res0 + rbs + 32 * u, a.V - 1) * a.ld_w;
+    for (int u = 0; u < 2; ++u) hrow[u] = (const E*)a.wgt + (int64_t)min(res0 + rbs + 32 * u, a.V - 1) * a.ld_w;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) bias_res[j] = res0 + 32 * j + r < a.V ? bias_at(a, res0 + 32 * j + r) : 0.f;
+    for (int j = 0; j < 2; ++j) bias_res[j] = res0 + 32 * j + r < a.V ? bias_at<E>(a, res0 + 32 * j + r) : 0.f;
   }
+  typedef typename Vec<E>::type frag;
   const int vec_res = PASS == 2 ? a.vec_h : a.vec_w, vec_walk = PASS == 2 ? a.vec_w : a.vec_h;
   const int rb2 = wave & 1, kb = wave >> 1;              // the wave's 32 x 32 block of a 64 x 64 block of the output
   float16v out[NC];
@@ -192,22 +208,22 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
   for (int t_i = tile_lo; t_i < tile_hi; ++t_i) {
     const int w0 = t_i * TN;
     // walked row rbs + 32 u of the tile, clamped to a valid one (its dx is zero)
-    auto walk_row = [&](int u) -> const _Float16* {
-      if (PASS == 2) return a.wgt + (int64_t)min(w0 + rbs + 32 * u, a.V - 1) * a.ld_w;
-      return a.hid + sh_off[rbs + 32 * u];
+    auto walk_row = [&](int u) -> const E* {
+      if (PASS == 2) return (const E*)a.wgt + (int64_t)min(w0 + rbs + 32 * u, a.V - 1) * a.ld_w;
+      return (const E*)a.hid + sh_off[rbs + 32 * u];
     };
     if (PASS == 2) {
-      sh_bias[tid] = w0 + tid < a.V ? bias_at(a, w0 + tid) : 0.f;
+      sh_bias[tid] = w0 + tid < a.V ? bias_at<E>(a, w0 + tid) : 0.f;
     } else {
       token_slot(w0 + tid);
       __syncthreads();                                     // the rows' addresses are read below
     }
     float16v acc[2][2];
     {
-      const _Float16* wrow[TN / 32];
+      const E* wrow[TN / 32];
 #pragma unroll
       for (int u = 0; u < TN / 32; ++u) wrow[u] = walk_row(u);
-      tile_product_rows<true>(tile, a.H, hrow, vec_res, wrow, vec_walk, acc);   // (its first barrier publishes the tables, it ends with one)
+      tile_product_rows<E, true>(tile, a.H, hrow, vec_res, wrow, vec_walk, acc);   // (its first barrier publishes the tables, it ends with one)
     }
     // dx of walked row wave * 64 + 32 i + 8 qd + 4 h + e against resident row 32 j + r, four adjacent walked rows as one 8-byte store
 #pragma unroll
@@ -218,7 +234,7 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int rslot = 32 * j + r;
-          union { uint2 u; _Float16 t[4]; } d4;
+          union { uint2 u; E t[4]; } d4;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int tslot = PASS == 2 ? rslot : ws0 + e;
@@ -234,7 +250,7 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
               dx = p * (routed - st.w);
             }
             if (PASS == 3) db[j] += dx;
-            d4.t[e] = (_Float16)dx;
+            d4.t[e] = (E)dx;                               // the one rounding of dx, to nearest even
           }
           *reinterpret_cast<uint2*>(dxs + rslot * DXP + 2 * ws0) = d4.u;
         }
@@ -263,14 +279,15 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
         if (c + 1 < q.c_n) fetch(c + 1);
 #pragma unroll 4
         for (int s = 0; s < TN / 16; ++s) {
-          const half8 df = *reinterpret_cast<const half8*>(dxs + (32 * rb2 + r) * DXP + 2 * (16 * s + 8 * h));
+          const frag df = *reinterpret_cast<const frag*>(dxs + (32 * rb2 + r) * DXP + 2 * (16 * s + 8 * h));
           // the staged image read by columns, walked rows 16 s + 8 h + (0 .. 7) of column 32 kb + r: two transposed reads of 4 rows x 16
           // columns per 16 lanes (lane 4 q + p of the group gives the address of row q, columns 4 p .. 4 p + 3, and receives its own column)
           const unsigned char* tr = tile + (TM + 16 * s + 8 * h + ((lane >> 2) & 3)) * PITCH + 2 * (32 * kb + (lane & 16) + 4 * (lane & 3));
-          union { struct { short4t lo, hi; } p; half8 v; } wf;
+          union { struct { short4t lo, hi; } p; frag v; } wf;
           wf.p.lo = lds_read_tr16(tr);
           wf.p.hi = lds_read_tr16(tr + 4 * PITCH);
-          out[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(df, wf.v, out[c], 0, 0, 0);
+          if constexpr (__is_same(E, __bf16)) out[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, wf.v, out[c], 0, 0, 0);
+          else out[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(df, wf.v, out[c], 0, 0, 0);
         }
         __syncthreads();
       }
@@ -289,9 +306,9 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
             const int2 bt = sh_bt[rs];
             if (bt.y < 0) continue;
             if (q.n_split > 1) q.partial[((int64_t)blockIdx.y * (a.B * a.T) + res0 + rs) * a.H + col] = out[c][k];
-            else store_out(q.out, q.out_f32, (int64_t)bt.x * q.ld_ob + (int64_t)bt.y * q.ld_ot + col, out[c][k]);
+            else store_out<E>(q.out, q.out_f32, q.out_f16, (int64_t)bt.x * q.ld_ob + (int64_t)bt.y * q.ld_ot + col, out[c][k]);
           } else if (res0 + rs < a.V) {
-            store_out(q.out, q.out_f32, (int64_t)(res0 + rs) * q.ld_ob + col, out[c][k]);
+            store_out<E>(q.out, q.out_f32, q.out_f16, (int64_t)(res0 + rs) * q.ld_ob + col, out[c][k]);
           }
         }
       }
@@ -304,13 +321,14 @@ __global__ void __launch_bounds__(256) proj_grad_kernel(ProjArgs a, GradArgs q) 
     if (tid < TM && res0 + tid < a.V) {
       float s = sh_red[0][tid];
       for (int k = 1; k < 8; ++k) s += sh_red[k][tid];
-      store_out(q.dbias, q.dbias_f32, res0 + tid, s);
+      store_out<E>(q.dbias, q.dbias_f32, q.dbias_f16, res0 + tid, s);
     }
   }
 #endif
 }
 
 // the shares of pass 2 in share order (fp64, rounded once) -> dhidden.  grid: (rows of the worst-case list, blocks of 256 columns of H)
+template <typename E>
 __global__ void __launch_bounds__(256) proj_grad_combine_kernel(ProjArgs a, GradArgs q) {
   const int row = blockIdx.x, col = blockIdx.y * 256 + threadIdx.x;
   if (row >= a.hdr[0] || col >= a.H) return;
@@ -318,7 +336,7 @@ __global__ void __launch_bounds__(256) proj_grad_combine_kernel(ProjArgs a, Grad
   const int b = id / a.T, t = id - b * a.T;
   double s = 0.0;
   for (int k = 0; k < q.n_split; ++k) s += (double)q.partial[((int64_t)k * (a.B * a.T) + row) * a.H + col];
-  store_out(q.out, q.out_f32, (int64_t)b * q.ld_ob + (int64_t)t * q.ld_ot + col, (float)s);
+  store_out<E>(q.out, q.out_f32, q.out_f16, (int64_t)b * q.ld_ob + (int64_t)t * q.ld_ot + col, (float)s);
 }
 
 struct Layout {
@@ -354,7 +372,7 @@ int check_common(const char* what, int32_t mem_kind, const void* hidden, int32_t
                  int32_t bias_dtype, const float* term_weights, int64_t ld_weights, const float* mask, int64_t ld_mask, int64_t workspace_bytes) {
   if (!hidden || !weight || !term_weights || !mask) return set_error(DHR_ERR_INVALID, "null pointer");
   if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
-  if (!val_ok(value_dtype) || (bias && !val_ok(bias_dtype))) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (!val_ok_bf16(value_dtype) || (bias && !val_ok_bf16(bias_dtype))) return set_error(DHR_ERR_INVALID, "bad value dtype");
   if (batch < 0 || n_tokens <= 0 || vocab <= 0 || hidden_dim <= 0 || skip_tokens < 0 || skip_tokens > MAX_TOKENS || ld_token < hidden_dim ||
       ld_batch < (int64_t)(n_tokens + skip_tokens - 1) * ld_token + hidden_dim || ld_weight < hidden_dim || ld_weights < n_tokens ||
       ld_mask < n_tokens || workspace_bytes < 0 || batch * ((int64_t)n_tokens + skip_tokens) > ((int64_t)1 << 31) - 1)
@@ -362,7 +380,9 @@ int check_common(const char* what, int32_t mem_kind, const void* hidden, int32_t
   if (hidden_dim % 8) return set_error(DHR_ERR_INVALID, "the hidden size must be a multiple of 8");
   if (n_tokens > MAX_TOKENS) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 tokens (the token index is int16)");
   if (hidden_dim > MAX_H) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden sizes above 1024 are not built");
-  if (value_dtype != DHR_VAL_F16) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden states and weight must be fp16");
+  if (value_dtype == DHR_VAL_F32) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden states and weight must be fp16 or bf16");
+  if (bias && bias_dtype == DHR_VAL_BF16 && value_dtype == DHR_VAL_F16)
+    return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": a bf16 bias needs bf16 hidden states and weight (the fp16 kernels read fp32 or fp16)");
   if (mem_kind != DHR_MEM_DEVICE)
     return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": host arrays are not staged, training tensors live on the device (DHR_MEM_DEVICE)");
   return DHR_OK;
@@ -382,7 +402,7 @@ ProjArgs proj_args(const Layout& l, const void* hidden, int64_t batch, int32_t n
   ProjArgs a{};
   a.hid = (const _Float16*)hidden + (int64_t)skip_tokens * ld_token; a.ld_hb = ld_batch; a.ld_ht = ld_token;
   a.wgt = (const _Float16*)weight; a.ld_w = ld_weight;
-  a.bias = bias; a.bias_f32 = bias_dtype == DHR_VAL_F32;
+  a.bias = bias; a.bias_f32 = bias_dtype == DHR_VAL_F32; a.bias_f16 = bias_dtype == DHR_VAL_F16;
   a.tw = term_weights; a.ld_tw = ld_weights; a.mask = mask; a.ld_mask = ld_mask;
   a.B = batch; a.T = n_tokens; a.H = hidden_dim; a.V = vocab;
   a.vec_h = (uintptr_t)a.hid % 16 == 0 && ld_batch % 8 == 0 && ld_token % 8 == 0;
@@ -396,15 +416,15 @@ ProjArgs proj_args(const Layout& l, const void* hidden, int64_t batch, int32_t n
 
 // One launch per slab of H: up to MAX_CHUNKS 64-column chunks fit the registers; a wider H (above 768) is cut into equal slabs, each of
 // which computes x again.  dbias belongs to the first slab; where it is all that is wanted (no out), the later slabs have nothing to write.
-template <int PASS>
+template <typename E, int PASS>
 void launch_grad(int hidden_dim, dim3 grid, hipStream_t s, const ProjArgs& a, GradArgs q) {
   const int n_chunks = (hidden_dim + BK - 1) / BK;
   const int n_slabs = (n_chunks + MAX_CHUNKS - 1) / MAX_CHUNKS, per = (n_chunks + n_slabs - 1) / n_slabs;
   for (int c = 0; c < n_chunks; c += per) {
     q.c_lo = c; q.c_n = std::min(per, n_chunks - c);
-    if (per <= 2) hipLaunchKernelGGL((proj_grad_kernel<PASS, 2>), grid, dim3(256), 0, s, a, q);
-    else if (per <= 6) hipLaunchKernelGGL((proj_grad_kernel<PASS, 6>), grid, dim3(256), 0, s, a, q);
-    else hipLaunchKernelGGL((proj_grad_kernel<PASS, MAX_CHUNKS>), grid, dim3(256), 0, s, a, q);
+    if (per <= 2) hipLaunchKernelGGL((proj_grad_kernel<E, PASS, 2>), grid, dim3(256), 0, s, a, q);
+    else if (per <= 6) hipLaunchKernelGGL((proj_grad_kernel<E, PASS, 6>), grid, dim3(256), 0, s, a, q);
+    else hipLaunchKernelGGL((proj_grad_kernel<E, PASS, MAX_CHUNKS>), grid, dim3(256), 0, s, a, q);
     if (!q.out) break;
     q.dbias = nullptr;
   }
@@ -445,9 +465,12 @@ extern "C" int dhr_lexical_proj_train(int32_t device, int32_t mem_kind, const vo
   hipLaunchKernelGGL(proj_count_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
   hipLaunchKernelGGL(proj_scan_kernel, dim3(1), dim3(256), 0, s, a);
   hipLaunchKernelGGL(proj_fill_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(proj_stats_kernel, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), dim3(256), 0, s, a);
+  const dim3 g_stats((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), g_fold((unsigned)l.n_ntiles, (unsigned)((batch + a.group - 1) / a.group));
+  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL(proj_stats_kernel<__bf16>, g_stats, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(proj_stats_kernel<_Float16>, g_stats, dim3(256), 0, s, a);
   hipLaunchKernelGGL(proj_combine_kernel, dim3((unsigned)((BT + 255) / 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(proj_fold_kernel<true>, dim3((unsigned)l.n_ntiles, (unsigned)((batch + a.group - 1) / a.group)), dim3(256), 0, s, a);
+  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL((proj_fold_kernel<__bf16, true>), g_fold, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((proj_fold_kernel<_Float16, true>), g_fold, dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -465,8 +488,12 @@ extern "C" int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const
   int rc = check_common("dhr_lexical_proj_backward", mem_kind, hidden, value_dtype, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token,
                         weight, vocab, ld_weight, bias, bias_dtype, term_weights, ld_weights, mask, ld_mask, workspace_bytes);
   if (rc) return rc;
-  if ((grad_hidden && !val_ok(grad_hidden_dtype)) || (grad_weight && !val_ok(grad_weight_dtype)) || (grad_bias && !val_ok(grad_bias_dtype)))
+  if ((grad_hidden && !val_ok_bf16(grad_hidden_dtype)) || (grad_weight && !val_ok_bf16(grad_weight_dtype)) ||
+      (grad_bias && !val_ok_bf16(grad_bias_dtype)))
     return set_error(DHR_ERR_INVALID, "bad value dtype");
+  auto bf16_of_fp16 = [&](const void* p, int32_t dt) { return p && dt == DHR_VAL_BF16 && value_dtype == DHR_VAL_F16; };
+  if (bf16_of_fp16(grad_hidden, grad_hidden_dtype) || bf16_of_fp16(grad_weight, grad_weight_dtype) || bf16_of_fp16(grad_bias, grad_bias_dtype))
+    return set_error(DHR_ERR_UNSUPPORTED, "dhr_lexical_proj_backward: a bf16 gradient needs bf16 hidden states and weight (the fp16 kernels write fp32 or fp16)");
   if (ld_grad_reps < vocab || ld_tokens < vocab || ld_pwin < vocab || (grad_term_weights && ld_grad_term_weights < n_tokens) ||
       (grad_weight && ld_grad_weight < hidden_dim) ||
       (grad_hidden && (ld_grad_token < hidden_dim || ld_grad_batch < (int64_t)(n_tokens + skip_tokens - 1) * ld_grad_token + hidden_dim)))
@@ -504,18 +531,23 @@ extern "C" int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const
     hipLaunchKernelGGL(proj_zero_rows_kernel, dim3((unsigned)(batch * (skip_tokens + T))), dim3(256), 0, s, a, grad_hidden,
                        (int)(grad_hidden_dtype == DHR_VAL_F32), ld_grad_batch, ld_grad_token, (int)skip_tokens);
     q.out = (char*)grad_hidden + (int64_t)skip_tokens * ld_grad_token * es;
-    q.out_f32 = grad_hidden_dtype == DHR_VAL_F32; q.ld_ob = ld_grad_batch; q.ld_ot = ld_grad_token;
+    q.out_f32 = grad_hidden_dtype == DHR_VAL_F32; q.out_f16 = grad_hidden_dtype == DHR_VAL_F16; q.ld_ob = ld_grad_batch; q.ld_ot = ld_grad_token;
     q.partial = (float*)((char*)workspace + l.partial); q.n_split = l.grad_split;
-    launch_grad<2>(hidden_dim, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)l.grad_split), s, a, q);
-    if (l.grad_split > 1)
-      hipLaunchKernelGGL(proj_grad_combine_kernel, dim3((unsigned)BT, (unsigned)((hidden_dim + 255) / 256)), dim3(256), 0, s, a, q);
+    if (value_dtype == DHR_VAL_BF16) launch_grad<__bf16, 2>(hidden_dim, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)l.grad_split), s, a, q);
+    else launch_grad<_Float16, 2>(hidden_dim, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)l.grad_split), s, a, q);
+    if (l.grad_split > 1) {
+      const dim3 g_comb((unsigned)BT, (unsigned)((hidden_dim + 255) / 256));
+      if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL(proj_grad_combine_kernel<__bf16>, g_comb, dim3(256), 0, s, a, q);
+      else hipLaunchKernelGGL(proj_grad_combine_kernel<_Float16>, g_comb, dim3(256), 0, s, a, q);
+    }
     HIP_TRY(hipGetLastError());
   }
   if (grad_weight || grad_bias) {                          // pass 3
-    q.out = grad_weight; q.out_f32 = grad_weight_dtype == DHR_VAL_F32; q.ld_ob = ld_grad_weight; q.ld_ot = 0;
-    q.dbias = grad_bias; q.dbias_f32 = grad_bias_dtype == DHR_VAL_F32;
+    q.out = grad_weight; q.out_f32 = grad_weight_dtype == DHR_VAL_F32; q.out_f16 = grad_weight_dtype == DHR_VAL_F16; q.ld_ob = ld_grad_weight; q.ld_ot = 0;
+    q.dbias = grad_bias; q.dbias_f32 = grad_bias_dtype == DHR_VAL_F32; q.dbias_f16 = grad_bias_dtype == DHR_VAL_F16;
     q.partial = nullptr; q.n_split = 1;
-    launch_grad<3>(hidden_dim, dim3((unsigned)((vocab + TM - 1) / TM)), s, a, q);
+    if (value_dtype == DHR_VAL_BF16) launch_grad<__bf16, 3>(hidden_dim, dim3((unsigned)((vocab + TM - 1) / TM)), s, a, q);
+    else launch_grad<_Float16, 3>(hidden_dim, dim3((unsigned)((vocab + TM - 1) / TM)), s, a, q);
     HIP_TRY(hipGetLastError());
   }
   return DHR_OK;

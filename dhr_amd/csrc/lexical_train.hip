@@ -15,7 +15,7 @@
 //                             Accumulation is fp64, rounded to fp32 once; there are no atomics, so two runs are bit-identical.
 //   lexical_dx_kernel         the streaming pass: a workgroup owns (b, 8 tokens, 2048 columns); a thread keeps g and tok of 8 adjacent columns
 //                             in registers and walks the tokens: one 16-byte load of the logits (two for fp32), one store of the gradient in the
-//                             logits' dtype.  p is recomputed from the saved (max, sum).  Rows of skipped and masked tokens are written as
+//                             logits' dtype (fp16 / bf16: rounded once from fp32, to nearest even).  p is recomputed from the saved (max, sum).  Rows of skipped and masked tokens are written as
 //                             zeros without being read.  Rows that are not 4-byte aligned (fp16 with an odd stride) take element-wise accesses.
 // Both passes take the model's full [B, L, V] logits and skip_tokens (the reference drops token 0): the gradient of the whole tensor is
 // written, so autograd never pads the gradient of a [:, 1:] view.  Everything is enqueued on the caller's stream; nothing is allocated.
@@ -184,7 +184,7 @@ int check_head(const void* logits, int32_t mem_kind, int32_t value_dtype, int64_
                int64_t ld_batch, int64_t ld_token, const void* workspace, const char* what) {
   if (!logits || !workspace) return set_error(DHR_ERR_INVALID, "null pointer");
   if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
-  if (!val_ok(value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (!val_ok_bf16(value_dtype)) return set_error(DHR_ERR_INVALID, "bad value dtype");
   if (batch < 0 || n_tokens <= 0 || vocab <= 0 || skip_tokens < 0 || skip_tokens > MAX_TOKENS || ld_token < vocab ||
       ld_batch < (int64_t)(n_tokens + skip_tokens - 1) * ld_token + vocab || batch * n_tokens > ((int64_t)1 << 31) - 1)
     return set_error(DHR_ERR_INVALID, "bad sizes / strides");
@@ -225,7 +225,7 @@ extern "C" int dhr_lexical_head_train(int32_t device, int32_t mem_kind, const vo
     hipLaunchKernelGGL(lexical_fold_tok_kernel<T_>, g_fold, dim3(256), 0, s, x, ld_batch, ld_token, T, vocab, batch, (const float4*)stats,        \
                        out_reps, ld_reps, out_tokens, ld_tokens);                                                                                \
   } while (0)
-  if (value_dtype == DHR_VAL_F32) LEX_TRAIN_FWD(float); else LEX_TRAIN_FWD(_Float16);
+  if (value_dtype == DHR_VAL_F32) LEX_TRAIN_FWD(float); else if (value_dtype == DHR_VAL_BF16) LEX_TRAIN_FWD(__bf16); else LEX_TRAIN_FWD(_Float16);
 #undef LEX_TRAIN_FWD
   HIP_TRY(hipGetLastError());
   return DHR_OK;
@@ -285,7 +285,7 @@ extern "C" int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const
       HIP_TRY(hipGetLastError());                                                                                                                \
     }                                                                                                                                            \
   } while (0)
-    if (value_dtype == DHR_VAL_F32) LEX_TRAIN_BWD(float); else LEX_TRAIN_BWD(_Float16);
+    if (value_dtype == DHR_VAL_F32) LEX_TRAIN_BWD(float); else if (value_dtype == DHR_VAL_BF16) LEX_TRAIN_BWD(__bf16); else LEX_TRAIN_BWD(_Float16);
 #undef LEX_TRAIN_BWD
   }
   return DHR_OK;

@@ -13,11 +13,12 @@ and the encoder driver then densifies (DHR) or aggregates (Aggretriever) the rep
     densify_lexical_into(..., value_out, index_out, dims, remove_dims, semantic_reps)   DHR / DLR records
     aggregate_lexical_into(..., value_out, agg_dim, full, semantic_reps)                Aggretriever records
 
-Arguments: `logits` [B, T, V] fp16 or fp32 (pass `psg_out.logits[:, 1:]`: any batch / token strides, the last dimension contiguous, the view
-is read in place), `term_weights` [B, T] or [B, T, 1] fp16 / fp32, `attention_mask` [B, T] or [B, T, 1] of any integer or bool dtype (the
-reference's `psg['attention_mask'][:, 1:]`).  Each contribution is (p * w) * mask in fp32, so a masked token folds in a zero with the sign of
-its weight, and ties keep the first token and the first group, like torch.max on the device.  Finite logits and -inf are in scope; NaN and
-+inf are not, and every unmasked token needs one finite logit.
+Arguments: `logits` [B, T, V] fp16, bf16 (torch tensors on a GPU; numpy has no bf16) or fp32 (pass `psg_out.logits[:, 1:]`: any batch /
+token strides, the last dimension contiguous, the view is read in place), `term_weights` [B, T] or [B, T, 1] fp16 / fp32, `attention_mask`
+[B, T] or [B, T, 1] of any integer or bool dtype (the reference's `psg['attention_mask'][:, 1:]`).  16-bit logits widen to fp32 exactly, so
+the same values in fp16 and in bf16 give the same bits.  Each contribution is (p * w) * mask in fp32, so a masked token folds in a zero with
+the sign of its weight, and ties keep the first token and the first group, like torch.max on the device.  Finite logits and -inf are in
+scope; NaN and +inf are not, and every unmasked token needs one finite logit.
 
 Torch CUDA tensors are processed on their device and on torch's current stream; the calls wait for that stream, so the outputs are complete
 on return.  numpy arrays are staged through device 0.  There is no CPU implementation: without the HIP library / a GPU the calls raise."""
@@ -69,8 +70,10 @@ def _inputs(logits, term_weights, attention_mask):
     B, T, V = (int(d) for d in logits.shape)
     if T == 0:
         raise ValueError('no tokens: the maximum over tokens of an empty sequence is undefined')
-    if M.dtype_name(logits) not in M.FLOATS:
-        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
+    if M.dtype_name(logits) not in M.FLOATS + ("bfloat16",):
+        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / bfloat16 / float32)")
+    if M.dtype_name(logits) == "bfloat16" and (M.is_np(logits) or not logits.is_cuda):
+        raise _lib.DhrError("lexical head: bfloat16 logits must live on a GPU (the staged host path serves numpy arrays, which have no bfloat16)")
     if M.is_np(logits):
         w = np.ascontiguousarray(np.asarray(term_weights).reshape(B, T), dtype=np.float32)
         m = np.ascontiguousarray(np.asarray(attention_mask).reshape(B, T), dtype=np.float32)
@@ -84,8 +87,8 @@ def _inputs(logits, term_weights, attention_mask):
 
 
 def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps):
+    lg, ldb, ldt, w, m, B, T, V = _inputs(logits, term_weights, attention_mask)     # (its dtype checks come before the library is touched)
     lib = _lib.load()
-    lg, ldb, ldt, w, m, B, T, V = _inputs(logits, term_weights, attention_mask)
     kind = M.mem_kind(lg)
     p_v, ld_v, kind_v = _lib._ptr_ld(value_out)
     if kind_v != kind:
@@ -107,7 +110,7 @@ def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims,
         c_dt, c_dim, keep = _lib._val_code(c), int(c.shape[1]), c
     if B:
         ws = M.empty(lg, B * T * 16, "uint8") if kind == _lib.MEM_DEVICE else None
-        _lib.check(lib.dhr_lexical_head(M.device(lg), kind, mode, M.data_ptr(lg), _lib._val_code(lg), B, T, V, ldb, ldt, M.data_ptr(w), T,
+        _lib.check(lib.dhr_lexical_head(M.device(lg), kind, mode, M.data_ptr(lg), _lib._val_code(lg, bf16=True), B, T, V, ldb, ldt, M.data_ptr(w), T,
                                         M.data_ptr(m), T, dims, remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt,
                                         ld_c, c_dim, M.data_ptr(ws), M.stream(lg)), "dhr_lexical_head")
     del keep

@@ -8,11 +8,12 @@ are never multiplied:
     densify_lexical_into(..., value_out, index_out, dims, remove_dims, semantic_reps)          DHR / DLR records
     aggregate_lexical_into(..., value_out, agg_dim, full, semantic_reps)                       Aggretriever records
 
-Arguments: `hidden` [B, T, H] fp16, the input of the vocabulary projector (DistilBERT: the output of `vocab_layer_norm`; BERT: of
+Arguments: `hidden` [B, T, H] fp16 or bf16, the input of the vocabulary projector (DistilBERT: the output of `vocab_layer_norm`; BERT: of
 `cls.predictions.transform`); pass the `[:, 1:]` view: any batch / token strides, the last dimension contiguous, H a multiple of 8, read in
-place.  `weight` [V, H] fp16 (any row stride), `bias` [V] fp16 / fp32 or None.  `term_weights`, `attention_mask`, the outputs and what is
-written into them are those of `dhr_amd.lexical`; the logits are x = hidden @ weight.T + bias with fp32 products and sums and are not rounded
-to fp16.
+place.  `weight` [V, H] of the same dtype as `hidden` (any row stride), `bias` [V] fp16 / bf16 / fp32 or None (a bf16 bias next to
+fp16 operands is widened to fp32 first, exactly).  `term_weights`, `attention_mask`, the outputs and what is written into them are those of
+`dhr_amd.lexical`; the logits are x = hidden @ weight.T + bias with fp32 products and sums (of the bf16 values where the operands are bf16:
+their range is kept) and are not rounded to 16 bits.
 
 Torch CUDA tensors only: the op runs on their device, enqueues on the current stream and does not wait.  CPU tensors and numpy arrays raise
 DhrError: there is no staged host path and no CPU implementation."""
@@ -40,8 +41,8 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
     V = int(weight.shape[0])
     if T == 0:
         raise ValueError('no tokens: the maximum over tokens of an empty sequence is undefined')
-    if hidden.dtype != torch.float16 or weight.dtype != torch.float16:
-        raise _lib.DhrError(f"unsupported hidden / weight dtype {hidden.dtype} / {weight.dtype} (float16)")
+    if hidden.dtype not in (torch.float16, torch.bfloat16) or weight.dtype != hidden.dtype:
+        raise _lib.DhrError(f"unsupported hidden / weight dtype {hidden.dtype} / {weight.dtype} (both float16 or both bfloat16)")
     if H % 8:
         raise _lib.DhrError(f"lexical projection head: the hidden size {H} is not a multiple of 8")
     lib = _lib.load()
@@ -53,12 +54,14 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
     p_b, b_dt = None, _lib.VAL_F32
     if bias is not None:
         _on_gpu("bias", bias)
-        if bias.dtype not in (torch.float16, torch.float32):
-            raise _lib.DhrError(f"unsupported bias dtype {bias.dtype} (float16 / float32)")
+        if bias.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise _lib.DhrError(f"unsupported bias dtype {bias.dtype} (float16 / bfloat16 / float32)")
         if bias.dim() != 1 or int(bias.shape[0]) != V:
             raise ValueError("bias does not match the vocabulary")
         bias = bias.detach().to(dev).contiguous()
-        p_b, b_dt = bias.data_ptr(), _lib._val_code(bias)
+        if bias.dtype == torch.bfloat16 and hidden.dtype == torch.float16:       # the fp16 kernels read fp32 or fp16: [V] values, widened exactly
+            bias = bias.float()
+        p_b, b_dt = bias.data_ptr(), _lib._val_code(bias, bf16=True)
     w = term_weights.detach().reshape(B, T).to(device=dev, dtype=torch.float32).contiguous()
     m = attention_mask.detach().reshape(B, T).to(device=dev, dtype=torch.float32).contiguous()
     p_v, ld_v, _ = _lib._ptr_ld(value_out)
@@ -78,7 +81,7 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
     if B:
         n_ws = int(lib.dhr_lexical_proj_workspace(B, T, V, mode))
         ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.dhr_lexical_proj_head(M.device(hidden), _lib.MEM_DEVICE, mode, hidden.data_ptr(), _lib.VAL_F16, B, T, H, ld_batch, ld_token,
+        _lib.check(lib.dhr_lexical_proj_head(M.device(hidden), _lib.MEM_DEVICE, mode, hidden.data_ptr(), _lib._val_code(hidden, bf16=True), B, T, H, ld_batch, ld_token,
                                              weight.data_ptr(), V, ld_weight, p_b, b_dt, w.data_ptr(), T, m.data_ptr(), T, dims, remove_dims, p_v,
                                              _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim, ws.data_ptr(), n_ws,
                                              M.stream(hidden)), "dhr_lexical_proj_head")

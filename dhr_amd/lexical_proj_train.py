@@ -10,13 +10,14 @@ encoding:
 and `.backward()` returns the gradients of `hidden`, `weight`, `bias` and `term_weights`.  The logits and their gradient exist only in
 registers and LDS; besides its inputs the op keeps the reps, the int16 token that attains each maximum, the softmax value of that token
 (fp32 [B, V]) and under 256 bytes per token.  Masked tokens are never multiplied.  The forward values are bit-identical to
-`dhr_amd.lexical_proj.lexical_reps` on the same fp16 operands.
+`dhr_amd.lexical_proj.lexical_reps` on the same fp16 or bf16 operands.
 
 Arguments: `hidden` [B, L, H], the input of the vocabulary projector (DistilBERT: the output of `vocab_layer_norm`), and `weight` [V, H]: fp16,
-or fp32, which is rounded to fp16 once, as autocast's `linear` does with the fp32 states of a layer norm and an fp32 master weight.  H is a
-multiple of 8, at most 1024.  `bias` [V] fp16 / fp32 or None.  `skip_tokens = s` drops the first s tokens; `term_weights` ([B, L - s] or
+bf16 or fp32.  The kernels read both in one 16-bit type: bf16 if either is bf16, else fp16 (one fp16 and one bf16 is a DhrError); an fp32
+operand is rounded to that type once, as autocast's `linear` does with the fp32 states of a layer norm and an fp32 master weight.  H is a
+multiple of 8, at most 1024.  `bias` [V] fp16 / bf16 / fp32 or None.  `skip_tokens = s` drops the first s tokens; `term_weights` ([B, L - s] or
 [B, L - s, 1], a floating dtype) and `attention_mask` ([B, L - s] or [B, L - s, 1]) are what the reference slices with [:, 1:].  Pass the
-model's whole hidden states with skip_tokens=1, or the `[:, 1:]` view with skip_tokens=0: the same bits.  fp16 tensors are read in place
+model's whole hidden states with skip_tokens=1, or the `[:, 1:]` view with skip_tokens=0: the same bits.  fp16 and bf16 tensors are read in place
 whatever their batch / token / row strides, the last dimension contiguous.
 
 Gradients: to `hidden` (all L tokens; skipped and masked rows are exact zeros), `weight` (a plain [V, H] tensor, so tied word embeddings
@@ -61,11 +62,13 @@ def _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens):
             raise ValueError('{} must be [{}, {}] or [{}, {}, 1] (batch, tokens - skip_tokens), got {}'.format(what, B, T, B, T, tuple(a.shape)))
     if T > MAX_TOKENS:
         raise ValueError('more than {} tokens'.format(MAX_TOKENS))
-    ok = (torch.float16, torch.float32)
+    ok = (torch.float16, torch.bfloat16, torch.float32)
     if hidden.dtype not in ok or weight.dtype not in ok:
-        raise _lib.DhrError(f"unsupported hidden / weight dtype {hidden.dtype} / {weight.dtype} (float16 / float32)")
+        raise _lib.DhrError(f"unsupported hidden / weight dtype {hidden.dtype} / {weight.dtype} (float16 / bfloat16 / float32)")
+    if {hidden.dtype, weight.dtype} == {torch.float16, torch.bfloat16}:
+        raise _lib.DhrError(f"hidden / weight dtype {hidden.dtype} / {weight.dtype}: one float16 and one bfloat16 operand have no common 16-bit type")
     if bias is not None and bias.dtype not in ok:
-        raise _lib.DhrError(f"unsupported bias dtype {bias.dtype} (float16 / float32)")
+        raise _lib.DhrError(f"unsupported bias dtype {bias.dtype} (float16 / bfloat16 / float32)")
     if not term_weights.dtype.is_floating_point:
         raise _lib.DhrError(f"unsupported term_weights dtype {term_weights.dtype} (a floating-point dtype)")
     if H % 8 or H > MAX_HIDDEN:
@@ -78,16 +81,21 @@ def _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens):
     return B, L, T, H, V
 
 
-def _fp16_rows(a):
-    """the fp16 operand as the kernels read it: rounded once if fp32, the last dimension contiguous, rows (and batches) not overlapping"""
-    return M.as_read(M.cast(a.detach(), "float16"))[0]
+def _operand_dtype(hidden, weight):
+    """the 16-bit type the kernels read both operands in: bfloat16 if either is, else float16"""
+    return "bfloat16" if "bfloat16" in (M.dtype_name(hidden), M.dtype_name(weight)) else "float16"
+
+
+def _rows16(a, dtype):
+    """the 16-bit operand as the kernels read it: rounded once if fp32, the last dimension contiguous, rows (and batches) not overlapping"""
+    return M.as_read(M.cast(a.detach(), dtype))[0]
 
 
 def _head_args(h, W, b, w, m, B, T, skip_tokens, H, V):
     """the arguments that dhr_lexical_proj_train and dhr_lexical_proj_backward share, from the tensors as they are NOW
-    (h, W: as _fp16_rows returns them; b, w [B, T], m [B, T]: contiguous)"""
-    return (M.device(h), _lib.MEM_DEVICE, h.data_ptr(), _lib.VAL_F16, B, T, skip_tokens, H, *M.lds(h), W.data_ptr(), V, *M.lds(W), M.data_ptr(b),
-            _lib.VAL_F32 if b is None else _lib._val_code(b), w.data_ptr(), T, m.data_ptr(), T)
+    (h, W: as _rows16 returns them, of one dtype; b, w [B, T], m [B, T]: contiguous)"""
+    return (M.device(h), _lib.MEM_DEVICE, h.data_ptr(), _lib._val_code(h, bf16=True), B, T, skip_tokens, H, *M.lds(h), W.data_ptr(), V, *M.lds(W), M.data_ptr(b),
+            _lib.VAL_F32 if b is None else _lib._val_code(b, bf16=True), w.data_ptr(), T, m.data_ptr(), T)
 
 
 def _function():
@@ -103,8 +111,11 @@ def _function():
             B, L, T, H, V = _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens)
             lib = _lib.load()
             dev = hidden.device
-            h, W = _fp16_rows(hidden), _fp16_rows(weight)
+            op = _operand_dtype(hidden, weight)
+            h, W = _rows16(hidden, op), _rows16(weight, op)
             b = None if bias is None else bias.detach().contiguous()
+            if b is not None and M.dtype_name(b) == "bfloat16" and op == "float16":  # the fp16 kernels read fp32 or fp16: [V] values, widened exactly
+                b = b.float()
             w = term_weights.detach().reshape(B, T).to(torch.float32).contiguous()
             m = attention_mask.detach().reshape(B, T).to(torch.float32).contiguous()
             reps = torch.empty((B, V), dtype=torch.float32, device=dev)
@@ -126,7 +137,7 @@ def _function():
         def backward(ctx, grad, _grad_tok):
             # ctx keeps scalars only: saved-tensor hooks (save_on_cpu, checkpointing) may hand back the tensors at other addresses
             h, W, b, w, m, tok, pwin, ws = ctx.saved_tensors
-            h, W = _fp16_rows(h), _fp16_rows(W)          # (no copies unless a hook changed the layout)
+            h, W = _rows16(h, h.dtype), _rows16(W, W.dtype)     # (no copies unless a hook changed the layout)
             b, w, m, tok, pwin, ws = (None if t is None else t.contiguous() for t in (b, w, m, tok, pwin, ws))
             B, L, T, H, V, skip_tokens, n_ws, h_dtype, W_dtype, b_dtype, w_shape, w_dtype = ctx.geom
             need_h, need_W, need_b, need_w = ctx.needs_input_grad[:4]
@@ -138,10 +149,10 @@ def _function():
             g, ld_g = M.grad_rows(grad, B, V)
             dh = torch.empty((B, L, H), dtype=h_dtype, device=dev) if need_h else None
             dW = torch.empty((V, H), dtype=W_dtype, device=dev) if need_W else None
-            db = torch.empty((V,), dtype=b_dtype, device=dev) if need_b else None
+            db = torch.empty((V,), dtype=b.dtype, device=dev) if need_b else None     # (fp32 where the forward widened the bias)
             dw = torch.empty((B, T), dtype=torch.float32, device=dev) if need_w else None
             if B:
-                ptr, code = M.data_ptr, lambda t: _lib.VAL_F32 if t is None else _lib._val_code(t)
+                ptr, code = M.data_ptr, lambda t: _lib.VAL_F32 if t is None else _lib._val_code(t, bf16=True)
                 _lib.check(lib.dhr_lexical_proj_backward(*_head_args(h, W, b, w, m, B, T, skip_tokens, H, V), g.data_ptr(), ld_g,
                                                          tok.data_ptr(), V, pwin.data_ptr(), V, ws.data_ptr(), n_ws, ptr(dh), code(dh), L * H, H,
                                                          ptr(dW), code(dW), H, ptr(db), code(db), ptr(dw), T, M.stream(h)),
@@ -150,7 +161,7 @@ def _function():
                 for t in (dW, db):
                     if t is not None:
                         t.zero_()
-            return dh, dW, db, (None if dw is None else dw.to(w_dtype).reshape(w_shape)), None, None
+            return dh, dW, (None if db is None else db.to(b_dtype)), (None if dw is None else dw.to(w_dtype).reshape(w_shape)), None, None
 
     _FN = LexicalProjReps
     return _FN

@@ -15,13 +15,13 @@ keeps, besides its inputs, the reps, the int16 token that attains each maximum a
 from the logits and writes the gradient of the logits in one streaming pass.  The forward values are bit-identical to
 `dhr_amd.lexical.lexical_reps` (which detaches its inputs and serves encoding).
 
-Arguments: `logits` [B, L, V] fp16 or fp32 on a GPU (any batch / token strides, the last dimension contiguous); `skip_tokens = s` drops the
+Arguments: `logits` [B, L, V] fp16, bf16 or fp32 on a GPU (any batch / token strides, the last dimension contiguous); `skip_tokens = s` drops the
 first s tokens, so `term_weights` ([B, L - s] or [B, L - s, 1], fp16 / fp32) and `attention_mask` ([B, L - s] or [B, L - s, 1], any integer,
 bool or float dtype) are what the reference slices with [:, 1:].  Pass the model's whole logits with skip_tokens=1: the gradient of the
 whole tensor is then written in one pass (rows of skipped and masked tokens as zeros), where autograd's backward of a `[:, 1:]` view would
 add a memset and a copy of the largest tensor of the step.  The view with skip_tokens=0 works too and gives the same numbers.
 
-Differentiable with respect to `logits` (the gradient comes back in their dtype) and `term_weights` (in their dtype and shape);
+Differentiable with respect to `logits` (the gradient comes back in their dtype, fp16 / bf16 rounded once from fp32) and `term_weights` (in their dtype and shape);
 `attention_mask` and `tok` are not differentiable.  At a tie the first token takes the gradient, like torch.max.  The sums of the backward
 run in a fixed order: two runs on the same inputs are bit-identical.  Everything is enqueued on torch's current stream of the logits'
 device, without a host synchronisation; buffers come from torch's allocator.  There is no CPU implementation: without a GPU the call raises."""
@@ -53,8 +53,8 @@ def _check(logits, term_weights, attention_mask, skip_tokens):
             raise ValueError('{} must be [{}, {}] or [{}, {}, 1] (batch, tokens - skip_tokens), got {}'.format(what, B, T, B, T, tuple(a.shape)))
     if T > MAX_TOKENS:
         raise ValueError('more than {} tokens'.format(MAX_TOKENS))
-    if logits.dtype not in (torch.float16, torch.float32):
-        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / float32)")
+    if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / bfloat16 / float32)")
     if not term_weights.dtype.is_floating_point:
         raise _lib.DhrError(f"unsupported term_weights dtype {term_weights.dtype} (a floating-point dtype)")
     if not logits.is_cuda:
@@ -83,7 +83,7 @@ def _function():
             tok = torch.empty((B, V), dtype=torch.int16, device=x.device)
             ws = torch.empty((int(lib.dhr_lexical_head_train_workspace(B, T)) if B else 0,), dtype=torch.uint8, device=x.device)
             if B:
-                _lib.check(lib.dhr_lexical_head_train(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x), B, T, skip_tokens, V, ld_batch,
+                _lib.check(lib.dhr_lexical_head_train(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x, bf16=True), B, T, skip_tokens, V, ld_batch,
                                                       ld_token, w.data_ptr(), T, m.data_ptr(), T, reps.data_ptr(), V, tok.data_ptr(), V, ws.data_ptr(),
                                                       M.stream(x)), "dhr_lexical_head_train")
             ctx.save_for_backward(x, tok, ws)
@@ -105,7 +105,7 @@ def _function():
             dx = torch.empty((B, L, V), dtype=x.dtype, device=x.device) if need_x else None
             dw = torch.empty((B, T), dtype=torch.float32, device=x.device) if need_w else None
             if B:
-                _lib.check(lib.dhr_lexical_head_backward(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x), B, T, skip_tokens, V, ld_batch,
+                _lib.check(lib.dhr_lexical_head_backward(M.device(x), _lib.MEM_DEVICE, x.data_ptr(), _lib._val_code(x, bf16=True), B, T, skip_tokens, V, ld_batch,
                                                          ld_token, g.data_ptr(), ld_g, tok.data_ptr(), V, ws.data_ptr(), M.data_ptr(dx), L * V, V,
                                                          M.data_ptr(dw), T, M.stream(x)), "dhr_lexical_head_backward")
             return dx, (None if dw is None else dw.to(w_dtype).reshape(w_shape)), None, None

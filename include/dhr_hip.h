@@ -41,7 +41,10 @@ typedef enum dhr_status {
 } dhr_status;
 
 typedef enum dhr_idx_dtype { DHR_IDX_NONE = 0, DHR_IDX_U8 = 1, DHR_IDX_I8 = 2, DHR_IDX_I16 = 3 } dhr_idx_dtype;
-typedef enum dhr_val_dtype { DHR_VAL_F16 = 0, DHR_VAL_F32 = 1 } dhr_val_dtype;
+/* DHR_VAL_BF16 is taken by the six lexical head entry points only (dhr_lexical_head, dhr_lexical_head_train / _backward, dhr_lexical_proj_head,
+ * dhr_lexical_proj_train / _backward): as the dtype of the logits or of hidden / weight, of the projection's bias and of the gradients the two
+ * backward calls write.  Every other value dtype argument (index records, query batches, value_out, cls, the other ops) refuses it. */
+typedef enum dhr_val_dtype { DHR_VAL_F16 = 0, DHR_VAL_F32 = 1, DHR_VAL_BF16 = 2 } dhr_val_dtype;
 typedef enum dhr_mem_kind { DHR_MEM_HOST = 0, DHR_MEM_DEVICE = 1 } dhr_mem_kind;
 
 typedef struct dhr_index dhr_index; /* opaque */
@@ -301,7 +304,7 @@ int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t v
 
 /* The lexical head of the encoders fused with the step after it (tevatron/DHR/modeling.py:297-300,328-331,
  * tevatron/Aggretriever/modeling.py:274-278,306-310; then densify or aggregate and the fp16 casts of tevatron/driver/encode.py:149-194).
- * logits is [batch, n_tokens, vocab] (value_dtype DHR_VAL_F16 / DHR_VAL_F32, strides ld_batch / ld_token / 1: the [:, 1:] view of the
+ * logits is [batch, n_tokens, vocab] (value_dtype DHR_VAL_F16 / DHR_VAL_BF16 / DHR_VAL_F32, strides ld_batch / ld_token / 1: the [:, 1:] view of the
  * model's [B, L, V] logits), term_weights and mask are fp32 [batch, n_tokens] (row strides ld_weights / ld_mask).  With
  * p = softmax over the whole vocabulary in fp32,
  *   reps[b][v] = max_t (p[b][t][v] * w[b][t]) * mask[b][t]       (first token on ties: a fully masked column keeps the sign of its first w)
@@ -311,7 +314,8 @@ int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t v
  *   DHR_LEX_AGG_FULL  aggregate(reps, dims, full=True): groups of 2*dims columns from remove_dims (a negative remove_dims pads -remove_dims
  *                     zero columns at the end), then pos * (pos > neg) - neg * (pos <= neg) of the even / odd columns
  *   DHR_LEX_AGG_SEMI  aggregate(reps, dims, full=False): groups of dims columns from remove_dims >= 0
- * out_value_dtype DHR_VAL_F16 rounds to fp16.  cls_dim > 0 copies cls [batch, cls_dim] (row stride ld_cls) into the record columns that follow
+ * out_value_dtype DHR_VAL_F16 rounds to fp16 (out_value and cls are never bf16).  bf16 logits widen to fp32 exactly: the same values in fp16 and
+ * in bf16 give the same bits.  cls_dim > 0 copies cls [batch, cls_dim] (row stride ld_cls) into the record columns that follow
  * (vocab or dims), so ld_value >= those + cls_dim.  workspace: NULL, or batch * n_tokens * 16 bytes of device memory on `device` (device
  * arrays only).  All arrays live in mem_kind memory; host arrays are staged through the device in blocks of rows.  NaN and +inf logits
  * are out of scope; every unmasked row needs a finite logit.  DHR_ERR_INVALID when the vocabulary does not split into whole groups.
@@ -330,16 +334,18 @@ int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexical, int32_t
 
 /* dhr_lexical_head with the vocabulary projection in front of it fused in, for ENCODING (forward only): the MLM logits
  *   x[b][t][v] = sum_k hidden[b][t][k] * weight[v][k] + bias[v]      (fp32 products and sums, never rounded to fp16)
- * are never written to memory, and masked tokens are never multiplied.  hidden is [batch, n_tokens, hidden_dim] (value_dtype DHR_VAL_F16,
+ * are never written to memory, and masked tokens are never multiplied.  hidden is [batch, n_tokens, hidden_dim] (value_dtype DHR_VAL_F16 or
+ * DHR_VAL_BF16: v_mfma_f32_32x32x16_f16 / _bf16, the same tiling, walk and reduction order for both;
  * strides ld_batch / ld_token / 1: the [:, 1:] view of the projector's input, read in place; hidden_dim a multiple of 8), weight is
- * [vocab, hidden_dim] of the same dtype (row stride ld_weight), bias [vocab] (bias_dtype DHR_VAL_F16 / DHR_VAL_F32) or NULL.  term_weights,
+ * [vocab, hidden_dim] of the same dtype (row stride ld_weight), bias [vocab] (bias_dtype DHR_VAL_F32 / DHR_VAL_F16; DHR_VAL_BF16 with bf16 operands) or NULL.  term_weights,
  * mask, mode, dims, remove_dims and every output argument are those of dhr_lexical_head, and so is what is written: reps, ties (the first
  * token, the first group) and the signs of zero; a masked token enters as (p * w) * 0.  DHR_LEX_RAW writes fp32 only.
  * Device memory only (mem_kind DHR_MEM_DEVICE).  The library allocates nothing: the caller passes dhr_lexical_proj_workspace(batch, n_tokens,
  * vocab, mode) bytes of device memory (at most 4 * batch * vocab + 256 * batch * n_tokens + 65536), aligned to 16 bytes.  The call ENQUEUES
  * on `stream` and returns without waiting.  No atomics: two calls on the same arguments are bit-identical.  NaN / inf are out of scope.
  * DHR_ERR_INVALID for NULL pointers, negative sizes, hidden_dim not a multiple of 8, unknown dtypes, host memory, a workspace that is too small,
- * a vocabulary that does not split into whole groups; DHR_ERR_UNSUPPORTED for fp32 operands and fp16 raw reps. */
+ * a vocabulary that does not split into whole groups; DHR_ERR_UNSUPPORTED for fp32 operands, a bf16 bias next to fp16 operands (the fp16
+ * kernels read fp32 or fp16, as before bf16 was taken) and fp16 raw reps. */
 int64_t dhr_lexical_proj_workspace(int64_t batch, int32_t n_tokens, int32_t vocab, int32_t mode);
 int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t mode, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens,
                           int32_t hidden_dim, int64_t ld_batch, int64_t ld_token, const void* weight, int32_t vocab, int64_t ld_weight,
@@ -381,7 +387,7 @@ int dhr_densify_backward(int32_t device, int32_t mem_kind, const float* grad_val
 
 /* The lexical head of a TRAINING step, forward and backward (the same lines of modeling.py as dhr_lexical_head, with autograd on): device
  * arrays only (DHR_ERR_UNSUPPORTED for DHR_MEM_HOST: training tensors live on the device), enqueued on `stream` without waiting, nothing
- * allocated.  logits is the model's [batch, skip_tokens + n_tokens, vocab] tensor (value_dtype DHR_VAL_F16 / DHR_VAL_F32, strides ld_batch /
+ * allocated.  logits is the model's [batch, skip_tokens + n_tokens, vocab] tensor (value_dtype DHR_VAL_F16 / DHR_VAL_BF16 / DHR_VAL_F32, strides ld_batch /
  * ld_token / 1); the first skip_tokens tokens take no part (the reference drops token 0; pass the [:, 1:] view with skip_tokens = 0 for the
  * same numbers).  term_weights and mask are fp32 [batch, n_tokens].  n_tokens <= 32767.
  *   dhr_lexical_head_train_workspace  bytes of device memory the two calls share: (max, sum, w, mask) per token, written by the forward and
@@ -392,7 +398,7 @@ int dhr_densify_backward(int32_t device, int32_t mem_kind, const float* grad_val
  *                                     A[b][t] = sum over {v : tokens[b][v] == t} of grad_reps[b][v] * p[b][t][v]:
  *                                     grad_weights[b][t] = mask * A (fp32 [batch, n_tokens]),
  *                                     grad_logits[b][t][v] = p * ([tokens[b][v] == t] * grad_reps[b][v] * w * mask - w * mask * A), in the
- *                                     logits' dtype, the WHOLE [batch, skip_tokens + n_tokens, vocab] tensor (strides ld_grad_batch /
+ *                                     logits' dtype (rounded once from fp32, to nearest even), the WHOLE [batch, skip_tokens + n_tokens, vocab] tensor (strides ld_grad_batch /
  *                                     ld_grad_token / 1): skipped and masked tokens are written as zeros.  Either output may be NULL.
  * p is recomputed from the logits, never stored.  A is accumulated in fp64 in a fixed order (no atomics): two calls on the same arguments are
  * bit-identical. */
@@ -410,9 +416,9 @@ int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logi
  * the op starts from the projector's input and returns the gradients of hidden, weight, bias and the term weights; the logits
  *   x[r][v] = hidden[r] . weight[v] + bias[v]      (fp32 products and sums)
  * and their gradient exist only in registers and LDS, forward and backward, and masked tokens are never multiplied.  hidden is the model's
- * [batch, skip_tokens + n_tokens, hidden_dim] tensor (value_dtype DHR_VAL_F16, strides ld_batch / ld_token / 1, hidden_dim a multiple of 8
- * up to 1024); the first skip_tokens tokens take no part.  weight is [vocab, hidden_dim] fp16 (row stride ld_weight), bias [vocab]
- * (DHR_VAL_F16 / DHR_VAL_F32) or NULL, term_weights and mask fp32 [batch, n_tokens], n_tokens <= 32767.
+ * [batch, skip_tokens + n_tokens, hidden_dim] tensor (value_dtype DHR_VAL_F16 or DHR_VAL_BF16, strides ld_batch / ld_token / 1, hidden_dim a
+ * multiple of 8 up to 1024); the first skip_tokens tokens take no part.  weight is [vocab, hidden_dim] of the same dtype (row stride ld_weight),
+ * bias [vocab] (DHR_VAL_F32 / DHR_VAL_F16; DHR_VAL_BF16 with bf16 operands) or NULL, term_weights and mask fp32 [batch, n_tokens], n_tokens <= 32767.
  *   dhr_lexical_proj_train_workspace  bytes of device memory the two calls share, aligned to 16 bytes (0 for invalid sizes; at most
  *                                     256 * batch * n_tokens + 65536 * hidden_dim + 65536): the list of unmasked token rows and their softmax
  *                                     statistics, written by the forward and read by the backward, and what the backward needs itself.
@@ -428,13 +434,15 @@ int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logi
  *                                                         tensor (strides ld_grad_batch / ld_grad_token / 1): skipped and masked tokens are zeros
  *                                     grad_weight[v][k] = sum_r dx[r][v] hidden[r][k]    [vocab, hidden_dim], row stride ld_grad_weight
  *                                     grad_bias[v]      = sum_r dx[r][v]
- *                                     each DHR_VAL_F16 or DHR_VAL_F32 (its *_dtype), rounded once from fp32 accumulators.  Any output may be NULL
+ *                                     each DHR_VAL_F16 or DHR_VAL_F32, or with bf16 operands DHR_VAL_BF16 (its *_dtype), rounded once from fp32
+ *                                     accumulators.  Any output may be NULL
  *                                     and is then not computed (no grad_weight and no grad_bias: the weight-gradient pass does not run; no
  *                                     grad_hidden: nor does the other GEMM pass); all NULL: DHR_OK, nothing is launched.
- * dx is rounded to fp16 once, as the operand of the second product.  Device memory only (DHR_ERR_UNSUPPORTED for DHR_MEM_HOST), nothing is
+ * dx is rounded once to the dtype of hidden / weight, as the operand of the second product.  Device memory only (DHR_ERR_UNSUPPORTED for DHR_MEM_HOST), nothing is
  * allocated, the calls ENQUEUE on `stream` and return without waiting.  No atomics, every sum in a fixed order: two calls on the same
  * arguments are bit-identical.  DHR_ERR_INVALID for NULL pointers, bad sizes / strides / dtypes, hidden_dim not a multiple of 8, a workspace
- * that is too small or not aligned; DHR_ERR_UNSUPPORTED for fp32 operands, hidden_dim > 1024, n_tokens > 32767. */
+ * that is too small or not aligned; DHR_ERR_UNSUPPORTED for fp32 operands, a bf16 bias or a bf16 gradient next to fp16 operands (the
+ * fp16 kernels read and write fp32 or fp16, as before bf16 was taken), hidden_dim > 1024, n_tokens > 32767. */
 int64_t dhr_lexical_proj_train_workspace(int64_t batch, int32_t n_tokens, int32_t vocab, int32_t hidden_dim);
 int dhr_lexical_proj_train(int32_t device, int32_t mem_kind, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens,
                            int32_t skip_tokens, int32_t hidden_dim, int64_t ld_batch, int64_t ld_token, const void* weight, int32_t vocab,

@@ -3,6 +3,99 @@
 // the sharded control flow: sharded.hip; error record, exception classifier: abi.cpp.
 #include "host_stage.h"
 
+namespace {
+// ---- what the search entry points share
+dhr_search_stats fresh_stats(const dhr_index* ix, int Q, int k) {
+  dhr_search_stats st{};
+  st.n_rows = ix->n_rows; st.n_queries = Q; st.k = k;
+  return st;
+}
+// The sorted top-k keys of the workspace -> the caller's score / row arrays (host arrays are staged through the workspace; the copies are enqueued)
+int emit_results(dhr_index* ix, Workspace& w, int Q, int k, float* out_scores, int64_t* out_rows, int out_mem_kind, hipStream_t s) {
+  float* d_scores = out_scores;
+  int64_t* d_rows = out_rows;
+  if (out_mem_kind == DHR_MEM_HOST) {
+    const int rc = grow(w.out_stage, w.out_stage_bytes, (size_t)Q * k * 12, w.bytes);
+    if (rc != DHR_OK) return rc;
+    d_rows = (int64_t*)w.out_stage;
+    d_scores = (float*)((char*)w.out_stage + (size_t)Q * k * 8);
+  }
+  HIP_TRY(launch_emit(w.topk_keys, w.kp, Q, k, ix->row_offset, d_scores, d_rows, s));
+  if (out_mem_kind == DHR_MEM_HOST) {
+    HIP_TRY(hipMemcpyAsync(out_rows, d_rows, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
+  }
+  return DHR_OK;
+}
+// The timers of one call (its stream must be idle) added to the running stats: a call that opens a search starts them from zero (fresh_stats),
+// one that continues a staged search from the handle's
+void collect_timers(Timer& tm, dhr_search_stats& st) {
+  double ms[5] = {0, 0, 0, 0, 0};
+  tm.collect(ms);
+  st.gemm_ms += ms[T_GEMM]; st.refine_ms += ms[T_REFINE]; st.rescore_ms += ms[T_RESCORE]; st.select_ms += ms[T_SELECT]; st.prep_ms += ms[T_PREP];
+}
+// Controller without read-backs: the candidate counters live on the device (zero otherwise) and run on over the calls of a staged search.
+// Reads them (synchronises s) and adds what they gained since the last fold of this staged search.
+int fold_device_counters(dhr_index* ix, dhr_search_stats& st, hipStream_t s) {
+  Workspace& w = ix->ws;
+  HIP_TRY(hipMemcpyAsync(w.h_stats, w.d_stats, 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int64_t bound = (int64_t)((unsigned long long*)w.h_stats)[0], exact = (int64_t)((unsigned long long*)w.h_stats)[1];
+  st.candidates_bound += bound - ix->pend.dev_bound;
+  st.candidates_exact += exact - ix->pend.dev_exact;
+  ix->pend.dev_bound = bound; ix->pend.dev_exact = exact;
+  return DHR_OK;
+}
+// Every staged entry point runs through here: one that fails -- a status or an exception on its way to the barrier -- leaves NO staged search
+// open on the handle.  Its workspace may be half-consumed, so a later dhr_search_mid / _finish must not be accepted: the caller starts again
+// with dhr_search_begin or dhr_search_pre.
+template <typename Body>
+int staged_call(dhr_index* ix, Body&& body) {
+  struct Close {
+    dhr_index* ix; bool ok = false;
+    ~Close() { if (!ok && ix) staged_set(ix, StagedState::None); }
+  } close{ix};
+  const int rc = body();
+  close.ok = rc == DHR_OK;
+  return rc;
+}
+// What the staged calls hand to the shards' agreement: the r best scores a handle has seen so far, [Q, r] on the device ...
+int emit_best_scores(dhr_index* ix, int Q, int r, float* out_dev, hipStream_t s) {
+  HIP_TRY(launch_emit_scores(ix->ws.topk_keys, ix->ws.kp, Q, r, out_dev, s));
+  return DHR_OK;
+}
+// ... after a sampled run: its dhr_search_sample_rank best (nothing where the shard is not sampled: the call already ran the whole search)
+int emit_sample_scores(dhr_index* ix, int Q, int k, float* out_dev, hipStream_t s) {
+  const int r = dhr_search_sample_rank(ix, k);
+  if (r <= 0 || ix->pend.state == StagedState::Complete) return DHR_OK;
+  if (!out_dev) return set_error(DHR_ERR_INVALID, "null sample score buffer");
+  return emit_best_scores(ix, Q, r, out_dev, s);
+}
+// What the staged entry points share behind their validation: one stage of search_core, what it hands out (emit: enqueued), and -- where the
+// caller waits for the call (collect) or profiles -- the device counters (fold) and the timers.  qb: the call opens the staged search and its
+// counters; else it continues them.  collect = false (dhr_search_sharded*): the call only enqueues, the shards of a one-process search work concurrently.
+template <typename Emit>
+int staged_step(dhr_index* ix, const dhr_query_batch* qb, int k, Stage stage, const float* tau_dev, void* stream, bool collect, bool fold, Emit&& emit) {
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (qb) { staged_set(ix, StagedState::None); ix->pend.dev_bound = ix->pend.dev_exact = 0; }
+  Timer tm{ix->profile != 0, s, {}, {}};
+  dhr_search_stats st = qb ? fresh_stats(ix, qb->n_queries, k) : ix->stats;
+  Drain drain{ix, s};
+  int rc = search_core(ix, ix->ws, qb, k, 0, tm, st, s, stage, tau_dev);
+  if (rc != DHR_OK || (rc = emit(s)) != DHR_OK) return rc;
+  if (collect || ix->profile) {
+    if (fold) rc = fold_device_counters(ix, st, s);
+    else HIP_TRY(hipStreamSynchronize(s));
+    if (rc != DHR_OK) return rc;
+    collect_timers(tm, st);
+  }
+  ix->stats = st;
+  drain.armed = false;
+  return DHR_OK;
+}
+}  // namespace
+
 extern "C" int dhr_search(dhr_index* ix, const dhr_query_batch* qb, int32_t k, float* out_scores, int64_t* out_rows,
                           int32_t out_mem_kind, void* stream) try {
   dhr::alloc_checkpoint();
@@ -15,41 +108,23 @@ extern "C" int dhr_search(dhr_index* ix, const dhr_query_batch* qb, int32_t k, f
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t s = (hipStream_t)stream;
   const int Q = qb->n_queries;
-  ix->pend.valid = false;          // a plain search overwrites the workspace of any staged search left open on this handle
+  staged_set(ix, StagedState::None);          // a plain search overwrites the workspace of any staged search left open on this handle
   Events evs;
   hipEvent_t ev0, ev1;
   HIP_TRY(evs.add(&ev0)); HIP_TRY(evs.add(&ev1));
   HIP_TRY(hipEventRecord(ev0, s));
   Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st{};
-  st.n_rows = ix->n_rows; st.n_queries = Q; st.k = k;
+  dhr_search_stats st = fresh_stats(ix, Q, k);
   Workspace& w = ix->ws;
   Drain drain{ix, s};
   if ((rc = search_core(ix, w, qb, k, 0, tm, st, s)) != DHR_OK) return rc;
-
-  // ---- results
-  float* d_scores = out_scores;
-  int64_t* d_rows = out_rows;
-  if (out_mem_kind == DHR_MEM_HOST) {
-    const size_t need = (size_t)Q * k * 12;
-    if ((rc = grow(w.out_stage, w.out_stage_bytes, need, w.bytes)) != DHR_OK) return rc;
-    d_rows = (int64_t*)w.out_stage;
-    d_scores = (float*)((char*)w.out_stage + (size_t)Q * k * 8);
-  }
-  HIP_TRY(launch_emit(w.topk_keys, w.kp, Q, k, ix->row_offset, d_scores, d_rows, s));
-  if (out_mem_kind == DHR_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(out_rows, d_rows, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-  }
+  if ((rc = emit_results(ix, w, Q, k, out_scores, out_rows, out_mem_kind, s)) != DHR_OK) return rc;
   HIP_TRY(hipEventRecord(ev1, s));
   HIP_TRY(hipStreamSynchronize(s));
   float total = 0.f;
   hipEventElapsedTime(&total, ev0, ev1);
   st.total_ms = total;
-  double ms[5] = {0, 0, 0, 0, 0};
-  tm.collect(ms);
-  st.gemm_ms = ms[T_GEMM]; st.refine_ms = ms[T_REFINE]; st.rescore_ms = ms[T_RESCORE]; st.select_ms = ms[T_SELECT];
-  st.prep_ms = ms[T_PREP];
+  collect_timers(tm, st);
   ix->stats = st;
   drain.armed = false;
   return DHR_OK;
@@ -77,29 +152,27 @@ extern "C" int dhr_search_rerank(dhr_index* ix, const dhr_query_batch* qb1, cons
   HIP_TRY(evs.add(&ev0)); HIP_TRY(evs.add(&ev1));
   HIP_TRY(hipEventRecord(ev0, s));
   Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st{};
-  st.n_rows = ix->n_rows; st.n_queries = Q; st.k = k;
+  dhr_search_stats st = fresh_stats(ix, Q, k);
   Workspace& w = ix->ws;
   Drain drain{ix, s};
   // ---- stage 1
   if ((rc = search_core(ix, w, qb1, k1, 0, tm, st, s)) != DHR_OK) return rc;
   // ---- stage 2: exact scores of the stage-1 rows under the full batch, top-k of those
-  DevMem rows_mem;
+  DevMem rows_mem;          // (releases the scratch on every way out)
   uint32_t*& d_rows32 = (uint32_t*&)rows_mem.p;
   HIP_TRY(hipMalloc((void**)&d_rows32, (size_t)Q * k1 * 4));
-  auto done = [&](int code) { return code; };       // (rows_mem releases the scratch)
-  if (launch_keys_to_rows(w.topk_keys, w.kp, Q, k1, d_rows32, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "keys_to_rows launch failed"));
-  if (w.keys_ld < k1) return done(set_error(DHR_ERR_INTERNAL, "key buffer smaller than k1"));
+  if (launch_keys_to_rows(w.topk_keys, w.kp, Q, k1, d_rows32, s) != hipSuccess) return set_error(DHR_ERR_HIP, "keys_to_rows launch failed");
+  if (w.keys_ld < k1) return set_error(DHR_ERR_INTERNAL, "key buffer smaller than k1");
   const bool gate2 = ix->d_dlr > 0 && qb2->index != nullptr && qb2->index_dtype != DHR_IDX_NONE;
   tm.begin(T_PREP);
-  if ((rc = prep_queries(ix, w, qb2, s)) != DHR_OK) return done(rc);
-  if (hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "memset failed"));
+  if ((rc = prep_queries(ix, w, qb2, s)) != DHR_OK) return rc;
+  if (hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s) != hipSuccess) return set_error(DHR_ERR_HIP, "memset failed");
   tm.end();
   RescoreArgs r = base_rescore_args(ix, w, Q, gate2);
   r.rows32 = d_rows32; r.ld_rows = k1; r.count_all = (uint32_t)k1; r.max_count = (uint32_t)k1;
   r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
   tm.begin(T_RESCORE);
-  if (launch_rescore(r, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "rescore launch failed"));
+  if (launch_rescore(r, s) != hipSuccess) return set_error(DHR_ERR_HIP, "rescore launch failed");
   tm.end();
   st.candidates_exact += (int64_t)Q * k1;
   SelectArgs sel{};
@@ -109,146 +182,80 @@ extern "C" int dhr_search_rerank(dhr_index* ix, const dhr_query_batch* qb1, cons
   sel.kps = 64; while (sel.kps < k) sel.kps <<= 1;
   sel.margin = w.margin; sel.tau = w.tau; sel.thr = w.thr; sel.n_queries = Q;
   tm.begin(T_SELECT);
-  if (launch_select(sel, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "select launch failed"));
+  if (launch_select(sel, s) != hipSuccess) return set_error(DHR_ERR_HIP, "select launch failed");
   tm.end();
-  // ---- results
-  float* d_scores = out_scores;
-  int64_t* d_rows = out_rows;
-  if (out_mem_kind == DHR_MEM_HOST) {
-    const size_t need = (size_t)Q * k * 12;
-    if ((rc = grow(w.out_stage, w.out_stage_bytes, need, w.bytes)) != DHR_OK) return done(rc);
-    d_rows = (int64_t*)w.out_stage;
-    d_scores = (float*)((char*)w.out_stage + (size_t)Q * k * 8);
-  }
-  if (launch_emit(w.topk_keys, w.kp, Q, k, ix->row_offset, d_scores, d_rows, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "emit launch failed"));
-  if (out_mem_kind == DHR_MEM_HOST) {
-    if (hipMemcpyAsync(out_rows, d_rows, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(out_scores, d_scores, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "D2H failed"));
-  }
-  if (hipEventRecord(ev1, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "two-stage search failed on the device"));
+  if ((rc = emit_results(ix, w, Q, k, out_scores, out_rows, out_mem_kind, s)) != DHR_OK) return rc;
+  if (hipEventRecord(ev1, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "two-stage search failed on the device");
   float total = 0.f;
   hipEventElapsedTime(&total, ev0, ev1);
   st.total_ms = total;
-  double ms[5] = {0, 0, 0, 0, 0};
-  tm.collect(ms);
-  st.gemm_ms = ms[T_GEMM]; st.refine_ms = ms[T_REFINE]; st.rescore_ms = ms[T_RESCORE]; st.select_ms = ms[T_SELECT];
-  st.prep_ms = ms[T_PREP];
+  collect_timers(tm, st);
   ix->stats = st;
   drain.armed = false;
-  return done(DHR_OK);
+  return DHR_OK;
 } DHR_CATCH_STATUS
 
 // ---- staged search for the row-sharded path (dhr_amd/dist.py): the shards agree on ONE threshold per
 // query after their sampled runs, so each shard collects only its share of the global top-k.
+// The rank queries read the plan the staged calls of this handle run (search_plan.h): a shard never reports a rank its controller does not chase.
 extern "C" int32_t dhr_search_sample_rank(const dhr_index* ix, int32_t k) try {
   if (!ix || k <= 0) return 0;
-  int S = 0, r = k;
-  plan_sampling(ix, k, S, r);
-  return S >= 2 ? local_sample_rank(ix, r) : 0;
+  const SearchPlan p = search_plan_of(ix, k, 0, true);
+  return p.S >= 2 ? p.r_eff : 0;
 } DHR_CATCH_VALUE(0)
 extern "C" int32_t dhr_search_union_rank(const dhr_index* ix, int32_t k) try {
   if (!ix || k <= 0) return 0;
-  int S = 0, r = k;
-  plan_sampling(ix, k, S, r);
-  return S >= 2 ? r : 0;
+  const SearchPlan p = search_plan_of(ix, k, 0, true);
+  return p.S >= 2 ? p.r : 0;
 } DHR_CATCH_VALUE(0)
 
 // Ranks of the second agreement (dhr_search_mid): after the head, the sample and the first slice of the main pass a shard has seen the
-// fraction f of its rows, scattered; the union of what the shards have seen holds k f +- sqrt(k f (1 - f)) of the final top-k, so its
-// (k f + 6 sigma + 4)-th best score lies below the final k-th best (the counts verify it; a failure is repaired like any other).  A shard
-// reports its share of that rank (local_sample_rank's rule).
+// fraction f of its rows, scattered; the shards agree on the (k f + 6 sigma + 4)-th best score of the union of what they have seen, and a shard
+// reports its share of that rank (SearchPlan::mid_union / mid_local; 0: this index has no mid step).
+static int32_t local_and_union(int32_t local, int32_t uni, int32_t* out_local, int32_t* out_union) {
+  if (out_local) *out_local = local;
+  if (out_union) *out_union = uni;
+  return local;
+}
 extern "C" int32_t dhr_search_mid_ranks(const dhr_index* ix, int32_t k, int32_t* out_local, int32_t* out_union) try {
-  if (out_local) *out_local = 0;
-  if (out_union) *out_union = 0;
-  if (!ix || k <= 0) return 0;
-  int S = 0, r = k;
-  plan_sampling(ix, k, S, r);
-  if (S < 2) return 0;
-  const int r_eff = local_sample_rank(ix, r);
-  int64_t first = head_rows(ix, S, r_eff);
-  first = std::min(round_up(first, TILE_ROWS), round_up(ix->n_rows, TILE_ROWS));
-  const int64_t head = first / TILE_ROWS, rest = ix->n_tiles - head;
-  if (rest <= 0) return 0;
-  const int64_t n_sample = (rest + S - 1) / S, n_main = rest - n_sample;
-  if (n_main < 64) return 0;
-  const int64_t off = std::min<int64_t>(n_main, round_up(n_main * mid_share16() / 16, DOC_GROUP));
-  const double f = (double)(head + n_sample + off) / (double)ix->n_tiles;
-  const int ru = (int)std::min<double>(k, std::ceil((double)k * f + 6.0 * std::sqrt((double)k * f * (1.0 - f)) + 4.0));
-  const double m = (double)ru / std::max(1, ix->sample_share);
-  const int rl = ix->sample_share <= 1 ? ru : std::min(ru, (int)std::ceil(m + 5.0 * std::sqrt(m) + 4.0));
-  if (out_local) *out_local = rl;
-  if (out_union) *out_union = ru;
-  return rl;
+  if (!ix || k <= 0) return local_and_union(0, 0, out_local, out_union);
+  const SearchPlan p = search_plan_of(ix, k, 0, true);
+  return local_and_union(p.mid_local, p.mid_union, out_local, out_union);
 } DHR_CATCH_VALUE(0)
 // The first slice of the main pass with the thresholds of the first agreement; leaves the shard's r_local best scores seen so far in
 // out_scores_dev [Q, r_local] (r_local: dhr_search_mid_ranks, or what the shards agreed on).  dhr_search_finish then takes the thresholds of the
 // second agreement.
 static int search_mid_impl(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream) {
-  if (!ix || !ix->pend.valid) return set_error(DHR_ERR_INVALID, "dhr_search_mid without a matching dhr_search_begin");
-  if (ix->pend.done) return DHR_OK;                   // the shard was not sampled: its search is complete already
-  if (ix->pend.mid) return set_error(DHR_ERR_INVALID, "dhr_search_mid called twice");
+  if (!ix || ix->pend.state == StagedState::None) return set_error(DHR_ERR_INVALID, "dhr_search_mid without a matching dhr_search_begin");
+  if (ix->pend.state == StagedState::Complete) return DHR_OK;                   // the shard was not sampled: its search is complete already
+  if (ix->pend.state == StagedState::AfterMid) return set_error(DHR_ERR_INVALID, "dhr_search_mid called twice");
   if (!tau_hat_dev || !out_scores_dev) return set_error(DHR_ERR_INVALID, "null pointer");
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t s = (hipStream_t)stream;
   if (dhr_search_mid_ranks(ix, ix->pend.k, nullptr, nullptr) <= 0) return set_error(DHR_ERR_INVALID, "this index has no mid step (dhr_search_mid_ranks returned 0)");
   if (r_local <= 0 || r_local > ix->pend.k) return set_error(DHR_ERR_INVALID, "r_local must be in [1, k]");
-  const int32_t rl = r_local;
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st = ix->stats;
-  int rc;
-  Drain drain{ix, s};
-  if ((rc = search_core(ix, ix->ws, nullptr, ix->pend.k, 0, tm, st, s, 3, tau_hat_dev)) != DHR_OK) return rc;
-  HIP_TRY(launch_emit_scores(ix->ws.topk_keys, ix->ws.kp, ix->pend.Q, rl, out_scores_dev, s));
-  if (ix->profile) {
-    HIP_TRY(hipStreamSynchronize(s));
-    double ms[5] = {0, 0, 0, 0, 0};
-    tm.collect(ms);
-    st.gemm_ms += ms[T_GEMM]; st.refine_ms += ms[T_REFINE]; st.rescore_ms += ms[T_RESCORE]; st.select_ms += ms[T_SELECT];
-  }
-  ix->stats = st;
-  drain.armed = false;
-  return DHR_OK;
+  return staged_step(ix, nullptr, ix->pend.k, Stage::Mid, tau_hat_dev, stream, false, false,
+                     [&](hipStream_t s) { return emit_best_scores(ix, ix->pend.Q, r_local, out_scores_dev, s); });
 }
 extern "C" int dhr_search_mid(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream) try {
-  int rc = search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream);
-  if (rc == DHR_OK && ix) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return rc;
+  return staged_call(ix, [&] {
+    int rc = search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream);
+    if (rc == DHR_OK && ix) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return rc;
+  });
 } DHR_CATCH_STATUS
 extern "C" int dhr_internal_search_mid_async(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream) try {
-  return search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream);
+  return staged_call(ix, [&] { return search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream); });
 } DHR_CATCH_STATUS
 
 // ---- first agreement in TWO rounds (round 5).  The shards of a sharded search each ran their whole sampled run from nothing, chasing their
 // share of the union's rank on their own: eight runs together rescored 3.2 k rows per query where the unsharded search's one run rescores
-// 0.7 k.  dhr_search_pre streams the first part of the shard's sample (pre_share16 / 16 of it) and reports its best scores seen so far; the
-// union of the parts is a fraction phi of the union sample, so its (r phi + 6 sigma + 4)-th best score lies below the union sample's final
-// r-th best (adaptive_rank's argument), and dhr_search_begin_rest streams the rest of the sample filtering at that COMMON threshold.  Whatever
-// the threshold is worth, the lists a shard reports afterwards are complete above it, so the union threshold computed from them can only
-// come out lower than the true one -- still valid; the count check at the end of the step verifies everything as before.
+// 0.7 k.  dhr_search_pre streams the first part of the shard's sample and reports its best scores seen so far, the shards agree on a COMMON
+// threshold from them (SearchPlan::pre_union / pre_local; 0: the sample is too small to split), and dhr_search_begin_rest streams the rest of
+// the sample filtering at it.  Whatever that threshold is worth, the lists a shard reports afterwards are complete above it, so the union
+// threshold computed from them can only come out lower than the true one -- still valid; the count check at the end of the step verifies it.
 extern "C" int32_t dhr_search_pre_ranks(const dhr_index* ix, int32_t k, int32_t* out_local, int32_t* out_union) try {
-  if (out_local) *out_local = 0;
-  if (out_union) *out_union = 0;
-  if (!ix || k <= 0) return 0;
-  int S = 0, r = k;
-  plan_sampling(ix, k, S, r);
-  if (S < 2) return 0;
-  const int r_eff = local_sample_rank(ix, r);
-  int64_t first = head_rows(ix, S, r_eff);
-  first = std::min(round_up(first, TILE_ROWS), round_up(ix->n_rows, TILE_ROWS));
-  const int64_t first_valid = std::min(first, ix->n_rows);
-  const int64_t rest = ix->n_tiles - first / TILE_ROWS;
-  if (rest <= 0) return 0;
-  const int64_t n_sample = (rest + S - 1) / S;
-  const int64_t n_a = pre_positions(n_sample);
-  if (n_a <= 0) return 0;
-  const double phi = (double)(first_valid + n_a * TILE_ROWS) / (double)(first_valid + n_sample * TILE_ROWS);
-  const int ru = adaptive_rank(r, phi);
-  const double m = (double)ru / std::max(1, ix->sample_share);
-  const int rl = ix->sample_share <= 1 ? ru : std::min(ru, (int)std::ceil(m + 5.0 * std::sqrt(m) + 4.0));
-  if (out_local) *out_local = rl;
-  if (out_union) *out_union = ru;
-  return rl;
+  if (!ix || k <= 0) return local_and_union(0, 0, out_local, out_union);
+  const SearchPlan p = search_plan_of(ix, k, 0, true);
+  return local_and_union(p.pre_local, p.pre_union, out_local, out_union);
 } DHR_CATCH_VALUE(0)
 static int search_pre_impl(dhr_index* ix, const dhr_query_batch* qb, int32_t k, int32_t r_local, float* out_scores_dev, void* stream, bool sync) {
   dhr::alloc_checkpoint();
@@ -258,168 +265,72 @@ static int search_pre_impl(dhr_index* ix, const dhr_query_batch* qb, int32_t k, 
   if (!out_scores_dev) return set_error(DHR_ERR_INVALID, "null pointer");
   if (dhr_search_pre_ranks(ix, k, nullptr, nullptr) <= 0) return set_error(DHR_ERR_INVALID, "this index has no pre step (dhr_search_pre_ranks returned 0)");
   if (r_local <= 0 || r_local > k) return set_error(DHR_ERR_INVALID, "r_local must be in [1, k]");
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t s = (hipStream_t)stream;
-  ix->pend.valid = false;
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st{};
-  st.n_rows = ix->n_rows; st.n_queries = qb->n_queries; st.k = k;
-  Drain drain{ix, s};
-  if ((rc = search_core(ix, ix->ws, qb, k, 0, tm, st, s, 4)) != DHR_OK) return rc;
-  HIP_TRY(launch_emit_scores(ix->ws.topk_keys, ix->ws.kp, qb->n_queries, r_local, out_scores_dev, s));
-  ix->pend.dev_bound = ix->pend.dev_exact = 0;
-  if (sync || ix->profile) {
-    HIP_TRY(hipStreamSynchronize(s));
-    double ms[5] = {0, 0, 0, 0, 0};
-    tm.collect(ms);
-    st.gemm_ms = ms[T_GEMM]; st.refine_ms = ms[T_REFINE]; st.rescore_ms = ms[T_RESCORE]; st.select_ms = ms[T_SELECT]; st.prep_ms = ms[T_PREP];
-  }
-  ix->stats = st;
-  drain.armed = false;
-  return DHR_OK;
+  return staged_step(ix, qb, k, Stage::Pre, nullptr, stream, sync, false,
+                     [&](hipStream_t s) { return emit_best_scores(ix, qb->n_queries, r_local, out_scores_dev, s); });
 }
 extern "C" int dhr_search_pre(dhr_index* ix, const dhr_query_batch* qb, int32_t k, int32_t r_local, float* out_scores_dev, void* stream) try {
-  return search_pre_impl(ix, qb, k, r_local, out_scores_dev, stream, true);
+  return staged_call(ix, [&] { return search_pre_impl(ix, qb, k, r_local, out_scores_dev, stream, true); });
 } DHR_CATCH_STATUS
 extern "C" int dhr_internal_search_pre_async(dhr_index* ix, const dhr_query_batch* qb, int32_t k, int32_t r_local, float* out_scores_dev, void* stream) try {
-  return search_pre_impl(ix, qb, k, r_local, out_scores_dev, stream, false);
+  return staged_call(ix, [&] { return search_pre_impl(ix, qb, k, r_local, out_scores_dev, stream, false); });
 } DHR_CATCH_STATUS
 // the rest of the sampled run behind dhr_search_pre; leaves the handle where dhr_search_begin leaves it (out_sample_scores_dev: [Q, dhr_search_sample_rank])
 static int search_begin_rest_impl(dhr_index* ix, const float* tau_dev, float* out_sample_scores_dev, void* stream, bool sync) {
-  if (!ix || !ix->pend.valid || !ix->pend.pre) return set_error(DHR_ERR_INVALID, "dhr_search_begin_rest without a matching dhr_search_pre");
+  if (!ix || ix->pend.state != StagedState::AfterPre) return set_error(DHR_ERR_INVALID, "dhr_search_begin_rest without a matching dhr_search_pre");
   if (!tau_dev || !out_sample_scores_dev) return set_error(DHR_ERR_INVALID, "null pointer");
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t s = (hipStream_t)stream;
   const int k = ix->pend.k, Q = ix->pend.Q;
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st = ix->stats;                     // continue the counters of the pre call
-  int rc;
-  Drain drain{ix, s};
-  if ((rc = search_core(ix, ix->ws, nullptr, k, 0, tm, st, s, 5, tau_dev)) != DHR_OK) return rc;
-  const int r = dhr_search_sample_rank(ix, k);
-  if (r > 0 && !ix->pend.done) HIP_TRY(launch_emit_scores(ix->ws.topk_keys, ix->ws.kp, Q, r, out_sample_scores_dev, s));
-  ix->pend.dev_bound = ix->pend.dev_exact = 0;
-  if (sync || ix->profile) {
-    HIP_TRY(hipMemcpyAsync(ix->ws.h_stats, ix->ws.d_stats, 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ix->pend.dev_bound = (int64_t)((unsigned long long*)ix->ws.h_stats)[0];
-    ix->pend.dev_exact = (int64_t)((unsigned long long*)ix->ws.h_stats)[1];
-    st.candidates_bound += ix->pend.dev_bound;
-    st.candidates_exact += ix->pend.dev_exact;
-    double ms[5] = {0, 0, 0, 0, 0};
-    tm.collect(ms);
-    st.gemm_ms += ms[T_GEMM]; st.refine_ms += ms[T_REFINE]; st.rescore_ms += ms[T_RESCORE]; st.select_ms += ms[T_SELECT]; st.prep_ms += ms[T_PREP];
-  }
-  ix->stats = st;
-  drain.armed = false;
-  return DHR_OK;
+  return staged_step(ix, nullptr, k, Stage::BeginRest, tau_dev, stream, sync, true,
+                     [&](hipStream_t s) { return emit_sample_scores(ix, Q, k, out_sample_scores_dev, s); });
 }
 extern "C" int dhr_search_begin_rest(dhr_index* ix, const float* tau_dev, float* out_sample_scores_dev, void* stream) try {
-  return search_begin_rest_impl(ix, tau_dev, out_sample_scores_dev, stream, true);
+  return staged_call(ix, [&] { return search_begin_rest_impl(ix, tau_dev, out_sample_scores_dev, stream, true); });
 } DHR_CATCH_STATUS
 extern "C" int dhr_internal_search_begin_rest_async(dhr_index* ix, const float* tau_dev, float* out_sample_scores_dev, void* stream) try {
-  return search_begin_rest_impl(ix, tau_dev, out_sample_scores_dev, stream, false);
+  return staged_call(ix, [&] { return search_begin_rest_impl(ix, tau_dev, out_sample_scores_dev, stream, false); });
 } DHR_CATCH_STATUS
 
-// sync = false (dhr_search_sharded*): only enqueues when the controller runs without read-backs -- the shards of a one-process search then
-// work concurrently until the collective layer's own synchronisation; statistics and timers are then not collected
+// (sync = false: the call only enqueues; statistics and timers are then not collected -- staged_step)
 static int search_begin_impl(dhr_index* ix, const dhr_query_batch* qb, int32_t k, float* out_sample_scores_dev, void* stream, bool sync) {
   dhr::alloc_checkpoint();
   int rc = check_queries(ix, qb);
   if (rc) return rc;
   if (k <= 0 || k > (1 << 20)) return set_error(DHR_ERR_INVALID, "k must be in [1, 1048576]");
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t s = (hipStream_t)stream;
-  ix->pend.valid = false;
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st{};
-  st.n_rows = ix->n_rows; st.n_queries = qb->n_queries; st.k = k;
-  Drain drain{ix, s};
-  if ((rc = search_core(ix, ix->ws, qb, k, 0, tm, st, s, 1)) != DHR_OK) return rc;
-  const int r = dhr_search_sample_rank(ix, k);
-  if (r > 0 && !ix->pend.done) {
-    if (!out_sample_scores_dev) return set_error(DHR_ERR_INVALID, "null sample score buffer");
-    HIP_TRY(launch_emit_scores(ix->ws.topk_keys, ix->ws.kp, qb->n_queries, r, out_sample_scores_dev, s));
-  }
-  ix->pend.dev_bound = ix->pend.dev_exact = 0;
-  if (sync || ix->profile) {
-    HIP_TRY(hipMemcpyAsync(ix->ws.h_stats, ix->ws.d_stats, 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // controller without read-backs: the counters live on the device (zero otherwise); remember what has been folded in
-    ix->pend.dev_bound = (int64_t)((unsigned long long*)ix->ws.h_stats)[0];
-    ix->pend.dev_exact = (int64_t)((unsigned long long*)ix->ws.h_stats)[1];
-    st.candidates_bound += ix->pend.dev_bound;
-    st.candidates_exact += ix->pend.dev_exact;
-    double ms[5] = {0, 0, 0, 0, 0};
-    tm.collect(ms);
-    st.gemm_ms = ms[T_GEMM]; st.refine_ms = ms[T_REFINE]; st.rescore_ms = ms[T_RESCORE]; st.select_ms = ms[T_SELECT]; st.prep_ms = ms[T_PREP];
-  }
-  ix->stats = st;
-  drain.armed = false;
-  return DHR_OK;
+  return staged_step(ix, qb, k, Stage::Begin, nullptr, stream, sync, true,
+                     [&](hipStream_t s) { return emit_sample_scores(ix, qb->n_queries, k, out_sample_scores_dev, s); });
 }
 extern "C" void dhr_internal_search_abort(dhr_index* ix) try {
-  if (ix) ix->pend.valid = false;
+  if (ix) staged_set(ix, StagedState::None);
 } DHR_CATCH_VOID
 extern "C" int dhr_search_begin(dhr_index* ix, const dhr_query_batch* qb, int32_t k, float* out_sample_scores_dev, void* stream) try {
-  return search_begin_impl(ix, qb, k, out_sample_scores_dev, stream, true);
+  return staged_call(ix, [&] { return search_begin_impl(ix, qb, k, out_sample_scores_dev, stream, true); });
 } DHR_CATCH_STATUS
 extern "C" int dhr_internal_search_begin_async(dhr_index* ix, const dhr_query_batch* qb, int32_t k, float* out_sample_scores_dev, void* stream) try {
-  return search_begin_impl(ix, qb, k, out_sample_scores_dev, stream, false);
+  return staged_call(ix, [&] { return search_begin_impl(ix, qb, k, out_sample_scores_dev, stream, false); });
 } DHR_CATCH_STATUS
 
 static int search_finish_impl(dhr_index* ix, const float* tau_hat_dev, float* out_scores, int64_t* out_rows,
                               int32_t* out_count_dev, int32_t out_mem_kind, void* stream, bool sync) {
-  if (!ix || !ix->pend.valid) return set_error(DHR_ERR_INVALID, "dhr_search_finish without a matching dhr_search_begin");
+  if (!ix || ix->pend.state == StagedState::None) return set_error(DHR_ERR_INVALID, "dhr_search_finish without a matching dhr_search_begin");
   if (!out_scores || !out_rows || !out_count_dev) return set_error(DHR_ERR_INVALID, "null output pointer");
   if (!DHR_MEM_KIND_OK(out_mem_kind)) return set_error(DHR_ERR_INVALID, "bad out_mem_kind");
-  if (!ix->pend.done && !tau_hat_dev) return set_error(DHR_ERR_INVALID, "thresholds are required (the shard ran a sampled pass)");
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t s = (hipStream_t)stream;
+  const bool complete = ix->pend.state == StagedState::Complete;      // the begin call already ran the whole (unsampled) search: no thresholds to check against
+  if (!complete && !tau_hat_dev) return set_error(DHR_ERR_INVALID, "thresholds are required (the shard ran a sampled pass)");
   const int Q = ix->pend.Q, k = ix->pend.k;
   Workspace& w = ix->ws;
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st = ix->stats;                     // continue the counters of the begin call
-  int rc;
-  Drain drain{ix, s};
-  if ((rc = search_core(ix, w, nullptr, k, 0, tm, st, s, 2, tau_hat_dev)) != DHR_OK) return rc;
-  HIP_TRY(launch_count_ge(w.topk_keys, w.kp, k, ix->pend.done ? nullptr : w.tau_hat, ix->pend.done ? nullptr : w.fail_flags, Q,
-                          out_count_dev, s));
-  float* d_scores = out_scores;
-  int64_t* d_rows = out_rows;
-  if (out_mem_kind == DHR_MEM_HOST) {
-    const size_t need = (size_t)Q * k * 12;
-    if ((rc = grow(w.out_stage, w.out_stage_bytes, need, w.bytes)) != DHR_OK) return rc;
-    d_rows = (int64_t*)w.out_stage;
-    d_scores = (float*)((char*)w.out_stage + (size_t)Q * k * 8);
-  }
-  HIP_TRY(launch_emit(w.topk_keys, w.kp, Q, k, ix->row_offset, d_scores, d_rows, s));
-  if (out_mem_kind == DHR_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(out_rows, d_rows, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-  }
-  if (sync || ix->profile || out_mem_kind == DHR_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(w.h_stats, w.d_stats, 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // device counters of a controller without read-backs: they run on from the begin call
-    st.candidates_bound += (int64_t)((unsigned long long*)w.h_stats)[0] - ix->pend.dev_bound;
-    st.candidates_exact += (int64_t)((unsigned long long*)w.h_stats)[1] - ix->pend.dev_exact;
-    double ms[5] = {0, 0, 0, 0, 0};
-    tm.collect(ms);
-    st.gemm_ms += ms[T_GEMM]; st.refine_ms += ms[T_REFINE]; st.rescore_ms += ms[T_RESCORE]; st.select_ms += ms[T_SELECT];
-  }
-  ix->stats = st;
-  ix->pend.valid = false;
-  drain.armed = false;
-  return DHR_OK;
+  const int rc = staged_step(ix, nullptr, k, Stage::Finish, tau_hat_dev, stream, sync || out_mem_kind == DHR_MEM_HOST, true, [&](hipStream_t s) {
+    HIP_TRY(launch_count_ge(w.topk_keys, w.kp, k, complete ? nullptr : w.tau_hat, complete ? nullptr : w.fail_flags, Q, out_count_dev, s));
+    return emit_results(ix, w, Q, k, out_scores, out_rows, out_mem_kind, s);
+  });
+  if (rc == DHR_OK) staged_set(ix, StagedState::None);
+  return rc;
 }
 extern "C" int dhr_search_finish(dhr_index* ix, const float* tau_hat_dev, float* out_scores, int64_t* out_rows,
                                  int32_t* out_count_dev, int32_t out_mem_kind, void* stream) try {
-  return search_finish_impl(ix, tau_hat_dev, out_scores, out_rows, out_count_dev, out_mem_kind, stream, true);
+  return staged_call(ix, [&] { return search_finish_impl(ix, tau_hat_dev, out_scores, out_rows, out_count_dev, out_mem_kind, stream, true); });
 } DHR_CATCH_STATUS
 extern "C" int dhr_internal_search_finish_async(dhr_index* ix, const float* tau_hat_dev, float* out_scores, int64_t* out_rows,
                                                 int32_t* out_count_dev, int32_t out_mem_kind, void* stream) try {
-  return search_finish_impl(ix, tau_hat_dev, out_scores, out_rows, out_count_dev, out_mem_kind, stream, false);
+  return staged_call(ix, [&] { return search_finish_impl(ix, tau_hat_dev, out_scores, out_rows, out_count_dev, out_mem_kind, stream, false); });
 } DHR_CATCH_STATUS
 
 extern "C" int dhr_score_rows(dhr_index* ix, const dhr_query_batch* qb, int32_t m, const int64_t* rows, float* out_scores,
@@ -429,7 +340,7 @@ extern "C" int dhr_score_rows(dhr_index* ix, const dhr_query_batch* qb, int32_t 
   if (rc) return rc;
   if (m <= 0 || !rows || !out_scores) return set_error(DHR_ERR_INVALID, "bad m / null pointer");
   if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
-  if (ix->pend.valid && !ix->pend.done)      // the staged search keeps its query batch in the workspace this call would overwrite
+  if (ix->pend.state != StagedState::None && ix->pend.state != StagedState::Complete)      // the staged search keeps its query batch in the workspace this call would overwrite
     return set_error(DHR_ERR_INVALID, "dhr_score_rows between dhr_search_begin and dhr_search_finish on the same handle");
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t s = (hipStream_t)stream;
@@ -446,21 +357,20 @@ extern "C" int dhr_score_rows(dhr_index* ix, const dhr_query_batch* qb, int32_t 
   uint32_t* d_rows32 = (uint32_t*)((char*)tmp + n * 8);
   float* d_sc = (float*)((char*)tmp + n * 12);
   const int64_t* src_rows = rows;
-  auto done = [&](int code) { return code; };       // (tmp_mem releases the scratch)
   if (mem_kind == DHR_MEM_HOST) {
-    if (hipMemcpyAsync(d_rows64, rows, n * 8, hipMemcpyHostToDevice, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "H2D failed"));
+    if (hipMemcpyAsync(d_rows64, rows, n * 8, hipMemcpyHostToDevice, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
     src_rows = d_rows64;
   }
   if (launch_rows_to_local(src_rows, (int64_t)n, ix->row_offset, ix->n_rows, d_rows32, s) != hipSuccess)
-    return done(set_error(DHR_ERR_HIP, "rows_to_local launch failed"));
+    return set_error(DHR_ERR_HIP, "rows_to_local launch failed");
   RescoreArgs r = base_rescore_args(ix, w, Q, gate);
   r.rows32 = d_rows32; r.ld_rows = m; r.count_all = (uint32_t)m; r.max_count = (uint32_t)m;
   r.out_scores = (mem_kind == DHR_MEM_HOST) ? d_sc : out_scores; r.ld_scores = m;
-  if (launch_rescore(r, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "rescore launch failed"));
+  if (launch_rescore(r, s) != hipSuccess) return set_error(DHR_ERR_HIP, "rescore launch failed");
   if (mem_kind == DHR_MEM_HOST && hipMemcpyAsync(out_scores, d_sc, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-    return done(set_error(DHR_ERR_HIP, "D2H failed"));
-  if (hipStreamSynchronize(s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "score_rows failed on the device"));
-  return done(DHR_OK);
+    return set_error(DHR_ERR_HIP, "D2H failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "score_rows failed on the device");
+  return DHR_OK;
 } DHR_CATCH_STATUS
 
 extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
@@ -490,22 +400,21 @@ extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * ies)));
   DevMem m_in, m_val, m_idx;
   void *&d_in = m_in.p, *&d_val = m_val.p, *&d_idx = m_idx.p;
-  auto done = [&](int code) { return code; };       // (the three DevMem release the staging buffers)
   if (dev_alloc(m_in, block * vocab * ies) != hipSuccess || dev_alloc(m_val, block * dims * oes) != hipSuccess ||
       dev_alloc(m_idx, block * dims * xes) != hipSuccess)
-    return done(set_error(DHR_ERR_HIP, "hipMalloc failed"));
+    return set_error(DHR_ERR_HIP, "hipMalloc failed");
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
-    if (copy_in(d_in, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "H2D failed"));
+    if (copy_in(d_in, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
     if (launch_densify(d_in, value_dtype == DHR_VAL_F32, vocab, rows, remove_dims, dims, n_groups, d_val, out_value_dtype == DHR_VAL_F32, dims, d_idx,
                        index_dtype == DHR_IDX_I16, dims, s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "densify launch failed"));
+      return set_error(DHR_ERR_HIP, "densify launch failed");
     if (stage_out((char*)out_value + lo * ld_value * oes, ld_value, d_val, rows, dims, oes, s) != hipSuccess ||
         stage_out((char*)out_index + lo * ld_index * xes, ld_index, d_idx, rows, dims, xes, s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "D2H failed"));
-    if (hipStreamSynchronize(s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "densify failed on the device"));
+      return set_error(DHR_ERR_HIP, "D2H failed");
+    if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "densify failed on the device");
   }
-  return done(DHR_OK);
+  return DHR_OK;
 } DHR_CATCH_STATUS
 
 // ------------------------------------------------------------------------------------------ product quantiser
@@ -569,31 +478,30 @@ extern "C" int dhr_pq_train_nbits(int32_t device, int32_t mem_kind, const void* 
   float* d_cb = (float*)cb.dev;
   DevMem m_sums, m_counts, m_err;
   float*& sums = (float*&)m_sums.p; uint32_t*& counts = (uint32_t*&)m_counts.p; float*& err = (float*&)m_err.p;
-  auto done = [&](int code) { return code; };       // (the three DevMem release the scratch)
   if (hipMalloc((void**)&sums, cb_bytes) != hipSuccess || hipMalloc((void**)&counts, (size_t)M * ksub * 4) != hipSuccess ||
       hipMalloc((void**)&err, (size_t)M * 4) != hipSuccess)
-    return done(set_error(DHR_ERR_HIP, "hipMalloc failed"));
-  if (launch_pq_init((const __half*)v.dev, v_ld, np, v_stride, dsub, M, d_cb, ksub, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "pq_init launch failed"));
+    return set_error(DHR_ERR_HIP, "hipMalloc failed");
+  if (launch_pq_init((const __half*)v.dev, v_ld, np, v_stride, dsub, M, d_cb, ksub, s) != hipSuccess) return set_error(DHR_ERR_HIP, "pq_init launch failed");
   for (int it = 0; it <= iters; ++it) {
     if (hipMemsetAsync(sums, 0, cb_bytes, s) != hipSuccess || hipMemsetAsync(counts, 0, (size_t)M * ksub * 4, s) != hipSuccess ||
         hipMemsetAsync(err, 0, (size_t)M * 4, s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "memset failed"));
+      return set_error(DHR_ERR_HIP, "memset failed");
     if (launch_pq_assign((const __half*)v.dev, v_ld, np, v_stride, dsub, M, d_cb, nullptr, 0, sums, counts, err, ksub, s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "pq_assign launch failed"));
+      return set_error(DHR_ERR_HIP, "pq_assign launch failed");
     if (it == iters) break;                               // the last pass only measures the error
-    if (launch_pq_update(d_cb, sums, counts, dsub, M, ksub, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "pq_update launch failed"));
+    if (launch_pq_update(d_cb, sums, counts, dsub, M, ksub, s) != hipSuccess) return set_error(DHR_ERR_HIP, "pq_update launch failed");
   }
   if (out_error) {
     std::vector<float> e(M);
     if (hipMemcpyAsync(e.data(), err, (size_t)M * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return done(set_error(DHR_ERR_HIP, "D2H failed"));
+      return set_error(DHR_ERR_HIP, "D2H failed");
     double t = 0;
     for (float x : e) t += x;
     *out_error = t / (double)np;
   }
-  if ((rc = cb.out(codebooks, cb_bytes, s)) != DHR_OK) return done(rc);
-  if (hipStreamSynchronize(s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "PQ training failed on the device"));
-  return done(DHR_OK);
+  if ((rc = cb.out(codebooks, cb_bytes, s)) != DHR_OK) return rc;
+  if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "PQ training failed on the device");
+  return DHR_OK;
 } DHR_CATCH_STATUS
 
 extern "C" int dhr_pq_encode(int32_t device, int32_t mem_kind, const void* values, int64_t ld, int64_t n, int32_t d, int32_t M,

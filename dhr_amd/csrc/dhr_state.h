@@ -11,9 +11,14 @@
 #include <vector>
 
 #include "dhr_internal.h"
+#include "search_plan.h"
 #include <hip/hip_ext.h>
 
 using namespace dhr;
+static_assert(plan::TILE_ROWS == TILE_ROWS && plan::DOC_GROUP == DOC_GROUP, "search_plan.h restates the tile geometry of dhr_internal.h");
+using plan::BOOT_M;
+using plan::SearchPlan;
+using plan::round_up;
 
 // the calling thread's error record lives in abi.cpp (a fixed buffer: recording a failure does not allocate)
 inline int set_error(int code, const std::string& msg) { return dhr_set_error_message(code, msg.c_str()); }
@@ -25,7 +30,6 @@ inline int set_error(int code, const std::string& msg) { return dhr_set_error_me
                                         std::to_string(__LINE__) + ")");                                       \
   } while (0)
 
-static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 // Scratch that must not outlive a call whichever way it ends -- an early `return set_error(...)`, or an exception on its way to the barrier
 // of the entry point (abi_guard.h)
 struct DevMem {
@@ -108,6 +112,13 @@ struct Workspace {
   int64_t bytes = 0;
 };
 
+// Where a handle stands in a staged search: nothing open; dhr_search_pre ran the first part of the sampled run; the sampled run is done
+// (dhr_search_begin / _begin_rest); dhr_search_mid ran the first slice of the main pass; the begin call already finished the search (the shard
+// is not sampled: only dhr_search_finish is left, to hand the result out).
+enum class StagedState { None, AfterPre, AfterBegin, AfterMid, Complete };
+// What one call of search_core runs: the whole search, or the part of it that one staged entry point stands for
+enum class Stage { Whole, Begin, Finish, Mid, Pre, BeginRest };
+
 struct dhr_index {
   int device = 0;
   int64_t n_rows = 0, n_tiles = 0, row_offset = 0;
@@ -154,7 +165,7 @@ struct dhr_index {
   int async_ctl = 2;                       // (2: + one 32-byte read after the sampled run for the chunk plan of the main pass) first attempt of a sampled search: the controller only ENQUEUES (no host read-backs between the phases; list
                                            // overflows are flagged on the device and cured by the fallback); 0 = the host-driven controller of rounds 1-2
   int sample_share = 1;                    // shards the sampled threshold is agreed between (dhr_search_sharded sets it): a shard then keeps only the part of
-                                           // the union's r best sample scores it can plausibly hold (local_sample_rank)
+                                           // the union's r best sample scores it can plausibly hold (plan::share_rank)
   int main_chunks = 2;
   int progressive_thr = 2;
   int n_cu = 256;
@@ -165,9 +176,14 @@ struct dhr_index {
   int aux_cus_made = -1, gemm_excl_made = -1;
   hipStream_t s_gemm = nullptr;         // main-pass GEMM stream when CU masks are in use
   hipStream_t s_aux = nullptr;          // non-blocking stream for rescoring/select overlapped with the main-pass GEMM
-  // staged search (dhr_search_begin / dhr_search_finish): state carried between the two calls
-  struct { bool valid = false, done = false, gate = false, mid = false, pre = false; int Q = 0, k = 0; double rate = 0.0, rate_r = 0.0; int64_t dev_bound = 0, dev_exact = 0;
-           int64_t pre_pos = 0, pre_seen = 0, pre_last_rows = 0; } pend;   // mid: dhr_search_mid ran the first slice of the main pass; pre: dhr_search_pre ran the first part of the sampled run (sample positions [0, pre_pos), pre_seen rows)
+  // staged search (dhr_search_pre / _begin / _begin_rest / _mid / _finish): where the handle stands, and what the next call resumes from
+  struct {
+    StagedState state = StagedState::None;       // (set through staged_set / staged_open only)
+    bool gate = false; int Q = 0, k = 0;                          // the batch the staged search was opened with
+    double rate = 0.0, rate_r = 0.0;                              // AfterBegin: fullest bound / survivor list per corpus row of the last sampled phase
+    int64_t dev_bound = 0, dev_exact = 0;                         // device counters already folded into the handle's stats (fold_device_counters, api.hip)
+    int64_t pre_pos = 0, pre_seen = 0, pre_last_rows = 0;         // AfterPre: sample positions [0, pre_pos) are done, pre_seen rows; rows of the last phase
+  } pend;
   Workspace ws, ws_fb[2];              // ws_fb[d]: workspace of fallback depth d+1 (16x candidate capacity)
   void* sh_arena = nullptr;            // grow-only scratch of dhr_search_sharded_local (sharded.hip): the gathered blocks of a step, kept between steps
   size_t sh_arena_bytes = 0;
@@ -188,7 +204,6 @@ inline void free_ws(Workspace& w) {
 
 
 // ---- search_core.hip
-constexpr int BOOT_M = 64;       // most rows the threshold bootstrap rescores per query
 constexpr int32_t MEM_DEVICE_PADDED = 2;      // internal sub-batches (the queries a fallback redoes) come from the library's own padded copies (dhr_index::dlr_pad)
 #ifndef SELECT_SORT_Q
 #define SELECT_SORT_Q 8       // LDS keys of select_kernel in quarters of kp: the list + one round of up to kp new keys (16 until round 5: 32 KB for top-1000 held a CU at 5 workgroups)
@@ -230,12 +245,18 @@ int check_queries(const dhr_index* ix, const dhr_query_batch* qb);
 int grow(void*& p, size_t& have, size_t need, int64_t& total);
 int prep_queries(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, hipStream_t s);
 dhr::RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_queries, bool gate);
-int adaptive_rank(int r, double phi);
-void plan_sampling(const dhr_index* ix, int k, int& S, int& r);
-int local_sample_rank(const dhr_index* ix, int r);
-int64_t pre_positions(int64_t n_sample);
-int mid_share16();
-int64_t head_rows(const dhr_index* ix, int S, int r_eff);
-// Leaves the sorted top-k keys of every query in w.topk_keys.  stage 0: whole search; 1 dhr_search_begin; 2 dhr_search_finish; 3 dhr_search_mid; 4 dhr_search_pre; 5 dhr_search_begin_rest
-int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, int depth, Timer& tm, dhr_search_stats& st, hipStream_t s, int stage = 0,
-                const float* tau_ext = nullptr);
+// The plan of a search of this handle for k rows (search_plan.h).  staged: a staged call or a rank query -- the handle chases its share of the
+// union's rank; a whole search (the repair dhr_search inside a sharded step among them) chases the rank itself.
+inline SearchPlan search_plan_of(const dhr_index* ix, int k, int depth, bool staged) {
+  plan::PlanInput in;
+  in.n_rows = ix->n_rows; in.n_tiles = ix->n_tiles; in.k = k; in.sample_period = ix->sample_period; in.sample_share = ix->sample_share;
+  in.first_rows = ix->first_rows; in.depth = depth; in.staged = staged;
+  return plan::make_search_plan(in);
+}
+// The ONE place that moves a handle through the staged search (api.hip: staged_call closes it when an entry point fails)
+inline void staged_set(dhr_index* ix, StagedState to) { ix->pend.state = to; }
+inline void staged_open(dhr_index* ix, StagedState to, bool gate, int Q, int k) { staged_set(ix, to); ix->pend.gate = gate; ix->pend.Q = Q; ix->pend.k = k; }
+// Leaves the sorted top-k keys of every query in w.topk_keys.  qb: the batch of a call that brings one (Whole, Begin, Pre), validated; tau_ext:
+// the thresholds the shards agreed on, device [Q] (Finish, Mid, BeginRest).
+int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, int depth, Timer& tm, dhr_search_stats& st, hipStream_t s,
+                Stage stage = Stage::Whole, const float* tau_ext = nullptr);

@@ -7,6 +7,9 @@
 // tau (exact k-th best so far) never exceeds the final k-th best and U >= exact score, so no row of
 // the true top-k is ever dropped; chunk sizes adapt to the observed candidate counts, and a phase
 // whose candidate list overflowed is re-run in halves (a chunk of <= cap rows cannot overflow).
+// Layout: the geometry of a search comes from ONE plan (search_plan.h; the rank queries of api.hip read the same);
+// search_core(..., Stage) runs the whole search or one staged entry point's part of it (what a later call resumes from: dhr_index::pend), as a
+// driver over prepare_and_phase0 -> sampled_run | adopt_thresholds -> main_pass -> verify_and_redo; one phase: stream_phases -> gemm_phase -> rescore_select[_async].
 #include "dhr_state.h"
 
 // ------------------------------------------------------------------------------------------ workspace
@@ -228,7 +231,7 @@ int prep_queries(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, hipStre
   return DHR_OK;
 }
 
-
+// ------------------------------------------------------------------------------------------ argument structs
 // The refine step serves gated batches, and -- on gated_i8 indexes -- ungated ones too (--IP stage 1): there it takes the int8
 // products of a row's listed entries off the bound and puts their real products back, whatever the index values (RefineArgs::ungated).
 static inline bool uses_refine(const dhr_index* ix, bool gate) { return (ix->heavy_key != nullptr && (gate || ix->gated_i8)) || ix->resid8 != nullptr; }
@@ -240,62 +243,93 @@ RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_que
   r.n_rows = ix->n_rows; r.n_queries = n_queries; r.gate = gate ? 1 : 0;
   return r;
 }
-
-// One bound-GEMM launch over sequence positions [lo,hi) + candidate statistics read back.
-static int gemm_phase(dhr_index* ix, Workspace& w, int Q, int64_t lo, int64_t hi, int map_mode, int period, int64_t head,
-                      Timer& tm, dhr_search_stats& st, hipStream_t s, uint32_t* maxc, unsigned long long* sumc) {
+// What every bound-GEMM launch of a search shares -- the operands of both sides, the geometry, the depth of the uniform lists; the caller adds the
+// tile range and its mapping, the thresholds and the list set
+static GemmArgs base_gemm_args(const dhr_index* ix, const Workspace& w, int Q) {
   GemmArgs g{};
-  g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.k_split = ix->d_dlr / TILE_K; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant; g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum;
-  g.seq_lo = lo; g.seq_hi = hi; g.map_mode = map_mode; g.period = period; g.head = head; g.n_tiles = ix->n_tiles;
-  g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows; g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
-  g.cap = (uint32_t)w.cap; g.n_queries = Q;
-  HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)w.q_pad * 4, s));
-  HIP_TRY(hipMemsetAsync(w.d_max, 0, 16, s));
-  tm.begin(T_GEMM); HIP_TRY(launch_gemm_filter(g, s)); tm.end();
-  ix->last_gemm_kernel = g_last_gemm_kernel;
-  HIP_TRY(launch_max_u32(w.cnt, Q, w.d_max, (unsigned long long*)(w.d_max + 2), s));
-  HIP_TRY(hipMemcpyAsync(w.h_pinned, w.d_max, 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *maxc = ((uint32_t*)w.h_pinned)[0];
-  memcpy(sumc, (uint32_t*)w.h_pinned + 2, 8);
-  const double rows = (double)(hi - lo) * TILE_ROWS;
-  st.phases++;
-  st.gemm_rows += (int64_t)rows;
-  st.gemm_flops += 2.0 * (double)w.q_pad * rows * (double)ix->kt;
-  st.gemm_flops_alg += 2.0 * (double)Q * rows * (double)ix->k;
-  return DHR_OK;
+  g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.k_split = ix->d_dlr / TILE_K; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant;
+  g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum;
+  g.n_tiles = ix->n_tiles; g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows; g.cap = (uint32_t)w.cap; g.n_queries = Q;
+  return g;
+}
+// ... and every refine launch: bound lists of depth w.cap filtered at thr into the survivor lists; the caller adds the list set and the launch geometry
+static RefineArgs base_refine_args(const dhr_index* ix, const Workspace& w, int Q, bool gate, const float* thr) {
+  RefineArgs f{};
+  f.cap = (uint32_t)w.cap; f.heavy_key = ix->heavy_key; f.heavy_val = ix->heavy_val;
+  f.q_pack = w.q_pack; f.d_dlr = ix->d_dlr; f.thr = thr; f.out = w.cand_r; f.out_cnt = w.cnt_r; f.out_cap = (uint32_t)w.cap_r;
+  f.n_queries = Q;
+  if (ix->gated_i8) { f.g8_q8 = w.g8_q8; f.g8_inv_cs = ix->g8_inv_cs; f.g8_unit = w.g8_unit; f.abs_mode = ix->abs_mode ? 1 : 0; f.ungated = gate ? 0 : 1; }
+  if (ix->resid8) { f.resid8 = ix->resid8; f.resid_ld = ix->resid_ld; f.q32 = w.q32; f.q32_ld = ix->k_rm; f.col_scale = ix->i8_col_scale; f.d_cls = ix->d_cls; f.thr_raise = w.thr_raise; }
+  return f;
 }
 
-// The same without a host read-back (controller of the first attempt of a sampled search): list lengths stay in device memory -- the
-// statistics are accumulated there (w.d_stats), a list that overflowed flags its query (fail_flags: redone by the fallback), and the
-// per-candidate kernels are launched with a fixed grid that walks the block list by grid stride.
-static uint32_t async_grid() {
-  return FLAT_GRID_ASYNC;
+// ------------------------------------------------------------------------------------------ one phase
+// One call of search_core: what its steps share
+struct Search {
+  dhr_index* ix; Workspace& w; Timer& tm; dhr_search_stats& st; hipStream_t s;
+  Stage stage; int depth, k; const float* tau_ext;
+  int Q = 0;
+  bool gate = false;
+  bool after_mid = false;          // Finish behind a dhr_search_mid: chunk 0 of the main pass is done, the thresholds are those of the second agreement
+  bool async_ctl = false;          // the controller only enqueues (no host read-backs between the phases)
+  SearchPlan p;
+  SelectArgs sel{};
+  double rate = 0.0, rate_r = 0.0; // fullest bound / survivor list per corpus row at the thresholds of the last sampled phase (0: not known)
+  bool whole() const { return stage == Stage::Whole; }                                  // not a staged call: extrapolated thresholds, read-back for the chunk plan, local verification
+  bool fresh() const { return whole() || stage == Stage::Begin || stage == Stage::Pre; }   // the call brings the query batch (else: resumed from ix->pend)
+};
+
+static void count_gemm(const Search& c, int64_t tiles) {
+  const double rows = (double)tiles * TILE_ROWS;
+  c.st.phases++;
+  c.st.gemm_rows += (int64_t)rows;
+  c.st.gemm_flops += 2.0 * (double)c.w.q_pad * rows * (double)c.ix->kt;
+  c.st.gemm_flops_alg += 2.0 * (double)c.Q * rows * (double)c.ix->k;
 }
-static int gemm_phase_async(dhr_index* ix, Workspace& w, int Q, int64_t lo, int64_t hi, int map_mode, int period, int64_t head,
-                            Timer& tm, dhr_search_stats& st, hipStream_t s) {
-  GemmArgs g{};
-  if (w.arena > 0) g.tier = w.tier_dev;      // two-tier lists: planned by the caller (stream_phases)
-  g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.k_split = ix->d_dlr / TILE_K; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant; g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum;
-  g.seq_lo = lo; g.seq_hi = hi; g.map_mode = map_mode; g.period = period; g.head = head; g.n_tiles = ix->n_tiles;
-  g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows; g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
-  g.cap = (uint32_t)w.cap; g.n_queries = Q;
+
+// One bound-GEMM launch over sequence positions [lo,hi) of the head-and-sample order.  Host-driven controller: + candidate statistics read back.
+// enqueue_only (controller of the first attempt of a sampled search): list lengths stay in device memory -- the statistics are accumulated
+// there (w.d_stats), a list that overflowed flags its query (fail_flags: redone by the fallback), and the per-candidate kernels are launched
+// with a fixed grid that walks the block list by grid stride (list statistics + overflow marks: rescore_select_async, one launch).
+static int gemm_phase(Search& c, int64_t lo, int64_t hi, int period, bool enqueue_only, uint32_t* maxc, unsigned long long* sumc) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; hipStream_t s = c.s;
+  GemmArgs g = base_gemm_args(ix, w, c.Q);
+  if (enqueue_only && w.arena > 0) g.tier = w.tier_dev;      // two-tier lists: planned by the caller (stream_phases)
+  g.seq_lo = lo; g.seq_hi = hi; g.map_mode = 1; g.period = period; g.head = c.p.head;
+  g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
   HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)w.q_pad * 4, s));
-  tm.begin(T_GEMM); HIP_TRY(launch_gemm_filter(g, s)); tm.end();      // (list statistics + overflow marks: rescore_select_async, one launch)
+  if (!enqueue_only) HIP_TRY(hipMemsetAsync(w.d_max, 0, 16, s));
+  c.tm.begin(T_GEMM); HIP_TRY(launch_gemm_filter(g, s)); c.tm.end();
   ix->last_gemm_kernel = g_last_gemm_kernel;
-  const double rows = (double)(hi - lo) * TILE_ROWS;
-  st.phases++;
-  st.gemm_rows += (int64_t)rows;
-  st.gemm_flops += 2.0 * (double)w.q_pad * rows * (double)ix->kt;
-  st.gemm_flops_alg += 2.0 * (double)Q * rows * (double)ix->k;
+  if (!enqueue_only) {
+    HIP_TRY(launch_max_u32(w.cnt, c.Q, w.d_max, (unsigned long long*)(w.d_max + 2), s));
+    HIP_TRY(hipMemcpyAsync(w.h_pinned, w.d_max, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *maxc = ((uint32_t*)w.h_pinned)[0];
+    memcpy(sumc, (uint32_t*)w.h_pinned + 2, 8);
+  }
+  count_gemm(c, hi - lo);
   return DHR_OK;
 }
+// Exact rescoring of the listed candidates (at most max_count per query, flat_blocks workgroups) and their merge into the running top-k
+static int rescore_and_select(Search& c, const uint2* cand, const uint32_t* cnt, uint32_t list_cap, uint32_t max_count, uint32_t flat_blocks, hipStream_t s) {
+  Workspace& w = c.w;
+  RescoreArgs r = base_rescore_args(c.ix, w, c.Q, c.gate);
+  r.cand = cand; r.cnt = cnt; r.cap = list_cap; r.max_count = max_count;
+  r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
+  r.blk_off = w.blk_off + w.q_pad + 1; r.flat_blocks = flat_blocks;
+  c.tm.begin_on(T_RESCORE, s); HIP_TRY(launch_rescore(r, s)); c.tm.end_on(s);
+  c.sel.cnt = cnt; c.sel.count_all = 0; c.sel.cap = list_cap;
+  c.tm.begin_on(T_SELECT, s); HIP_TRY(launch_select(c.sel, s)); c.tm.end_on(s);
+  return DHR_OK;
+}
+// Candidates of one phase -> [refine] -> exact rescoring -> top-k merge on `s`, without a host read-back.
 // (d_fullest_bound / d_fullest: where the length of the fullest bound / survivor list of this phase is stored, or nullptr)
-static int rescore_select_async(dhr_index* ix, Workspace& w, int Q, bool gate, SelectArgs& sel, const uint2* cand, const uint32_t* cnt,
-                                const float* thr, Timer& tm, hipStream_t s, uint32_t* d_fullest_bound = nullptr, uint32_t* d_fullest = nullptr,
-                                const uint2* ovf = nullptr) {
+static int rescore_select_async(Search& c, const uint2* cand, const uint32_t* cnt, const float* thr, hipStream_t s, uint32_t* d_fullest_bound = nullptr,
+                                uint32_t* d_fullest = nullptr, const uint2* ovf = nullptr) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; Timer& tm = c.tm; const int Q = c.Q;
   uint32_t list_cap = (uint32_t)w.cap;
-  const bool refine = uses_refine(ix, gate);
+  const bool refine = uses_refine(ix, c.gate);
   if (!refine) ovf = nullptr;                    // (the second tier exists for lists a refine level reads, ensure_ws)
   const uint32_t* ovf_cap = ovf ? w.ovf_cap : nullptr;
   // the bound lists: statistics, overflow marks, block offsets of the kernel that walks them and (refine) the survivor counters cleared
@@ -303,46 +337,31 @@ static int rescore_select_async(dhr_index* ix, Workspace& w, int Q, bool gate, S
                              d_fullest_bound, refine ? nullptr : d_fullest, w.d_stats + 0, refine ? nullptr : w.d_stats + 1, w.fail_flags,
                              refine ? w.cnt_r : nullptr, refine ? (int)w.q_pad : 0, s, ovf_cap));
   if (refine) {
-    RefineArgs f{};
+    RefineArgs f = base_refine_args(ix, w, Q, c.gate, thr);
     f.ovf = ovf; f.ovf_off = ovf ? w.ovf_off : nullptr; f.ovf_cap = ovf_cap;
-    f.cand = cand; f.cnt = cnt; f.cap = (uint32_t)w.cap; f.heavy_key = ix->heavy_key; f.heavy_val = ix->heavy_val;
-    f.q_pack = w.q_pack; f.d_dlr = ix->d_dlr; f.thr = thr; f.out = w.cand_r; f.out_cnt = w.cnt_r; f.out_cap = (uint32_t)w.cap_r;
-    f.n_queries = Q; f.max_count = 1;
-    if (ix->gated_i8) { f.g8_q8 = w.g8_q8; f.g8_inv_cs = ix->g8_inv_cs; f.g8_unit = w.g8_unit; f.abs_mode = ix->abs_mode ? 1 : 0; f.ungated = gate ? 0 : 1; }
-    if (ix->resid8) { f.resid8 = ix->resid8; f.resid_ld = ix->resid_ld; f.q32 = w.q32; f.q32_ld = ix->k_rm; f.col_scale = ix->i8_col_scale; f.d_cls = ix->d_cls; f.thr_raise = w.thr_raise; }
-    f.blk_off = w.blk_off; f.flat_blocks = async_grid();
+    f.cand = cand; f.cnt = cnt; f.max_count = 1;
+    f.blk_off = w.blk_off; f.flat_blocks = FLAT_GRID_ASYNC;
     tm.begin_on(T_REFINE, s); HIP_TRY(launch_refine(f, s)); tm.end_on(s);
     list_cap = (uint32_t)w.cap_r;
     cand = w.cand_r; cnt = w.cnt_r;
     HIP_TRY(launch_lists_ready(cnt, list_cap, Q, (uint32_t)RESCORE_CANDS_PER_WG, w.blk_off + w.q_pad + 1, d_fullest, nullptr, w.d_stats + 1,
                                nullptr, w.fail_flags, nullptr, 0, s));
   }
-  RescoreArgs r = base_rescore_args(ix, w, Q, gate);
-  r.cand = cand; r.cnt = cnt; r.cap = list_cap; r.max_count = 1;
-  r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
-  r.blk_off = w.blk_off + w.q_pad + 1; r.flat_blocks = async_grid();
-  tm.begin_on(T_RESCORE, s); HIP_TRY(launch_rescore(r, s)); tm.end_on(s);
-  sel.cnt = cnt; sel.count_all = 0; sel.cap = list_cap;
-  tm.begin_on(T_SELECT, s); HIP_TRY(launch_select(sel, s)); tm.end_on(s);
-  return DHR_OK;
+  return rescore_and_select(c, cand, cnt, list_cap, 1, FLAT_GRID_ASYNC, s);
 }
-
-// Candidates of one phase -> [refine on the heavy lists] -> exact rescoring -> top-k merge, all on `s`.
-// The refine step needs one host read-back (size of the surviving lists) to size the rescoring grid.
-static int rescore_select(dhr_index* ix, Workspace& w, int Q, bool gate, SelectArgs& sel, const uint2* cand,
-                          const uint32_t* cnt, const float* thr, uint32_t maxc, Timer& tm, dhr_search_stats& st,
-                          hipStream_t s, int64_t bound_sum, uint32_t* fail_flags) {
+// The same for the host-driven controller, which sizes every launch from the list lengths it read back (maxc, bound_sum).
+// The refine step needs one more read-back (size of the surviving lists) to size the rescoring grid.
+// fail_flags: where a survivor list that overflowed flags its query; nullptr (streaming controller): return 1, the caller redoes the chunk in halves.
+static int rescore_select(Search& c, const uint2* cand, const uint32_t* cnt, const float* thr, uint32_t maxc, hipStream_t s, int64_t bound_sum,
+                          uint32_t* fail_flags) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; Timer& tm = c.tm; const int Q = c.Q;
   uint32_t maxr = std::min<uint32_t>(maxc, (uint32_t)w.cap);
   if (maxr == 0) return DHR_OK;
   int64_t exact = bound_sum;
   uint32_t list_cap = (uint32_t)w.cap;
-  if (uses_refine(ix, gate)) {
-    RefineArgs f{};
-    f.cand = cand; f.cnt = cnt; f.cap = (uint32_t)w.cap; f.heavy_key = ix->heavy_key; f.heavy_val = ix->heavy_val;
-    f.q_pack = w.q_pack; f.d_dlr = ix->d_dlr; f.thr = thr; f.out = w.cand_r; f.out_cnt = w.cnt_r; f.out_cap = (uint32_t)w.cap_r;
-    f.n_queries = Q; f.max_count = maxr;
-    if (ix->gated_i8) { f.g8_q8 = w.g8_q8; f.g8_inv_cs = ix->g8_inv_cs; f.g8_unit = w.g8_unit; f.abs_mode = ix->abs_mode ? 1 : 0; f.ungated = gate ? 0 : 1; }
-    if (ix->resid8) { f.resid8 = ix->resid8; f.resid_ld = ix->resid_ld; f.q32 = w.q32; f.q32_ld = ix->k_rm; f.col_scale = ix->i8_col_scale; f.d_cls = ix->d_cls; f.thr_raise = w.thr_raise; }
+  if (uses_refine(ix, c.gate)) {
+    RefineArgs f = base_refine_args(ix, w, Q, c.gate, thr);
+    f.cand = cand; f.cnt = cnt; f.max_count = maxr;
     // flat launch: one workgroup per REAL block of 256 candidates (bound_sum / 256 + Q is an upper bound of their number)
     HIP_TRY(launch_block_offsets(cnt, (uint32_t)w.cap, Q, REFINE_PER_WG, w.blk_off, s));
     f.blk_off = w.blk_off; f.flat_blocks = (uint32_t)std::min<int64_t>(bound_sum / REFINE_PER_WG + Q, (int64_t)0x7fffffff);
@@ -364,73 +383,60 @@ static int rescore_select(dhr_index* ix, Workspace& w, int Q, bool gate, SelectA
     exact = (int64_t)sum;
     cand = w.cand_r; cnt = w.cnt_r;
   }
-  st.candidates_exact += exact;
+  c.st.candidates_exact += exact;
   if (getenv("DHR_DEBUG_PLAN"))
     fprintf(stderr, "[dhr]   lists: bound %.0f per query (fullest %u) -> exact %.0f per query (fullest %u)\n", (double)bound_sum / Q, maxc, (double)exact / Q, maxr);
   if (maxr == 0) return DHR_OK;
-  RescoreArgs r = base_rescore_args(ix, w, Q, gate);
-  r.cand = cand; r.cnt = cnt; r.cap = list_cap; r.max_count = maxr;
-  r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
   HIP_TRY(launch_block_offsets(cnt, list_cap, Q, RESCORE_CANDS_PER_WG, w.blk_off + w.q_pad + 1, s));
-  r.blk_off = w.blk_off + w.q_pad + 1; r.flat_blocks = (uint32_t)std::min<int64_t>(exact / RESCORE_CANDS_PER_WG + Q, (int64_t)0x7fffffff);
-  tm.begin_on(T_RESCORE, s); HIP_TRY(launch_rescore(r, s)); tm.end_on(s);
-  sel.cnt = cnt; sel.count_all = 0; sel.cap = list_cap;
-  tm.begin_on(T_SELECT, s); HIP_TRY(launch_select(sel, s)); tm.end_on(s);
-  return DHR_OK;
+  return rescore_and_select(c, cand, cnt, list_cap, maxr, (uint32_t)std::min<int64_t>(exact / RESCORE_CANDS_PER_WG + Q, (int64_t)0x7fffffff), s);
 }
 
-// Streaming phases over a tile sequence with growing chunks (exact for any input: tau only ever
-// comes from exact scores already seen, overflowing chunks are re-run in halves).
-// Rank that defines the threshold of a sampled run after a fraction phi of the sample has been seen.  The run's goal is the r-th best
-// score of the WHOLE sample; of the sample's r best rows a scattered fraction phi holds r phi +- sqrt(r phi (1 - phi)), so the
-// (r phi + 6 sigma + 4)-th best seen lies below the sample's final r-th best except with negligible probability (Poisson tail < 1e-8 per
-// check at every phi; a query for which it does not fails the final verification -- thresholds only ever rise, tau_hat is their maximum --
-// and is redone).  With the fixed rank r of rounds 1-3 every phase of the sampled run let ~r x (rows of the phase / rows seen) x the
-// bound's amplification through: 1 400 of the 4 340 exact rescorings per query of a config-3 step were spent finding the 64 best of
-// the 1/32 sample.
-int adaptive_rank(int r, double phi) {
-  if (!(phi < 1.0)) return r;
-  if (phi < 0.0) phi = 0.0;
-  const double m = (double)r * phi;
-  return std::max(1, std::min(r, (int)std::ceil(m + 6.0 * std::sqrt(m * (1.0 - phi)) + 4.0)));
-}
-
-static int stream_phases(dhr_index* ix, Workspace& w, int Q, bool gate, SelectArgs& sel, int64_t n_seq, int map_mode,
-                         int period, int64_t head, int64_t first_chunk, int64_t seen_rows, Timer& tm, dhr_search_stats& st,
-                         hipStream_t s, double* last_rate = nullptr, double* last_rate_r = nullptr, bool async_ctl = false,
-                         int64_t* last_rows = nullptr, int rank_target = 0, int64_t rank_rows = 0, int64_t pos0 = 0, int growth16 = 0, int64_t prev_rows0 = 0) {
-  if (growth16 <= 0) growth16 = ix->max_growth16;
-  int64_t pos = pos0;          // (pos0 > 0: the run resumes behind a part another call streamed -- dhr_search_begin_rest)
-  int64_t prev_rows = prev_rows0;      // rows of the phase whose list lengths w.cnt still holds (the second list tier of the next phase is planned from them)
+// Streaming phases over the head-and-sample order (period 1: every tile behind the head) with growing chunks (exact for any input: tau only
+// ever comes from exact scores already seen, overflowing chunks are re-run in halves).
+struct StreamOpts {
+  bool async_ctl = false;                 // enqueue only: an overflowing list flags its query instead of halving the chunk
+  double *last_rate = nullptr, *last_rate_r = nullptr;      // host-driven: fullest bound / survivor list per corpus row of the last phase
+  int64_t* last_rows = nullptr;           // enqueue only: rows of the last phase
+  int rank_target = 0;                    // sampled run: the rank of the threshold grows to this over rank_rows rows (adaptive_rank)
+  int64_t rank_rows = 0;
+  int64_t pos0 = 0;                       // the run resumes behind a part another call streamed (dhr_search_begin_rest) ...
+  int64_t prev_rows0 = 0;                 // ... whose last phase covered this many rows (w.cnt still holds its list lengths)
+  int growth16 = 0;                       // (next chunk) / (rows seen) in 1/16ths at most; 0: DHR_PARAM_MAX_GROWTH
+};
+static int stream_phases(Search& c, int64_t n_seq, int period, int64_t first_chunk, int64_t seen_rows, const StreamOpts& o = {}) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; dhr_search_stats& st = c.st; const int Q = c.Q;
+  const int growth16 = o.growth16 > 0 ? o.growth16 : ix->max_growth16;
+  int64_t pos = o.pos0;
+  int64_t prev_rows = o.prev_rows0;      // rows of the phase whose list lengths w.cnt still holds (the second list tier of the next phase is planned from them)
   int64_t chunk = std::max<int64_t>(DOC_GROUP, first_chunk);
   while (pos < n_seq) {
     chunk = std::min(chunk, round_up(n_seq - pos, DOC_GROUP));
     const int64_t hi = std::min(pos + chunk, n_seq);
-    if (rank_target > 0) {        // sampled run: the rank grows with the fraction of the sample seen once this phase is merged
-      sel.k = adaptive_rank(rank_target, (double)(seen_rows + (hi - pos) * TILE_ROWS) / (double)std::max<int64_t>(rank_rows, 1));
-      sel.monotone = 1;
+    const int64_t chunk_rows = (hi - pos) * TILE_ROWS;
+    if (o.rank_target > 0) {        // sampled run: the rank grows with the fraction of the sample seen once this phase is merged
+      c.sel.k = plan::adaptive_rank(o.rank_target, (double)(seen_rows + chunk_rows) / (double)std::max<int64_t>(o.rank_rows, 1));
+      c.sel.monotone = 1;
     }
-    if (async_ctl) {          // enqueue only: an overflowing list flags its query instead of halving the chunk
+    if (o.async_ctl) {
       // two-tier lists: the second tier of this phase from the list lengths of the previous one (w.cnt still holds them; none for the first)
       if (w.arena > 0)
-        HIP_TRY(launch_plan_overflow(prev_rows > 0 ? w.cnt : nullptr, prev_rows > 0 ? (double)((hi - pos) * TILE_ROWS) / (double)prev_rows : 0.0, (uint32_t)w.cap,
-                                     (uint32_t)(w.cap_deep - w.cap), (uint32_t)w.arena, Q, w.ovf_off, w.ovf_cap, s));
-      // (d_max2: {fullest bound list, -, -, -, fullest survivor list} of the latest phase -- what the chunk plan of the main pass reads)
-      int rc = gemm_phase_async(ix, w, Q, pos, hi, map_mode, period, head, tm, st, s);
+        HIP_TRY(launch_plan_overflow(prev_rows > 0 ? w.cnt : nullptr, prev_rows > 0 ? (double)chunk_rows / (double)prev_rows : 0.0, (uint32_t)w.cap,
+                                     (uint32_t)(w.cap_deep - w.cap), (uint32_t)w.arena, Q, w.ovf_off, w.ovf_cap, c.s));
+      int rc = gemm_phase(c, pos, hi, period, true, nullptr, nullptr);
       if (rc) return rc;
-      if ((rc = rescore_select_async(ix, w, Q, gate, sel, w.cand, w.cnt, w.thr, tm, s, w.d_max2, w.d_max2 + 4, w.arena > 0 ? w.ovf : nullptr)) != DHR_OK) return rc;
-      prev_rows = (hi - pos) * TILE_ROWS;
-      if (last_rows) *last_rows = (hi - pos) * TILE_ROWS;
-      seen_rows += (hi - pos) * TILE_ROWS;
+      // (d_max2: {fullest bound list, -, -, -, fullest survivor list} of the latest phase -- what the chunk plan of the main pass reads)
+      if ((rc = rescore_select_async(c, w.cand, w.cnt, w.thr, c.s, w.d_max2, w.d_max2 + 4, w.arena > 0 ? w.ovf : nullptr)) != DHR_OK) return rc;
+      prev_rows = chunk_rows;
+      if (o.last_rows) *o.last_rows = chunk_rows;
+      seen_rows += chunk_rows;
       pos = hi;
       chunk = std::max<int64_t>(DOC_GROUP, round_up(seen_rows * growth16 / 16 / TILE_ROWS, DOC_GROUP));
       continue;
     }
     uint32_t maxc; unsigned long long sumc;
-    int rc = gemm_phase(ix, w, Q, pos, hi, map_mode, period, head, tm, st, s, &maxc, &sumc);
+    int rc = gemm_phase(c, pos, hi, period, false, &maxc, &sumc);
     if (rc) return rc;
     if (getenv("DHR_DEBUG_PLAN")) fprintf(stderr, "[dhr] stream phase: tiles [%lld, %lld) of %lld (period %d)\n", (long long)pos, (long long)hi, (long long)n_seq, period);
-    const int64_t chunk_rows = (hi - pos) * TILE_ROWS;
     if (maxc > w.cap && chunk > DOC_GROUP) {               // overflow: redo this chunk in halves
       st.overflow_retries++;
       chunk = std::max<int64_t>(DOC_GROUP, round_up(chunk / 2, DOC_GROUP));
@@ -439,15 +445,15 @@ static int stream_phases(dhr_index* ix, Workspace& w, int Q, bool gate, SelectAr
     // (cannot happen: every list depth the workspace plans holds the rows of a minimum chunk -- ensure_ws, DHR_PARAM_CAND_CAP / _LIST_STRIDE >= 1024)
     if (maxc > w.cap) return set_error(DHR_ERR_INTERNAL, "bound list overflow at the minimum chunk size");
     st.candidates_bound += (int64_t)sumc;
-    if (last_rate) *last_rate = (double)maxc / (double)chunk_rows;      // fullest list per corpus row, at the latest thresholds
-    rc = rescore_select(ix, w, Q, gate, sel, w.cand, w.cnt, w.thr, maxc, tm, st, s, (int64_t)sumc, nullptr);
+    if (o.last_rate) *o.last_rate = (double)maxc / (double)chunk_rows;      // fullest list per corpus row, at the latest thresholds
+    rc = rescore_select(c, w.cand, w.cnt, w.thr, maxc, c.s, (int64_t)sumc, nullptr);
     if (rc == 1 && chunk > DOC_GROUP) {                    // survivor lists overflowed: same cure as a bound-list overflow
       st.overflow_retries++;
       chunk = std::max<int64_t>(DOC_GROUP, round_up(chunk / 2, DOC_GROUP));
       continue;
     }
     if (rc != DHR_OK) return rc < 0 ? rc : set_error(DHR_ERR_INTERNAL, "survivor list overflow at the minimum chunk size");
-    if (last_rate_r) *last_rate_r = (uses_refine(ix, gate) && maxc > 0) ? (double)w.last_maxr / (double)chunk_rows : 0.0;   // fullest SURVIVOR list per corpus row
+    if (o.last_rate_r) *o.last_rate_r = (uses_refine(ix, c.gate) && maxc > 0) ? (double)w.last_maxr / (double)chunk_rows : 0.0;   // fullest SURVIVOR list per corpus row
     pos = hi;
     seen_rows += chunk_rows;
     // next chunk: aim at cap/4 candidates for the fullest query, never more than growth * rows seen
@@ -459,470 +465,362 @@ static int stream_phases(dhr_index* ix, Workspace& w, int Q, bool gate, SelectAr
   return DHR_OK;
 }
 
-// Leaves the sorted top-k keys of every query in w.topk_keys.  qb must already be validated.
-// stage 3 (dhr_search_mid): the first slice of the main pass with the caller's thresholds, then stop -- dhr_search_finish resumes behind it with
-// the thresholds the shards agree on from what they have seen by then.
-// stage 0: whole search.  stage 1 (dhr_search_begin): stop after the sampled run.  stage 2 (dhr_search_finish):
-// resume at the main pass with the caller's thresholds tau_ext (device [Q]); no local verification.
-// Conservative rank of the sampled threshold: the k/S top rows a 1/S sample holds on average + 5 sigma + 4 (4 sigma until round 2:
-// one query in ~50 000 then saw its sample hold 58 rows above a score that fewer than k rows of the corpus reach, and a failed
-// query costs extra passes over the corpus for its whole query tile; the extrapolated thresholds make the looser start cheap).
-static int sample_rank_of(double mean) { return (int)std::ceil(mean + 5.0 * std::sqrt(mean) + 4.0); }
-
-// Sample period and rank for this index and k: the configured period, halved (32 -> 16 -> 8 -> 4) while the corpus is too small for it
-// -- the sample must span >= 32 tiles and hold >= 16 r rows, and r must stay below k; S = 0 (r = k): no sampling, plain streaming.
-// (Until round 2 a corpus below ~270 k rows was never sampled: the 100 k-row config 1 rescored 8.7 k rows per query, most of them while
-// the streaming thresholds were still warming up.)
-void plan_sampling(const dhr_index* ix, int k, int& S, int& r) {
-  for (S = ix->sample_period; S >= 2; S = S >= 8 ? S / 2 : 0) {
-    const int rr = sample_rank_of((double)k / S);
-    const int64_t head_guess = round_up(std::max<int64_t>(256, 2 * (int64_t)rr), TILE_ROWS) / TILE_ROWS;
-    const int64_t rest_guess = ix->n_tiles - head_guess;
-    if (!(rr >= k || rest_guess < 32 * (int64_t)S || (rest_guess / S) * TILE_ROWS < 16 * (int64_t)rr)) { r = rr; return; }
-  }
-  S = 0; r = k;
-}
-
-// Sharded search: the common threshold is the r-th best sample score of the UNION of the shards' samples.  A shard's share of those r
-// scores is ~Binomial(r, 1 / shards), so it only has to report (and, during its sampled run, to chase) its
-// r / shards + 5 sqrt(r / shards) + 4 best: 26 instead of 64 at 8 shards.  A longer share than that only makes the union's r-th best
-// come out LOWER (still a valid threshold, the verification of the counts catches what it costs).
-int local_sample_rank(const dhr_index* ix, int r) {
-  if (ix->sample_share <= 1 || r <= 0) return r;
-  const double m = (double)r / ix->sample_share;
-  return std::min(r, (int)std::ceil(m + 5.0 * std::sqrt(m) + 4.0));
-}
-
-// Share of the main pass that dhr_search_mid runs before the shards agree on thresholds a second time, in 1/16ths (default 2 = 1/8: with the
-// 1/32 sample the shards have then seen ~15 % of their rows)
-// Share of the SAMPLE that dhr_search_pre streams before the shards agree on a first common threshold, in 1/16ths (default 2 = 1/8), and the
-// sample positions that is (whole tile groups; 0: the sample is too small to split)
-// (round 6 swept both shares on the emulated 8-shard step -- pre 2 / 4, mid 1 / 2 / 3 sixteenths, one phase or two for the first part, sample
-// period 16: 18.1-18.6 ms against 18.3, inside the box-to-box noise (profiles/r06_shard_sim.txt) -- and made them constants)
-static int pre_share16() { return 2; }
-int64_t pre_positions(int64_t n_sample) {
-  if (n_sample < 64) return 0;
-  const int64_t a = round_up(std::max<int64_t>(DOC_GROUP, n_sample * pre_share16() / 16), DOC_GROUP);
-  return a < n_sample ? a : 0;
-}
-int mid_share16() { return 2; }
-// Rows scored exhaustively in phase 0 (>= the rank that defines tau, so that tau exists afterwards), whole tiles -- 512 rows until round 3, 256
-// since; 0 = none: a sampled search (S >= 2) bootstraps its first thresholds from the bound GEMM instead (search_core), unless the caller
-// fixed the head (DHR_PARAM_FIRST_ROWS).
-int64_t head_rows(const dhr_index* ix, int S, int r_eff) {
-  if (S >= 2 && ix->first_rows <= 0 && ix->n_tiles >= 8) {
-    // the bootstrap takes the r0-th best of at most BOOT_M rows of tile 0: a sampling rule under which r0 outgrows that (today r0 <= 44) must not
-    // publish the threshold of a lower rank -- it falls back to the exhaustive head instead (search_core computes r0 from the same expression)
-    const int64_t sample_rows = ((ix->n_tiles + S - 1) / S) * TILE_ROWS;
-    if (adaptive_rank(r_eff, (double)TILE_ROWS / (double)sample_rows) <= BOOT_M) return 0;
-  }
-  return ix->first_rows > 0 ? std::max<int64_t>(ix->first_rows, 2 * (int64_t)r_eff) : std::max<int64_t>(S >= 2 ? 256 : 512, 2 * (int64_t)r_eff);
-}
-int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, int depth, Timer& tm,
-                       dhr_search_stats& st, hipStream_t s, int stage, const float* tau_ext) {
+// ------------------------------------------------------------------------------------------ the steps of a search
+// Step 1 (calls that bring the query batch): query preparation, then phase 0 -- the threshold bootstrap of a sampled search, or the
+// exhaustive exact scoring of rows [0, first_valid).
+static int prepare_and_phase0(Search& c, const dhr_query_batch* qb) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; Timer& tm = c.tm; hipStream_t s = c.s; const SearchPlan& p = c.p; const int Q = c.Q;
   int rc;
-  // stage 4 (dhr_search_pre): query preparation, phase 0 and the FIRST part of the sampled run, then stop -- the shards exchange their best sample
-  // scores seen so far; stage 5 (dhr_search_begin_rest): the rest of the sampled run from the threshold they agreed on, then as stage 1.
-  const bool fresh = stage == 0 || stage == 1 || stage == 4;       // the call brings the query batch (else: resumed from ix->pend)
-  const int Q = !fresh ? ix->pend.Q : qb->n_queries;
-  const bool gate = !fresh ? ix->pend.gate
-                           : (ix->d_dlr > 0 && qb->index != nullptr && qb->index_dtype != DHR_IDX_NONE);   // else plain IP
-  const int64_t n = ix->n_rows;
-  // depth 0: sampled thresholds; depth 1 (queries that failed at depth 0): the same with 16x list capacity;
-  // depth 2: plain streaming, exact for any input
-  const bool allow_sampling = depth < 2;
-  // sampled threshold: period S, conservative rank r (DESIGN.md "controller")
-  int S = 0, r_eff = k;
-  if (allow_sampling) plan_sampling(ix, k, S, r_eff);
-  if (S >= 2 && stage != 0) r_eff = local_sample_rank(ix, r_eff);          // staged (sharded) search: this shard's share of the union's rank
-  // rows scored exhaustively in phase 0 (>= the rank that defines tau, so that tau exists afterwards), whole tile groups
-  // (512 rows until round 3; with sampled thresholds the head only has to hold 2 r rows, and it is a fixed cost of every rank of the
-  // sharded search: 256 rows x 6 980 queries are 1.1 ms of exhaustive rescoring)
-  int64_t first = head_rows(ix, S, r_eff);
-  // Round 5: a SAMPLED search seeds its thresholds without an exhaustive head (use_bootstrap: first == 0).  The head cost every search
-  // 256 rows x all queries of exact rescoring, bound by instruction issue (0.9-1.1 ms; for a 1/8 shard a quarter of its sampled run), only
-  // to know the ~6th best score of 256 rows.  Instead: ONE corpus tile through the bound GEMM with an open filter, the BOOT_M-or-fewer best
-  // rows of every query BY BOUND rescored exactly, and the r0-th best of those exact scores is the first threshold -- a lower bound of the
-  // r0-th best of the tile whatever the bound's ranking is worth (adaptive_rank's argument with phi = 256 rows of the sample).  The running
-  // list is cleared again: tile 0 is the first tile of the sample and comes back through the ordinary filtered phases.
-  const bool bootstrap = first == 0;
-  first = std::min(round_up(first, TILE_ROWS), round_up(n, TILE_ROWS));
-  const int64_t first_valid = std::min(first, n);
-  if ((rc = ensure_ws(ix, w, Q, k, first_valid, depth == 0 ? 1 : 16, gate || ix->gated_i8 || ix->resid8 != nullptr)) != DHR_OK) return rc;
-
-  // first attempt of a sampled search: the controller only enqueues (no host read-backs); DHR_PARAM_ASYNC_CONTROLLER 0 keeps the
-  // host-driven controller (and the fallback depths always use it: it is the one that is exact for any input)
-  const bool async_ctl = depth == 0 && S >= 2 && ix->async_ctl != 0 && !getenv("DHR_DEBUG_PLAN");
-  const bool plan_read = ix->async_ctl >= 2;      // 2: the chunk plan of the main pass reads the sampled run's list lengths back
-  if (fresh) {
-    tm.begin(T_PREP);
-    if ((rc = prep_queries(ix, w, qb, s)) != DHR_OK) return rc;
-    HIP_TRY(hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s));
-    HIP_TRY(hipMemsetAsync(w.fail_flags, 0, (size_t)w.q_pad * 4, s));
-    HIP_TRY(hipMemsetAsync(w.d_stats, 0, 32, s));
-    tm.end();
-  }
-
-  const int64_t head = first / TILE_ROWS;                       // tiles scored exhaustively
-  const int64_t rest = ix->n_tiles - head;
-
-  SelectArgs sel{};
-  sel.topk_keys = w.topk_keys; sel.in_keys = w.rs_keys; sel.ld_keys = w.keys_ld; sel.cap = (uint32_t)w.cap;
-  sel.k = r_eff; sel.kp = w.kp; sel.sort_n = select_sort_n(w.kp);
-  sel.k_keep = k;                          // the threshold is the r-th best seen, the list keeps the k best (ties with the final k-th score survive the sampled run)
-  sel.kps = 64; while (sel.kps < k) sel.kps <<= 1; sel.margin = w.margin; sel.tau = w.tau; sel.thr = w.thr;
-  sel.n_queries = Q;
-
-  // ---- phase 0: threshold bootstrap (sampled searches), or exhaustive exact scoring of rows [0, first_valid)
-  if (fresh && bootstrap) {
-    const int64_t sample_rows = ((rest + S - 1) / S) * TILE_ROWS;
-    const int r0 = adaptive_rank(r_eff, (double)TILE_ROWS / (double)sample_rows);
-    const int m = std::min(BOOT_M, std::max(16, 2 * r0));
+  tm.begin(T_PREP);
+  if ((rc = prep_queries(ix, w, qb, s)) != DHR_OK) return rc;
+  HIP_TRY(hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s));
+  HIP_TRY(hipMemsetAsync(w.fail_flags, 0, (size_t)w.q_pad * 4, s));
+  HIP_TRY(hipMemsetAsync(w.d_stats, 0, 32, s));
+  tm.end();
+  RescoreArgs r = base_rescore_args(ix, w, Q, c.gate);
+  r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
+  c.sel.cnt = nullptr;
+  if (p.bootstrap) {
+    // (the running list is cleared again below: tile 0 is the first tile of the sample and comes back through the ordinary filtered phases)
+    const int m = p.boot_m;
     {      // tile 0 through the bound GEMM's dump variant: [Q][256] bound scores, no lists
-      GemmArgs g{};
-      g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.k_split = ix->d_dlr / TILE_K; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant; g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum;
-      g.seq_lo = 0; g.seq_hi = 1; g.map_mode = 0; g.period = 1; g.head = 0; g.n_tiles = ix->n_tiles;
-      g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows; g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt; g.cap = (uint32_t)w.cap; g.n_queries = Q;
+      GemmArgs g = base_gemm_args(ix, w, Q);
+      g.seq_lo = 0; g.seq_hi = 1; g.map_mode = 0; g.period = 1; g.head = 0;
+      g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
       g.dump = w.boot_bound; g.dump_ld = TILE_ROWS; g.dump_row0 = 0;
       tm.begin(T_GEMM); HIP_TRY(launch_gemm_filter(g, s)); tm.end();
-      st.phases++;
+      c.st.phases++;
     }
-    HIP_TRY(launch_bound_topm(w.boot_bound, (int)std::min<int64_t>(TILE_ROWS, n), Q, m, w.boot_rows, s));
-    RescoreArgs r = base_rescore_args(ix, w, Q, gate);
+    HIP_TRY(launch_bound_topm(w.boot_bound, (int)std::min<int64_t>(TILE_ROWS, ix->n_rows), Q, m, w.boot_rows, s));
     r.rows32 = w.boot_rows; r.ld_rows = m; r.count_all = (uint32_t)m; r.max_count = (uint32_t)m;
-    r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
     tm.begin(T_RESCORE); HIP_TRY(launch_rescore(r, s)); tm.end();
-    sel.cnt = nullptr; sel.count_all = (uint32_t)m;
-    sel.k = std::min(r0, m); sel.monotone = 1;
-    tm.begin(T_SELECT); HIP_TRY(launch_select(sel, s)); tm.end();
+    c.sel.count_all = (uint32_t)m;
+    c.sel.k = std::min(p.boot_r0, m); c.sel.monotone = 1;
+    tm.begin(T_SELECT); HIP_TRY(launch_select(c.sel, s)); tm.end();
     HIP_TRY(hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s));       // thresholds stay (tau, thr); the rows come back with the sample
-    st.candidates_exact += (int64_t)m * Q;
-  } else if (fresh) {
-    RescoreArgs r = base_rescore_args(ix, w, Q, gate);
-    r.row0 = 0; r.count_all = (uint32_t)first_valid; r.max_count = (uint32_t)first_valid;
-    r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
-    tm.begin(T_RESCORE); HIP_TRY(launch_rescore(r, s)); tm.end();
-    sel.cnt = nullptr; sel.count_all = (uint32_t)first_valid;
-    if (S >= 2 && rest > 0) {       // the head is the first part of the sample (adaptive_rank)
-      const int64_t sample_rows = first_valid + ((rest + S - 1) / S) * TILE_ROWS;
-      sel.k = adaptive_rank(r_eff, (double)first_valid / (double)sample_rows);
-      sel.monotone = 1;
-    }
-    tm.begin(T_SELECT); HIP_TRY(launch_select(sel, s)); tm.end();
-    st.candidates_exact += (int64_t)first_valid * Q;
-  }
-  if (!fresh && ix->pend.done) return DHR_OK;              // the begin call already finished the search
-  if (rest <= 0 || S < 2) {
-    // plain streaming over all remaining tiles
-    if (rest > 0 && (rc = stream_phases(ix, w, Q, gate, sel, rest, 1, 1, head, head, first_valid, tm, st, s)) != DHR_OK) return rc;
-    if (stage == 1 || stage == 4) { ix->pend.valid = true; ix->pend.done = true; ix->pend.pre = false; ix->pend.gate = gate; ix->pend.Q = Q; ix->pend.k = k; }
+    c.st.candidates_exact += (int64_t)m * Q;
     return DHR_OK;
   }
+  r.row0 = 0; r.count_all = (uint32_t)p.first_valid; r.max_count = (uint32_t)p.first_valid;
+  tm.begin(T_RESCORE); HIP_TRY(launch_rescore(r, s)); tm.end();
+  c.sel.count_all = (uint32_t)p.first_valid;
+  if (p.sampled) { c.sel.k = p.head_rank; c.sel.monotone = 1; }       // the head is the first part of the sample (adaptive_rank)
+  tm.begin(T_SELECT); HIP_TRY(launch_select(c.sel, s)); tm.end();
+  c.st.candidates_exact += (int64_t)p.first_valid * Q;
+  return DHR_OK;
+}
 
-  // ---- sampled run: top-r_eff of {head rows} + {every S-th tile}  ->  tau_hat
-  const int64_t n_sample = (rest + S - 1) / S;
-  double rate = 0.0, rate_r = 0.0;
-  if (fresh || stage == 5) {
-    int64_t last_rows = 0;
-    int64_t pos0 = 0, seen0 = first_valid, n_hi = n_sample, chunk0 = std::max<int64_t>(head, DOC_GROUP);
-    if (stage == 4) {
-      n_hi = pre_positions(n_sample);
-      if (n_hi <= 0) return set_error(DHR_ERR_INVALID, "the sample of this index is too small for a pre step");
-    }
-    if (stage == 5) {
-      // the threshold the shards agreed on after the first part (never below this shard's own: thresholds only rise), and on with the growth rule
-      pos0 = ix->pend.pre_pos; seen0 = ix->pend.pre_seen;
-      HIP_TRY(launch_raise_thr(w.tau, tau_ext, Q, s));
-      HIP_TRY(launch_make_thr(w.tau, w.margin, Q, w.q_pad, w.thr, s));
-      // ONE phase for the rest: the agreed threshold is the union's (r phi + 6 sigma + 4)-th best of 1/8 of
-      // the union sample -- 8 x the rows this shard has seen -- and a phase of a shard's sampled run is bound by its launches, not by its rows
-      chunk0 = round_up(n_sample - pos0, DOC_GROUP);
-    }
+// Step 2: the sampled run -- top-r_eff of {head rows} + {every S-th tile} -> tau_hat.  Pre runs its first part and stops; BeginRest resumes
+// behind that part from the threshold the shards agreed on; Begin and BeginRest leave the handle ready for the main pass of a later call.
+static int sampled_run(Search& c) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; hipStream_t s = c.s; const SearchPlan& p = c.p; const int Q = c.Q;
+  int64_t last_rows = 0;
+  int64_t seen0 = p.first_valid, n_hi = p.n_sample, chunk0 = std::max<int64_t>(p.head, DOC_GROUP);
+  StreamOpts o;
+  o.async_ctl = c.async_ctl; o.last_rate = &c.rate; o.last_rate_r = &c.rate_r; o.last_rows = &last_rows;
+  o.rank_target = p.r_eff; o.rank_rows = p.sample_rows;
+  const bool pre = c.stage == Stage::Pre;
+  if (pre) {
+    n_hi = p.pre_positions;
+    if (n_hi <= 0) return set_error(DHR_ERR_INVALID, "the sample of this index is too small for a pre step");
     // (the first part of a shard's sample is 17 tiles of a 1/8 shard of the benchmark: phases of 4 + 13 tiles instead of 4 + 8 + 5 -- a phase there
     // is bound by its ~8 dependent launches, 0.4-0.5 ms, not by its rows: growth 4 x there)
     constexpr int pre_growth = 64;
-    if ((rc = stream_phases(ix, w, Q, gate, sel, n_hi, 1, S, head, chunk0, seen0, tm, st, s, &rate, &rate_r, async_ctl, &last_rows,
-                            r_eff, first_valid + n_sample * TILE_ROWS, pos0, stage == 4 ? std::max(ix->max_growth16, pre_growth) : 0,
-                            stage == 5 ? ix->pend.pre_last_rows : 0)) != DHR_OK) return rc;      // (stage 5: w.cnt still holds the lists of the pre call's last phase)
-    if (stage == 4) {
-      ix->pend.valid = true; ix->pend.done = false; ix->pend.mid = false; ix->pend.pre = true; ix->pend.gate = gate; ix->pend.Q = Q; ix->pend.k = k;
-      ix->pend.pre_pos = n_hi; ix->pend.pre_seen = first_valid + n_hi * TILE_ROWS; ix->pend.pre_last_rows = last_rows;
-      return DHR_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(w.tau_hat, w.tau, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
-    if (async_ctl && w.arena > 0) {          // the main pass plans its second list tier from these (possibly in a later call: staged search)
-      HIP_TRY(hipMemcpyAsync(w.cnt_plan, w.cnt, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
-      w.plan_rows = last_rows;
-    } else w.plan_rows = 0;                  // nothing to plan from: a main pass that finds the arena in use (a controller switched between the calls) plans no segments
-    if (async_ctl && plan_read && stage == 0 && last_rows > 0) {
-      // the ONE read-back besides the final one: 32 bytes, the fullest bound / survivor list of the last sampled phase -> how many chunks
-      // the main pass needs for the hottest query's lists to fit (a list that overflows costs its query tile an extra pass over the corpus:
-      // on the 5 M-row BEIR corpora 4 of 7 405 queries per step did, 85.5 ms instead of 77.7)
-      HIP_TRY(hipMemcpyAsync(w.h_pinned2, w.d_max2, 32, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      const uint32_t* hp = (const uint32_t*)w.h_pinned2;
-      rate = (double)hp[0] / (double)last_rows;
-      rate_r = uses_refine(ix, gate) ? (double)hp[4] / (double)last_rows : 0.0;
-    }
-    if (stage == 1 || stage == 5) {
-      ix->pend.valid = true; ix->pend.done = false; ix->pend.mid = false; ix->pend.pre = false; ix->pend.gate = gate; ix->pend.Q = Q; ix->pend.k = k; ix->pend.rate = rate; ix->pend.rate_r = rate_r;
-      return DHR_OK;
-    }
-  } else {
-    rate = ix->pend.rate; rate_r = ix->pend.rate_r;
-    if (stage == 2 && ix->pend.mid) {
-      // second agreement (after dhr_search_mid): thresholds only ever rise
-      HIP_TRY(launch_raise_thr(w.tau_hat, tau_ext, Q, s));
-      HIP_TRY(launch_make_thr(w.tau_hat, w.margin, Q, w.q_pad, w.thr, s));
-      HIP_TRY(launch_raise_thr(w.thr_hat, w.thr, Q, s));
-    } else {
-      // thresholds agreed between the shards: tau_ext >= this shard's own tau_hat in general
-      HIP_TRY(hipMemcpyAsync(w.tau_hat, tau_ext, (size_t)Q * 4, hipMemcpyDeviceToDevice, s));
-      HIP_TRY(launch_flag_tau_above(w.tau, w.tau_hat, Q, w.fail_flags, s));      // sample rows this shard dropped below its own (higher) threshold
-      HIP_TRY(launch_make_thr(w.tau_hat, w.margin, Q, w.q_pad, w.thr, s));
-    }
+    o.growth16 = std::max(ix->max_growth16, pre_growth);
   }
+  if (c.stage == Stage::BeginRest) {
+    // the threshold the shards agreed on after the first part (never below this shard's own: thresholds only rise), and on with the growth rule
+    o.pos0 = ix->pend.pre_pos; seen0 = ix->pend.pre_seen;
+    o.prev_rows0 = ix->pend.pre_last_rows;      // (w.cnt still holds the lists of the pre call's last phase)
+    HIP_TRY(launch_raise_thr(w.tau, c.tau_ext, Q, s));
+    HIP_TRY(launch_make_thr(w.tau, w.margin, Q, w.q_pad, w.thr, s));
+    // ONE phase for the rest: the agreed threshold is the union's (r phi + 6 sigma + 4)-th best of 1/8 of
+    // the union sample -- 8 x the rows this shard has seen -- and a phase of a shard's sampled run is bound by its launches, not by its rows
+    chunk0 = round_up(p.n_sample - o.pos0, DOC_GROUP);
+  }
+  int rc = stream_phases(c, n_hi, p.S, chunk0, seen0, o);
+  if (rc != DHR_OK) return rc;
+  if (pre) {
+    staged_open(ix, StagedState::AfterPre, c.gate, Q, c.k);
+    ix->pend.pre_pos = n_hi; ix->pend.pre_seen = p.first_valid + n_hi * TILE_ROWS; ix->pend.pre_last_rows = last_rows;
+    return DHR_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(w.tau_hat, w.tau, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
+  if (c.async_ctl && w.arena > 0) {          // the main pass plans its second list tier from these (possibly in a later call: staged search)
+    HIP_TRY(hipMemcpyAsync(w.cnt_plan, w.cnt, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
+    w.plan_rows = last_rows;
+  } else w.plan_rows = 0;                  // nothing to plan from: a main pass that finds the arena in use (a controller switched between the calls) plans no segments
+  if (c.async_ctl && ix->async_ctl >= 2 && c.whole() && last_rows > 0) {
+    // the ONE read-back besides the final one: 32 bytes, the fullest bound / survivor list of the last sampled phase -> how many chunks
+    // the main pass needs for the hottest query's lists to fit (a list that overflows costs its query tile an extra pass over the corpus:
+    // on the 5 M-row BEIR corpora 4 of 7 405 queries per step did, 85.5 ms instead of 77.7)
+    HIP_TRY(hipMemcpyAsync(w.h_pinned2, w.d_max2, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t* hp = (const uint32_t*)w.h_pinned2;
+    c.rate = (double)hp[0] / (double)last_rows;
+    c.rate_r = uses_refine(ix, c.gate) ? (double)hp[4] / (double)last_rows : 0.0;
+  }
+  if (!c.whole()) {
+    staged_open(ix, StagedState::AfterBegin, c.gate, Q, c.k);
+    ix->pend.rate = c.rate; ix->pend.rate_r = c.rate_r;
+  }
+  return DHR_OK;
+}
 
-  // ---- main pass: all other tiles with the FROZEN threshold tau_hat - margin, in a few chunks; the
-  // bound GEMM of chunk i+1 (stream s) overlaps the exact rescoring + top-k merge of chunk i (aux stream)
-  sel.k = k; sel.kps = w.kp; sel.monotone = 0;
-  const int64_t n_main = rest - n_sample;
+// Step 2' (Mid, Finish): the sampled run was another call's -- take its rates and the thresholds the shards agreed on
+static int adopt_thresholds(Search& c) {
+  Workspace& w = c.w; hipStream_t s = c.s; const int Q = c.Q;
+  c.rate = c.ix->pend.rate; c.rate_r = c.ix->pend.rate_r;
+  if (c.after_mid) {
+    // second agreement (after dhr_search_mid): thresholds only ever rise
+    HIP_TRY(launch_raise_thr(w.tau_hat, c.tau_ext, Q, s));
+    HIP_TRY(launch_make_thr(w.tau_hat, w.margin, Q, w.q_pad, w.thr, s));
+    HIP_TRY(launch_raise_thr(w.thr_hat, w.thr, Q, s));
+  } else {
+    // thresholds agreed between the shards: tau_ext >= this shard's own tau_hat in general
+    HIP_TRY(hipMemcpyAsync(w.tau_hat, c.tau_ext, (size_t)Q * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(launch_flag_tau_above(w.tau, w.tau_hat, Q, w.fail_flags, s));      // sample rows this shard dropped below its own (higher) threshold
+    HIP_TRY(launch_make_thr(w.tau_hat, w.margin, Q, w.q_pad, w.thr, s));
+  }
+  return DHR_OK;
+}
+// ---- step 3, the main pass: all other tiles with the FROZEN threshold tau_hat - margin, in a few chunks; the
+// bound GEMM of chunk i+1 (stream sg) overlaps the exact rescoring + top-k merge of chunk i (stream sb)
+struct MainPass {
+  hipStream_t sg = nullptr, sb = nullptr;      // the streams of the bound GEMM and of refine / rescoring / select
+  bool extrapolate = false, scatter = false, two_tier = false;
+  int M = 0, c_lo = 0, c_hi = 0;               // chunks of the pass, and the chunks [c_lo, c_hi) THIS call runs
+  std::vector<int64_t> bound;                  // chunk i covers main-pass positions [bound[i], bound[i + 1])
+  std::vector<hipEvent_t> ev_gemm, ev_done;
+  Events evs;                                  // every event of the pass (destroyed on every way out)
+};
+// Streams of the main pass.  Default: the bound GEMM on the caller's stream, refine/rescoring/select on a
+// non-blocking aux stream.  With aux_cus = N the aux stream is confined to N CUs (the low N bits of the CU
+// mask are spread evenly over the 8 XCDs) so that the memory-bound aux kernels take only the CUs they need
+// from the GEMM; gemm_exclusive additionally keeps the GEMM (on an internal stream) off those CUs.
+// (measured on a 1/8 shard of config 4, round 3: unmasked 17.0 ms per finish, 128 CUs 18.2, no overlap 18.1; dense-only indexes
+// measured best with 128 CUs in round 1)
+static int main_streams(Search& c, MainPass& mp) {
+  dhr_index* ix = c.ix;
+  const int aux_cus = ix->aux_cus >= 0 ? ix->aux_cus : (ix->d_dlr == 0 ? 128 : 0);
+  if (ix->aux_cus_made != aux_cus || ix->gemm_excl_made != ix->gemm_exclusive) {
+    if (ix->s_aux) { hipStreamDestroy(ix->s_aux); ix->s_aux = nullptr; }
+    if (ix->s_gemm) { hipStreamDestroy(ix->s_gemm); ix->s_gemm = nullptr; }
+    if (aux_cus > 0) {
+      uint32_t m_aux[8], m_gemm[8];
+      for (int i = 0; i < 8; ++i) {
+        const int lo = i * 32;
+        const int n = std::max(0, std::min(32, aux_cus - lo));
+        m_aux[i] = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
+        m_gemm[i] = ix->gemm_exclusive ? ~m_aux[i] : 0xffffffffu;
+      }
+      // (a runtime that refuses the mask -- other CU count, masking disabled -- just gets the unmasked streams)
+      if (hipExtStreamCreateWithCUMask(&ix->s_aux, 8, m_aux) != hipSuccess ||
+          hipExtStreamCreateWithCUMask(&ix->s_gemm, 8, m_gemm) != hipSuccess) {
+        (void)hipGetLastError();
+        if (ix->s_aux) { hipStreamDestroy(ix->s_aux); ix->s_aux = nullptr; }
+        if (ix->s_gemm) { hipStreamDestroy(ix->s_gemm); ix->s_gemm = nullptr; }
+      }
+    }
+    if (!ix->s_aux) {
+      // (round 5 measured the aux stream at the lowest queue priority: no gain -- a CU between two GEMM workgroups fills with gather waves whatever the priority)
+      HIP_TRY(hipStreamCreateWithFlags(&ix->s_aux, hipStreamNonBlocking));
+    }
+    ix->aux_cus_made = aux_cus; ix->gemm_excl_made = ix->gemm_exclusive;
+  }
+  mp.sg = ix->s_gemm ? ix->s_gemm : c.s;
+  // default: dense-only indexes, and the main pass of a SHARD (staged search: its refine / rescoring / select are a larger share of a
+  // shorter step -- 18.1 -> 17.0 ms per finish on a 1/8 shard of config 4; the unsharded gated search gains 2 % and its GEMM launches
+  // would be timed under contention, so it keeps them serial)
+  // Round 4: the default everywhere.  The unsharded gated search gains 2 ms per config-3 step (124.5 vs 126.2 ms; 1.5 % in round 3); its GEMM
+  // launches then share CUs and the memory system with the gathers (92 -> 116 ms of launch durations per step), so the kernel's own rate
+  // is profiled with DHR_PARAM_OVERLAP_AUX = 0 (bench.py reports both).
+  const bool overlap = ix->overlap_aux < 0 ? true : ix->overlap_aux != 0;
+  mp.sb = overlap ? ix->s_aux : mp.sg;
+  return DHR_OK;
+}
+// Chunks of the main pass besides the slice of a mid step: at least main_chunks, more when the sampled run predicts that the fullest list
+// would not fit (rate = bound candidates per corpus row of the fullest query at the final sample thresholds, 1.5x headroom)
+// ... and the same for the survivor lists of the refine step, which are shallower (cap_r): a query whose bound the heavy lists
+// do not tighten fills them first
+// (two-tier lists: a hot query's list may grow to cap_deep; the host-driven controller only has the uniform stride)
+static int main_chunk_count(const Search& c, const MainPass& mp, bool mid_proto) {
+  const dhr_index* ix = c.ix; const Workspace& w = c.w; const int64_t n_main = c.p.n_main; const double rate = c.rate, rate_r = c.rate_r;
+  const bool plan_read = ix->async_ctl >= 2 && c.whole();     // the chunk plan reads the sampled run's list lengths back (sampled_run)
+  const int64_t plan_cap = mp.two_tier ? w.cap_deep : w.cap;
+  const int64_t need = std::max((int64_t)std::ceil(1.5 * rate * (double)n_main * TILE_ROWS / (double)plan_cap),
+                                (int64_t)std::ceil(1.5 * rate_r * (double)n_main * TILE_ROWS / (double)w.cap_r));
+  // (without read-backs the sampled run's rates are not known here: a fixed 8 chunks (12 where the thresholds are extrapolated, below), which the deep lists of round 3 cover at config 3 --
+  // 203 k entries in the fullest list of the first chunk against 262 144 slots; a list that overflows anyway flags its query)
+  // ... scaled with the shard: one chunk per ~4 200 tiles, 2 to 8 (a 1/8 shard of config 4: 2 chunks; 8 cost it 7 ms of launches)
+  // ... and, where that takes at most 12 chunks, so many that the FIRST (largest: 3 / (2 M) of the pass) chunk has no more rows than a list has
+  // slots: a small corpus then cannot overflow a list whatever its scores are (queries with fewer than k matching rows filter at 0)
+  int64_t by_size = std::min<int64_t>(8, std::max<int64_t>(2, (n_main + 4199) / 4200));
+  const int64_t no_overflow = (3 * n_main * TILE_ROWS + 2 * std::min(plan_cap, w.cap_r) - 1) / (2 * std::min(plan_cap, w.cap_r));
+  if (no_overflow <= 12) by_size = std::max(by_size, no_overflow);
+  // ... and so many that the HOTTEST queries fit: on the benchmark's data a query passes ~20 k rows per 1 000 results through the bound
+  // filter and ~4 k through the refine step, the hottest ten times that, whatever the corpus size -- on a 0.5 M-row corpus (BEIR quora,
+  // 10 000 queries) that is a fifth of the rows of a chunk, and with 2 chunks 195 queries per step overflowed their 65 536-entry lists and
+  // were redone (60 ms per step instead of 28).  The first chunk is 3 / (2 M) of the pass.  (A shard chases its share of k.)
+  {
+    const double k_eff = (double)c.k / (double)std::max(1, c.whole() ? 1 : ix->sample_share);
+    const int64_t by_hot = (int64_t)std::ceil(300.0 * k_eff / (double)plan_cap);
+    const int64_t by_hot_r = (int64_t)std::ceil(65.0 * k_eff / (double)w.cap_r);
+    by_size = std::max(by_size, std::min<int64_t>(24, std::max(by_hot, by_hot_r)));
+  }
+  // ... and, where the thresholds are extrapolated between the chunks (unsharded search), one chunk per ~2 800 tiles up to 12: every chunk
+  // boundary is a chance to raise them.  Config 3: 8 -> 12 chunks rescores 3.29 k instead of 3.37 k rows per query, -0.4 ms; config 2 (whose
+  // refine level is the larger share of its step): 78.0 -> 75.5 ms.  16 measure the same, 24 / 32 / 48 lose it again to launch boundaries
+  // (config 3: 121.9 / 123.2 / 126.6 ms against 121.2-121.6 at 16 and 121.9 at 8 on one box).
+  if (mp.extrapolate) by_size = std::max(by_size, std::min<int64_t>(12, (n_main + 2799) / 2800));
+  const int64_t want = c.async_ctl ? std::max<int64_t>(std::max<int64_t>(ix->main_chunks, by_size), plan_read ? need : 0) : std::max<int64_t>(ix->main_chunks, need);
+  // (k > 4096: every chunk boundary costs a merge of the 16 384-slot running list of every query, 1.0-2.3 ms whatever the chunk brought; capping
+  // the plan at 4 / 6 / 8 chunks there was measured in round 5 -- 242 -> 250-275 ms for --theta 0.3 --rerank with agip_topk 10 000: the
+  // lists of the hottest queries overflow and their queries are redone.  The plan stays.)
+  const int M_plain = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, 64), n_main / (16 * DOC_GROUP)));
+  if (getenv("DHR_DEBUG_PLAN"))
+    fprintf(stderr, "[dhr] main pass: rate %.3e (x n_main rows = %.0f of cap %lld), rate_r %.3e (%.0f of cap_r %lld), need %lld, chunks %d, n_main %lld tiles\n", rate,
+            rate * (double)n_main * TILE_ROWS, (long long)w.cap, rate_r, rate_r * (double)n_main * TILE_ROWS, (long long)w.cap_r, (long long)need, M_plain + (mid_proto ? 1 : 0), (long long)n_main);
+  return M_plain;
+}
+// The bound GEMM of chunk i into list set i & 1 on sg
+static int main_gemm(Search& c, MainPass& mp, int i) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; hipStream_t sg = mp.sg;
+  uint32_t* cnt = (i & 1) ? w.cnt2 : w.cnt;
+  if (i >= mp.c_lo + 2) HIP_TRY(hipStreamWaitEvent(sg, mp.ev_done[i - 2], 0));      // list set is free again
+  GemmArgs g = base_gemm_args(ix, w, c.Q);
+  g.seq_lo = mp.bound[i]; g.seq_hi = mp.bound[i + 1]; g.map_mode = mp.scatter ? 3 : 2; g.period = c.p.S; g.head = c.p.head;
+  g.perm_mul = mp.scatter ? c.p.perm_mul : 1; g.perm_n = c.p.n_main;
+  g.thr = w.thr_hat; g.cand = (i & 1) ? w.cand2 : w.cand; g.cnt = cnt;
+  if (mp.two_tier) g.tier = w.tier_dev + (i & 1);
+  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)w.q_pad * 4, sg));
+  if (!c.async_ctl) HIP_TRY(hipMemsetAsync(w.d_max2 + 4 * (i & 1), 0, 16, sg));
+  c.tm.begin_on(T_GEMM, sg); HIP_TRY(launch_gemm_filter(g, sg)); c.tm.end_on(sg);
+  ix->last_gemm_kernel = g_last_gemm_kernel;
+  if (!c.async_ctl) {       // the host-driven controller sizes the per-candidate launches from the list lengths; the enqueue-only one leaves them on the device
+    HIP_TRY(launch_max_u32(cnt, c.Q, w.d_max2 + 4 * (i & 1), (unsigned long long*)(w.d_max2 + 4 * (i & 1) + 2), sg));
+    HIP_TRY(hipMemcpyAsync(w.h_pinned2 + 16 * (i & 1), w.d_max2 + 4 * (i & 1), 16, hipMemcpyDeviceToHost, sg));
+  }
+  HIP_TRY(hipEventRecord(mp.ev_gemm[i], sg));
+  count_gemm(c, mp.bound[i + 1] - mp.bound[i]);
+  return DHR_OK;
+}
+// Chunks [c_lo, c_hi): GEMM i + 1 is enqueued before the lists of chunk i are refined, rescored and merged on sb
+static int main_chunks(Search& c, MainPass& mp) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; const SearchPlan& p = c.p; const int Q = c.Q;
+  hipStream_t sb = mp.sb;
+  int rc;
+  if ((rc = main_gemm(c, mp, mp.c_lo)) != DHR_OK) return rc;
+  for (int i = mp.c_lo; i < mp.c_hi; ++i) {
+    if (i + 1 < mp.c_hi && (rc = main_gemm(c, mp, i + 1)) != DHR_OK) return rc;
+    uint2* cand = (i & 1) ? w.cand2 : w.cand;
+    uint32_t* cnt = (i & 1) ? w.cnt2 : w.cnt;
+    if (c.async_ctl) {
+      if (sb != mp.sg) HIP_TRY(hipStreamWaitEvent(sb, mp.ev_gemm[i], 0));
+      if ((rc = rescore_select_async(c, cand, cnt, w.thr_hat, sb, nullptr, nullptr, mp.two_tier ? ((i & 1) ? w.ovf2 : w.ovf) : nullptr)) != DHR_OK) return rc;
+    } else {
+      HIP_TRY(hipEventSynchronize(mp.ev_gemm[i]));
+      const uint32_t maxc = *(const uint32_t*)(w.h_pinned2 + 16 * (i & 1));      // 16 bytes per set: {max, pad, sum64}; two sets live in 32 bytes
+      unsigned long long sumc;
+      memcpy(&sumc, w.h_pinned2 + 16 * (i & 1) + 8, 8);
+      c.st.candidates_bound += (int64_t)sumc;
+      if (getenv("DHR_DEBUG_PLAN")) fprintf(stderr, "[dhr] main chunk %d: tiles [%lld, %lld)\n", i, (long long)mp.bound[i], (long long)mp.bound[i + 1]);
+      HIP_TRY(launch_mark_overflow(cnt, (uint32_t)w.cap, Q, w.fail_flags, sb));
+      if ((rc = rescore_select(c, cand, cnt, w.thr_hat, maxc, sb, (int64_t)sumc, w.fail_flags)) != DHR_OK) return rc;
+    }
+    if (ix->progressive_thr) HIP_TRY(launch_raise_thr(w.thr_hat, c.sel.thr, Q, sb));   // later chunks filter with the running exact thresholds
+    if (mp.extrapolate && i + 1 < mp.M) {
+      const int r = plan::extrapolated_rank(c.k, (double)(p.head + p.n_sample + mp.bound[i + 1]) / (double)ix->n_tiles);
+      if (r < c.k) HIP_TRY(launch_raise_thr_rank(w.thr_hat, w.tau_hat, w.topk_keys, w.kp, r, w.margin, Q, sb));
+    }
+    HIP_TRY(hipEventRecord(mp.ev_done[i], sb));
+  }
+  return DHR_OK;
+}
+static int main_pass(Search& c) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; hipStream_t s = c.s; const SearchPlan& p = c.p;
+  MainPass mp;
+  c.sel.k = c.k; c.sel.kps = w.kp; c.sel.monotone = 0;
   // progressive_thr 2 (default, first attempt of an unsharded search only): the main pass visits the non-sample tiles in a scattered
   // order (i -> i * perm_mul mod n_main, perm_mul ~ 0.618 n_main and coprime), so that what has been seen after any chunk is a
   // scattered fraction of the corpus whatever the order of the rows, and the thresholds are extrapolated from it (raise_thr_rank_kernel)
-  const bool extrapolate = ix->progressive_thr >= 2 && stage == 0 && depth == 0 && n_main >= 64 && k >= 16;
-  const bool mid_proto = stage == 3 || (stage == 2 && ix->pend.mid);       // the shards agree a second time after a first slice: it must be a scattered one
-  const bool scatter = extrapolate || (mid_proto && n_main >= 64);
-  int64_t perm_mul = 1;
-  if (scatter) {
-    perm_mul = (int64_t)(0.6180339887 * (double)n_main) | 1;
-    auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
-    while (gcd(perm_mul, n_main) != 1) perm_mul += 2;
+  mp.extrapolate = ix->progressive_thr >= 2 && c.whole() && c.depth == 0 && p.n_main >= 64 && c.k >= 16;
+  const bool mid = c.stage == Stage::Mid;       // this call runs the first slice only
+  const bool mid_proto = mid || c.after_mid;      // the shards agree a second time after a first slice: it must be a scattered one
+  mp.scatter = mp.extrapolate || (mid_proto && p.n_main >= 64);
+  if (!c.after_mid) HIP_TRY(hipMemcpyAsync(w.thr_hat, w.thr, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
+  if (!w.cand2) {          // the second list set
+    int64_t tot = 0;
+    HIP_TRY(re_malloc(w.cand2, (size_t)w.q_alloc * w.cap * 8, tot));
+    HIP_TRY(re_malloc(w.cnt2, (size_t)w.q_alloc * 4, tot));
+    if (w.arena > 0) {
+      HIP_TRY(re_malloc(w.ovf2, (size_t)w.arena * 8, tot));
+      const ListTier t1{w.ovf2, w.ovf_off, w.ovf_cap};
+      HIP_TRY(hipMemcpy(w.tier_dev + 1, &t1, sizeof t1, hipMemcpyHostToDevice));
+    }
+    w.bytes += tot;
   }
-  {
-    if (!(stage == 2 && ix->pend.mid)) HIP_TRY(hipMemcpyAsync(w.thr_hat, w.thr, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
-    if (!w.cand2) {
-      int64_t tot = 0;
-      HIP_TRY(re_malloc(w.cand2, (size_t)w.q_alloc * w.cap * 8, tot));
-      HIP_TRY(re_malloc(w.cnt2, (size_t)w.q_alloc * 4, tot));
-      if (w.arena > 0) {
-        HIP_TRY(re_malloc(w.ovf2, (size_t)w.arena * 8, tot));
-        const ListTier t1{w.ovf2, w.ovf_off, w.ovf_cap};
-        HIP_TRY(hipMemcpy(w.tier_dev + 1, &t1, sizeof t1, hipMemcpyHostToDevice));
-      }
-      w.bytes += tot;
-    }
-    // Streams of the main pass.  Default: the bound GEMM on the caller's stream, refine/rescoring/select on a
-    // non-blocking aux stream.  With aux_cus = N the aux stream is confined to N CUs (the low N bits of the CU
-    // mask are spread evenly over the 8 XCDs) so that the memory-bound aux kernels take only the CUs they need
-    // from the GEMM; gemm_exclusive additionally keeps the GEMM (on an internal stream) off those CUs.
-    // (measured on a 1/8 shard of config 4, round 3: unmasked 17.0 ms per finish, 128 CUs 18.2, no overlap 18.1; dense-only indexes
-    // measured best with 128 CUs in round 1)
-    const int aux_cus = ix->aux_cus >= 0 ? ix->aux_cus : (ix->d_dlr == 0 ? 128 : 0);
-    if (ix->aux_cus_made != aux_cus || ix->gemm_excl_made != ix->gemm_exclusive) {
-      if (ix->s_aux) { hipStreamDestroy(ix->s_aux); ix->s_aux = nullptr; }
-      if (ix->s_gemm) { hipStreamDestroy(ix->s_gemm); ix->s_gemm = nullptr; }
-      if (aux_cus > 0) {
-        uint32_t m_aux[8], m_gemm[8];
-        for (int i = 0; i < 8; ++i) {
-          const int lo = i * 32;
-          const int n = std::max(0, std::min(32, aux_cus - lo));
-          m_aux[i] = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
-          m_gemm[i] = ix->gemm_exclusive ? ~m_aux[i] : 0xffffffffu;
-        }
-        // (a runtime that refuses the mask -- other CU count, masking disabled -- just gets the unmasked streams)
-        if (hipExtStreamCreateWithCUMask(&ix->s_aux, 8, m_aux) != hipSuccess ||
-            hipExtStreamCreateWithCUMask(&ix->s_gemm, 8, m_gemm) != hipSuccess) {
-          (void)hipGetLastError();
-          if (ix->s_aux) { hipStreamDestroy(ix->s_aux); ix->s_aux = nullptr; }
-          if (ix->s_gemm) { hipStreamDestroy(ix->s_gemm); ix->s_gemm = nullptr; }
-        }
-      }
-      if (!ix->s_aux) {
-        // (round 5 measured the aux stream at the lowest queue priority: no gain -- a CU between two GEMM workgroups fills with gather waves whatever the priority)
-        HIP_TRY(hipStreamCreateWithFlags(&ix->s_aux, hipStreamNonBlocking));
-      }
-      ix->aux_cus_made = aux_cus; ix->gemm_excl_made = ix->gemm_exclusive;
-    }
-    hipStream_t sg = ix->s_gemm ? ix->s_gemm : s;
-    // default: dense-only indexes, and the main pass of a SHARD (staged search: its refine / rescoring / select are a larger share of a
-    // shorter step -- 18.1 -> 17.0 ms per finish on a 1/8 shard of config 4; the unsharded gated search gains 2 % and its GEMM launches
-    // would be timed under contention, so it keeps them serial)
-    // Round 4: the default everywhere.  The unsharded gated search gains 2 ms per config-3 step (124.5 vs 126.2 ms; 1.5 % in round 3); its GEMM
-    // launches then share CUs and the memory system with the gathers (92 -> 116 ms of launch durations per step), so the kernel's own rate
-    // is profiled with DHR_PARAM_OVERLAP_AUX = 0 (bench.py reports both).
-    const bool overlap = ix->overlap_aux < 0 ? true : ix->overlap_aux != 0;
-    hipStream_t sb = overlap ? ix->s_aux : sg;
-    Events evs;                 // every event of the pass (destroyed on every way out)
-    // chunk count: at least main_chunks, more when the sampled run predicts that the fullest list would not fit
-    // (rate = bound candidates per corpus row of the fullest query at the final sample thresholds, 1.5x headroom)
-    // ... and the same for the survivor lists of the refine step, which are shallower (cap_r): a query whose bound the heavy lists
-    // do not tighten fills them first
-    // (two-tier lists: a hot query's list may grow to cap_deep; the host-driven controller only has the uniform stride)
-    const bool two_tier = async_ctl && w.arena > 0;
-    const int64_t plan_cap = two_tier ? w.cap_deep : w.cap;
-    const int64_t need = std::max((int64_t)std::ceil(1.5 * rate * (double)n_main * TILE_ROWS / (double)plan_cap),
-                                  (int64_t)std::ceil(1.5 * rate_r * (double)n_main * TILE_ROWS / (double)w.cap_r));
-    // (without read-backs the sampled run's rates are not known here: a fixed 8 chunks (12 where the thresholds are extrapolated, below), which the deep lists of round 3 cover at config 3 --
-    // 203 k entries in the fullest list of the first chunk against 262 144 slots; a list that overflows anyway flags its query)
-    // ... scaled with the shard: one chunk per ~4 200 tiles, 2 to 8 (a 1/8 shard of config 4: 2 chunks; 8 cost it 7 ms of launches)
-    // ... and, where that takes at most 12 chunks, so many that the FIRST (largest: 3 / (2 M) of the pass) chunk has no more rows than a list has
-    // slots: a small corpus then cannot overflow a list whatever its scores are (queries with fewer than k matching rows filter at 0)
-    int64_t by_size = std::min<int64_t>(8, std::max<int64_t>(2, (n_main + 4199) / 4200));
-    const int64_t no_overflow = (3 * n_main * TILE_ROWS + 2 * std::min(plan_cap, w.cap_r) - 1) / (2 * std::min(plan_cap, w.cap_r));
-    if (no_overflow <= 12) by_size = std::max(by_size, no_overflow);
-    // ... and so many that the HOTTEST queries fit: on the benchmark's data a query passes ~20 k rows per 1 000 results through the bound
-    // filter and ~4 k through the refine step, the hottest ten times that, whatever the corpus size -- on a 0.5 M-row corpus (BEIR quora,
-    // 10 000 queries) that is a fifth of the rows of a chunk, and with 2 chunks 195 queries per step overflowed their 65 536-entry lists and
-    // were redone (60 ms per step instead of 28).  The first chunk is 3 / (2 M) of the pass.  (A shard chases its share of k.)
-    {
-      const double k_eff = (double)k / (double)std::max(1, stage >= 2 ? ix->sample_share : 1);
-      const int64_t by_hot = (int64_t)std::ceil(300.0 * k_eff / (double)plan_cap);
-      const int64_t by_hot_r = (int64_t)std::ceil(65.0 * k_eff / (double)w.cap_r);
-      by_size = std::max(by_size, std::min<int64_t>(24, std::max(by_hot, by_hot_r)));
-    }
-    // ... and, where the thresholds are extrapolated between the chunks (unsharded search), one chunk per ~2 800 tiles up to 12: every chunk
-    // boundary is a chance to raise them.  Config 3: 8 -> 12 chunks rescores 3.29 k instead of 3.37 k rows per query, -0.4 ms; config 2 (whose
-    // refine level is the larger share of its step): 78.0 -> 75.5 ms.  16 measure the same, 24 / 32 / 48 lose it again to launch boundaries
-    // (config 3: 121.9 / 123.2 / 126.6 ms against 121.2-121.6 at 16 and 121.9 at 8 on one box).
-    if (extrapolate) by_size = std::max(by_size, std::min<int64_t>(12, (n_main + 2799) / 2800));
-    const int64_t want = async_ctl ? std::max<int64_t>(std::max<int64_t>(ix->main_chunks, by_size), (plan_read && stage == 0) ? need : 0) : std::max<int64_t>(ix->main_chunks, need);
-    // (k > 4096: every chunk boundary costs a merge of the 16 384-slot running list of every query, 1.0-2.3 ms whatever the chunk brought; capping
-    // the plan at 4 / 6 / 8 chunks there was measured in round 5 -- 242 -> 250-275 ms for --theta 0.3 --rerank with agip_topk 10 000: the
-    // lists of the hottest queries overflow and their queries are redone.  The plan stays.)
-    const int M_plain = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, 64), n_main / (16 * DOC_GROUP)));
-    // mid protocol: chunk 0 is the slice dhr_search_mid runs (mid_share16 / 16 of the pass), the plain plan covers the rest
-    const int M = mid_proto ? M_plain + 1 : M_plain;
-    if (getenv("DHR_DEBUG_PLAN"))
-      fprintf(stderr, "[dhr] main pass: rate %.3e (x n_main rows = %.0f of cap %lld), rate_r %.3e (%.0f of cap_r %lld), need %lld, chunks %d, n_main %lld tiles\n", rate,
-              rate * (double)n_main * TILE_ROWS, (long long)w.cap, rate_r, rate_r * (double)n_main * TILE_ROWS, (long long)w.cap_r, (long long)need, M, (long long)n_main);
-    // chunk i covers [bound[i], bound[i+1]): sizes fall off linearly (weights M, M-1, ..., 1 on top of an equal
-    // share) so that the refine/rescoring tail that cannot overlap a GEMM (the last chunk's) is short
-    std::vector<int64_t> bound(M + 1, 0);
-    {
-      const int first = mid_proto ? 1 : 0;
-      const int64_t off = mid_proto ? std::min<int64_t>(n_main, round_up(n_main * mid_share16() / 16, DOC_GROUP)) : 0;
-      bound[first] = off;
-      double acc = 0.0, tot = 0.0;
-      for (int i = 0; i < M_plain; ++i) tot += 1.0 + 2.0 * (M_plain - 1 - i) / std::max(1, M_plain - 1);
-      for (int i = 0; i < M_plain; ++i) {
-        acc += 1.0 + 2.0 * (M_plain - 1 - i) / std::max(1, M_plain - 1);
-        bound[first + i + 1] = std::min<int64_t>(n_main, off + round_up((int64_t)((n_main - off) * acc / tot), DOC_GROUP));
-      }
-      bound[M] = n_main;
-    }
-    const int c_lo = (stage == 2 && ix->pend.mid) ? 1 : 0, c_hi = stage == 3 ? 1 : M;      // the chunks THIS call runs
-    if (two_tier) {
-      // second tier of the bound lists, ONE plan for every chunk of the pass (both list sets share it): from the lists of the last sampled
-      // phase, scaled to the largest chunk -- the pass filters with thresholds at least as high as that phase did, and they only rise
-      int64_t big = 0;
-      for (int i = 0; i < M; ++i) big = std::max(big, bound[i + 1] - bound[i]);
-      HIP_TRY(launch_plan_overflow(w.plan_rows > 0 ? w.cnt_plan : nullptr, w.plan_rows > 0 ? (double)(big * TILE_ROWS) / (double)w.plan_rows : 0.0, (uint32_t)w.cap,
-                                   (uint32_t)(w.cap_deep - w.cap), (uint32_t)w.arena, Q, w.ovf_off, w.ovf_cap, s));
-    }
-    // The GEMM / aux streams enter the pass behind everything the caller's stream holds so far -- INCLUDING the plan above: with CU masks
-    // (DHR_PARAM_AUX_CUS / GEMM_EXCLUSIVE) the bound GEMM runs on s_gemm and refine on s_aux, and until round 5 they waited on an event
-    // recorded BEFORE the plan kernel, so a GEMM that spilled past `cap` could pair a new ovf_cap with an old ovf_off.
-    if (sg != s || sb != s) {
-      hipEvent_t ev_enter = nullptr;
-      HIP_TRY(evs.add(&ev_enter, hipEventDisableTiming));
-      HIP_TRY(hipEventRecord(ev_enter, s));
-      if (sg != s) HIP_TRY(hipStreamWaitEvent(sg, ev_enter, 0));
-      if (sb != s) HIP_TRY(hipStreamWaitEvent(sb, ev_enter, 0));
-    }
-    std::vector<hipEvent_t> ev_gemm(M), ev_done(M);
-    for (int i = 0; i < M; ++i) {
-      HIP_TRY(evs.add(&ev_gemm[i], hipEventDisableTiming));
-      HIP_TRY(evs.add(&ev_done[i], hipEventDisableTiming));
-    }
-    uint32_t* h = (uint32_t*)w.h_pinned;          // 16 bytes per set: {max, pad, sum64}; two sets live in 32 bytes
-    auto enqueue_gemm = [&](int i) -> int {
-      uint2* cand = (i & 1) ? w.cand2 : w.cand;
-      uint32_t* cnt = (i & 1) ? w.cnt2 : w.cnt;
-      const int64_t lo = bound[i], hi = bound[i + 1];
-      if (i >= c_lo + 2) HIP_TRY(hipStreamWaitEvent(sg, ev_done[i - 2], 0));      // list set is free again
-      GemmArgs g{};
-      g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.k_split = ix->d_dlr / TILE_K; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant; g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum;
-      g.seq_lo = lo; g.seq_hi = hi; g.map_mode = scatter ? 3 : 2; g.period = S; g.head = head; g.n_tiles = ix->n_tiles; g.perm_mul = perm_mul; g.perm_n = n_main;
-      g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows; g.thr = w.thr_hat; g.cand = cand; g.cnt = cnt;
-      g.cap = (uint32_t)w.cap; g.n_queries = Q;
-      if (two_tier) g.tier = w.tier_dev + (i & 1);
-      HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)w.q_pad * 4, sg));
-      if (!async_ctl) HIP_TRY(hipMemsetAsync(w.d_max2 + 4 * (i & 1), 0, 16, sg));
-      tm.begin_on(T_GEMM, sg); HIP_TRY(launch_gemm_filter(g, sg)); tm.end_on(sg);
-      ix->last_gemm_kernel = g_last_gemm_kernel;
-      if (!async_ctl) {       // the host-driven controller sizes the per-candidate launches from the list lengths; the enqueue-only one leaves them on the device
-        HIP_TRY(launch_max_u32(cnt, Q, w.d_max2 + 4 * (i & 1), (unsigned long long*)(w.d_max2 + 4 * (i & 1) + 2), sg));
-        HIP_TRY(hipMemcpyAsync(w.h_pinned2 + 16 * (i & 1), w.d_max2 + 4 * (i & 1), 16, hipMemcpyDeviceToHost, sg));
-      }
-      HIP_TRY(hipEventRecord(ev_gemm[i], sg));
-      const double rows = (double)(hi - lo) * TILE_ROWS;
-      st.phases++;
-      st.gemm_rows += (int64_t)rows;
-      st.gemm_flops += 2.0 * (double)w.q_pad * rows * (double)ix->kt;
-      st.gemm_flops_alg += 2.0 * (double)Q * rows * (double)ix->k;
-      return DHR_OK;
-    };
-    (void)h;
-    if ((rc = enqueue_gemm(c_lo)) != DHR_OK) return rc;
-    for (int i = c_lo; i < c_hi; ++i) {
-      if (i + 1 < c_hi && (rc = enqueue_gemm(i + 1)) != DHR_OK) return rc;
-      if (async_ctl) {
-        uint2* cand_a = (i & 1) ? w.cand2 : w.cand;
-        uint32_t* cnt_a = (i & 1) ? w.cnt2 : w.cnt;
-        if (sb != sg) HIP_TRY(hipStreamWaitEvent(sb, ev_gemm[i], 0));
-        if ((rc = rescore_select_async(ix, w, Q, gate, sel, cand_a, cnt_a, w.thr_hat, tm, sb, nullptr, nullptr, two_tier ? ((i & 1) ? w.ovf2 : w.ovf) : nullptr)) != DHR_OK) return rc;
-        if (ix->progressive_thr) HIP_TRY(launch_raise_thr(w.thr_hat, sel.thr, Q, sb));
-        if (extrapolate && i + 1 < M) {
-          const double f = (double)(head + n_sample + bound[i + 1]) / (double)ix->n_tiles;
-          const int r = (int)std::ceil((double)k * f + 6.0 * std::sqrt((double)k * f * (1.0 - f)) + 4.0);
-          if (r < k) HIP_TRY(launch_raise_thr_rank(w.thr_hat, w.tau_hat, w.topk_keys, w.kp, r, w.margin, Q, sb));
-        }
-        HIP_TRY(hipEventRecord(ev_done[i], sb));
-        continue;
-      }
-      HIP_TRY(hipEventSynchronize(ev_gemm[i]));
-      const uint32_t maxc = *(const uint32_t*)(w.h_pinned2 + 16 * (i & 1));
-      unsigned long long sumc;
-      memcpy(&sumc, w.h_pinned2 + 16 * (i & 1) + 8, 8);
-      st.candidates_bound += (int64_t)sumc;
-      uint2* cand = (i & 1) ? w.cand2 : w.cand;
-      uint32_t* cnt = (i & 1) ? w.cnt2 : w.cnt;
-      if (getenv("DHR_DEBUG_PLAN")) fprintf(stderr, "[dhr] main chunk %d: tiles [%lld, %lld)\n", i, (long long)bound[i], (long long)bound[i + 1]);
-      HIP_TRY(launch_mark_overflow(cnt, (uint32_t)w.cap, Q, w.fail_flags, sb));
-      if ((rc = rescore_select(ix, w, Q, gate, sel, cand, cnt, w.thr_hat, maxc, tm, st, sb, (int64_t)sumc, w.fail_flags)) != DHR_OK) return rc;
-      if (ix->progressive_thr) HIP_TRY(launch_raise_thr(w.thr_hat, sel.thr, Q, sb));   // later chunks filter with the running exact thresholds
-      if (extrapolate && i + 1 < M) {
-        const double f = (double)(head + n_sample + bound[i + 1]) / (double)ix->n_tiles;
-        const int r = (int)std::ceil((double)k * f + 6.0 * std::sqrt((double)k * f * (1.0 - f)) + 4.0);      // 6 sigma: a failure costs a whole extra pass for its query tile
-        if (r < k) HIP_TRY(launch_raise_thr_rank(w.thr_hat, w.tau_hat, w.topk_keys, w.kp, r, w.margin, Q, sb));
-      }
-      HIP_TRY(hipEventRecord(ev_done[i], sb));
-    }
-    HIP_TRY(hipStreamWaitEvent(s, ev_done[c_hi - 1], 0));
+  int rc;
+  if ((rc = main_streams(c, mp)) != DHR_OK) return rc;
+  hipStream_t sg = mp.sg, sb = mp.sb;
+  mp.two_tier = c.async_ctl && w.arena > 0;
+  // mid protocol: chunk 0 is the slice dhr_search_mid runs (MID_SHARE16 / 16 of the pass), the plain plan covers the rest
+  mp.bound = plan::main_chunk_bounds(p.n_main, main_chunk_count(c, mp, mid_proto), mid_proto ? p.mid_offset : 0);
+  if (mid_proto) mp.bound.insert(mp.bound.begin(), 0);
+  mp.M = (int)mp.bound.size() - 1;
+  mp.c_lo = c.after_mid ? 1 : 0; mp.c_hi = mid ? 1 : mp.M;
+  if (mp.two_tier) {
+    // second tier of the bound lists, ONE plan for every chunk of the pass (both list sets share it): from the lists of the last sampled
+    // phase, scaled to the largest chunk -- the pass filters with thresholds at least as high as that phase did, and they only rise
+    int64_t big = 0;
+    for (int i = 0; i < mp.M; ++i) big = std::max(big, mp.bound[i + 1] - mp.bound[i]);
+    HIP_TRY(launch_plan_overflow(w.plan_rows > 0 ? w.cnt_plan : nullptr, w.plan_rows > 0 ? (double)(big * TILE_ROWS) / (double)w.plan_rows : 0.0, (uint32_t)w.cap,
+                                 (uint32_t)(w.cap_deep - w.cap), (uint32_t)w.arena, c.Q, w.ovf_off, w.ovf_cap, s));
   }
-  if (stage == 3) ix->pend.mid = true;
-  if (stage >= 2) return DHR_OK;                                // the caller verifies across shards
-  // ---- verify; queries whose list overflowed or that found < k rows above tau_hat are redone exactly
-  if (getenv("DHR_DEBUG_FAIL")) {        // diagnostics: which queries are about to be redone, and why
-    std::vector<uint32_t> ff(Q); std::vector<float> th(Q);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(ff.data(), w.fail_flags, (size_t)Q * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(th.data(), w.tau_hat, (size_t)Q * 4, hipMemcpyDeviceToHost);
-    for (int q = 0; q < Q; ++q) {
-      uint64_t key = 0;
-      (void)hipMemcpy(&key, w.topk_keys + (size_t)q * w.kp + (k - 1), 8, hipMemcpyDeviceToHost);
-      const float kth = key ? ordered_f32((uint32_t)(key >> 32)) : -INFINITY;
-      if (ff[q] || !(kth >= th[q])) fprintf(stderr, "[dhr] depth %d query %d will be redone: list overflow %u, k-th best %.6f, threshold %.6f\n", depth, q, ff[q], kth, th[q]);
-    }
+  // The GEMM / aux streams enter the pass behind everything the caller's stream holds so far -- INCLUDING the plan above: with CU masks
+  // (DHR_PARAM_AUX_CUS / GEMM_EXCLUSIVE) the bound GEMM runs on s_gemm and refine on s_aux, and until round 5 they waited on an event
+  // recorded BEFORE the plan kernel, so a GEMM that spilled past `cap` could pair a new ovf_cap with an old ovf_off.
+  if (sg != s || sb != s) {
+    hipEvent_t ev_enter = nullptr;
+    HIP_TRY(mp.evs.add(&ev_enter, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ev_enter, s));
+    if (sg != s) HIP_TRY(hipStreamWaitEvent(sg, ev_enter, 0));
+    if (sb != s) HIP_TRY(hipStreamWaitEvent(sb, ev_enter, 0));
   }
+  mp.ev_gemm.resize(mp.M); mp.ev_done.resize(mp.M);
+  for (int i = 0; i < mp.M; ++i) {
+    HIP_TRY(mp.evs.add(&mp.ev_gemm[i], hipEventDisableTiming));
+    HIP_TRY(mp.evs.add(&mp.ev_done[i], hipEventDisableTiming));
+  }
+  if ((rc = main_chunks(c, mp)) != DHR_OK) return rc;
+  HIP_TRY(hipStreamWaitEvent(s, mp.ev_done[mp.c_hi - 1], 0));
+  return DHR_OK;
+}
+
+// ---- step 4 (whole searches): verify; queries whose list overflowed or that found < k rows above tau_hat are redone exactly
+static void debug_report_failures(const Search& c) {        // DHR_DEBUG_FAIL: which queries are about to be redone, and why
+  const Workspace& w = c.w; const int Q = c.Q;
+  std::vector<uint32_t> ff(Q); std::vector<float> th(Q);
+  (void)hipStreamSynchronize(c.s);
+  (void)hipMemcpy(ff.data(), w.fail_flags, (size_t)Q * 4, hipMemcpyDeviceToHost);
+  (void)hipMemcpy(th.data(), w.tau_hat, (size_t)Q * 4, hipMemcpyDeviceToHost);
+  for (int q = 0; q < Q; ++q) {
+    uint64_t key = 0;
+    (void)hipMemcpy(&key, w.topk_keys + (size_t)q * w.kp + (c.k - 1), 8, hipMemcpyDeviceToHost);
+    const float kth = key ? ordered_f32((uint32_t)(key >> 32)) : -INFINITY;
+    if (ff[q] || !(kth >= th[q])) fprintf(stderr, "[dhr] depth %d query %d will be redone: list overflow %u, k-th best %.6f, threshold %.6f\n", c.depth, q, ff[q], kth, th[q]);
+  }
+}
+static int verify_and_redo(Search& c) {
+  dhr_index* ix = c.ix; Workspace& w = c.w; dhr_search_stats& st = c.st; hipStream_t s = c.s; const int Q = c.Q, k = c.k;
+  if (getenv("DHR_DEBUG_FAIL")) debug_report_failures(c);
   HIP_TRY(hipMemsetAsync(w.d_max, 0, 16, s));
   HIP_TRY(launch_max_u32(w.fail_flags, Q, w.d_max + 1, (unsigned long long*)(w.d_max + 2), s));      // overflow marks so far (the verification adds its own below)
   HIP_TRY(launch_verify(w.topk_keys, w.kp, k, w.tau_hat, Q, w.fail_flags, w.d_max, s));
   HIP_TRY(hipMemcpyAsync(w.h_pinned, w.d_max, 16, hipMemcpyDeviceToHost, s));
-  if (async_ctl) HIP_TRY(hipMemcpyAsync(w.h_stats, w.d_stats, 32, hipMemcpyDeviceToHost, s));
+  if (c.async_ctl) HIP_TRY(hipMemcpyAsync(w.h_stats, w.d_stats, 32, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));            // the ONE host read of a search whose first attempt succeeds: how many queries must be redone
-  if (async_ctl) {
+  if (c.async_ctl) {
     st.candidates_bound += (int64_t)((unsigned long long*)w.h_stats)[0];
     st.candidates_exact += (int64_t)((unsigned long long*)w.h_stats)[1];
   }
@@ -938,28 +836,75 @@ int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, i
     if (flags[q]) ids.push_back(q);
   // depth 1 (the same sampling scheme with 16x deeper lists) only cures overflowed lists; a threshold that came out too high would
   // come out too high again from the same sample: those queries go straight to the plain streaming pass
-  int next_depth = depth + 1;
-  if (depth == 0 && (int)n_overflow == 0) next_depth = 2;
+  int next_depth = c.depth + 1;
+  if (c.depth == 0 && (int)n_overflow == 0) next_depth = 2;
   const int nf = (int)ids.size();
-  DevMem tmp_mem;
+  DevMem tmp_mem;          // (releases the scratch on every way out)
   void*& tmp = tmp_mem.p;
   const size_t b32 = (size_t)nf * ix->k_rm * 4, bidx = (size_t)nf * std::max(ix->d_dlr, 8) * 2, bids = (size_t)nf * 4;
   HIP_TRY(hipMalloc(&tmp, b32 + bidx + bids + 64));
   float* f32 = (float*)tmp;
   int16_t* fidx = (int16_t*)((char*)tmp + b32);
   int32_t* d_ids = (int32_t*)((char*)tmp + b32 + bidx);
-  auto done = [&](int code) { return code; };       // (tmp_mem releases the scratch)
-  if (hipMemcpyAsync(d_ids, ids.data(), bids, hipMemcpyHostToDevice, s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "H2D failed"));
+  if (hipMemcpyAsync(d_ids, ids.data(), bids, hipMemcpyHostToDevice, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
   if (launch_gather_queries(w.q32, w.q_idx, ix->k_rm, ix->d_dlr, d_ids, nf, f32, fidx, s) != hipSuccess)
-    return done(set_error(DHR_ERR_HIP, "gather_queries launch failed"));
+    return set_error(DHR_ERR_HIP, "gather_queries launch failed");
   dhr_query_batch sub{};
   sub.n_queries = nf; sub.mem_kind = ix->dlr_pad > 0 ? MEM_DEVICE_PADDED : DHR_MEM_DEVICE; sub.value = f32; sub.value_dtype = DHR_VAL_F32; sub.ld_value = ix->k_rm;
-  sub.index = gate ? fidx : nullptr; sub.index_dtype = gate ? DHR_IDX_I16 : DHR_IDX_NONE; sub.ld_index = ix->d_dlr;
+  sub.index = c.gate ? fidx : nullptr; sub.index_dtype = c.gate ? DHR_IDX_I16 : DHR_IDX_NONE; sub.ld_index = ix->d_dlr;
   Workspace& w2 = ix->ws_fb[next_depth - 1];
-  if ((rc = search_core(ix, w2, &sub, k, next_depth, tm, st, s)) != DHR_OK) return done(rc);
-  if (w2.kp != w.kp) return done(set_error(DHR_ERR_INTERNAL, "fallback workspace mismatch"));
+  int rc;
+  if ((rc = search_core(ix, w2, &sub, k, next_depth, c.tm, st, s)) != DHR_OK) return rc;
+  if (w2.kp != w.kp) return set_error(DHR_ERR_INTERNAL, "fallback workspace mismatch");
   if (launch_scatter_keys(w2.topk_keys, w.topk_keys, w.kp, d_ids, nf, s) != hipSuccess)
-    return done(set_error(DHR_ERR_HIP, "scatter_keys launch failed"));
-  if (hipStreamSynchronize(s) != hipSuccess) return done(set_error(DHR_ERR_HIP, "fallback search failed on the device"));
-  return done(DHR_OK);
+    return set_error(DHR_ERR_HIP, "scatter_keys launch failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "fallback search failed on the device");
+  return DHR_OK;
 }
+
+// ------------------------------------------------------------------------------------------ the driver
+int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, int depth, Timer& tm, dhr_search_stats& st, hipStream_t s,
+                Stage stage, const float* tau_ext) {
+  Search c{ix, w, tm, st, s, stage, depth, k, tau_ext};
+  const bool fresh = c.fresh();
+  c.Q = fresh ? qb->n_queries : ix->pend.Q;
+  c.gate = fresh ? (ix->d_dlr > 0 && qb->index != nullptr && qb->index_dtype != DHR_IDX_NONE) : ix->pend.gate;   // else plain IP
+  c.after_mid = stage == Stage::Finish && ix->pend.state == StagedState::AfterMid;
+  // depth 0: sampled thresholds; depth 1 (queries that failed at depth 0): the same with 16x list capacity;
+  // depth 2: plain streaming, exact for any input
+  c.p = search_plan_of(ix, k, depth, !c.whole());
+  const SearchPlan& p = c.p;
+  int rc;
+  if ((rc = ensure_ws(ix, w, c.Q, k, p.first_valid, depth == 0 ? 1 : 16, c.gate || ix->gated_i8 || ix->resid8 != nullptr)) != DHR_OK) return rc;
+  // first attempt of a sampled search: the controller only enqueues (no host read-backs); DHR_PARAM_ASYNC_CONTROLLER 0 keeps the
+  // host-driven controller (and the fallback depths always use it: it is the one that is exact for any input)
+  c.async_ctl = depth == 0 && p.S >= 2 && ix->async_ctl != 0 && !getenv("DHR_DEBUG_PLAN");
+  SelectArgs& sel = c.sel;
+  sel.topk_keys = w.topk_keys; sel.in_keys = w.rs_keys; sel.ld_keys = w.keys_ld; sel.cap = (uint32_t)w.cap;
+  sel.k = p.r_eff; sel.kp = w.kp; sel.sort_n = select_sort_n(w.kp);
+  sel.k_keep = k;                          // the threshold is the r-th best seen, the list keeps the k best (ties with the final k-th score survive the sampled run)
+  sel.kps = 64; while (sel.kps < k) sel.kps <<= 1; sel.margin = w.margin; sel.tau = w.tau; sel.thr = w.thr;
+  sel.n_queries = c.Q;
+
+  if (fresh && (rc = prepare_and_phase0(c, qb)) != DHR_OK) return rc;
+  if (!fresh && ix->pend.state == StagedState::Complete) return DHR_OK;              // the begin call already finished the search
+  if (!p.sampled) {
+    // plain streaming over all remaining tiles
+    if (p.rest > 0 && (rc = stream_phases(c, p.rest, 1, p.head, p.first_valid)) != DHR_OK) return rc;
+    if (fresh && !c.whole()) staged_open(ix, StagedState::Complete, c.gate, c.Q, k);      // Begin, Pre: only dhr_search_finish is left
+    return DHR_OK;
+  }
+  switch (stage) {
+    case Stage::Whole:
+      if ((rc = sampled_run(c)) != DHR_OK || (rc = main_pass(c)) != DHR_OK) return rc;
+      return verify_and_redo(c);
+    case Stage::Begin: case Stage::Pre: case Stage::BeginRest:
+      return sampled_run(c);                               // the staged search goes on in another call
+    case Stage::Mid: case Stage::Finish:
+      if ((rc = adopt_thresholds(c)) != DHR_OK || (rc = main_pass(c)) != DHR_OK) return rc;
+      if (stage == Stage::Mid) staged_set(ix, StagedState::AfterMid);
+      return DHR_OK;                                       // the caller verifies across shards
+  }
+  return set_error(DHR_ERR_INTERNAL, "unknown search stage");
+}
+

@@ -229,7 +229,10 @@ int dhr_search_rerank(dhr_index* index, const dhr_query_batch* stage1, const dhr
  * how many of its rows reach tau_hat (-1: a candidate list overflowed).  If the counts of all shards
  * sum to >= k (and none is -1) the union of the shard lists contains the global top-k; otherwise
  * those queries are redone with dhr_search.  Replaces one process per shard + merge.result.py.
- * out_sample_scores_dev / tau_hat_dev / out_count_dev are DEVICE pointers. */
+ * out_sample_scores_dev / tau_hat_dev / out_count_dev are DEVICE pointers.
+ * Errors: a staged call (begin, finish, and the optional mid / pre / begin_rest below) that returns an error leaves NO staged search
+ * open on the handle -- its workspace may be half-consumed -- so a later dhr_search_mid / dhr_search_finish is refused ("without a matching
+ * dhr_search_begin"): after an error from any staged call, start again with dhr_search_begin or dhr_search_pre. */
 int32_t dhr_search_sample_rank(const dhr_index* index, int32_t k);
 /* The rank of the union of the shards' samples that defines the common threshold (== dhr_search_sample_rank unless
  * DHR_PARAM_SAMPLE_SHARE > 1): the caller merges the gathered [shards, Q, sample_rank] lists and takes the

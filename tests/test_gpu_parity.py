@@ -1917,6 +1917,45 @@ def test_staged_search_call_sequences(G, monkeypatch):
     fuzz_staged.main()
 
 
+def test_staged_call_that_fails_closes_the_staged_search(G):
+    """A staged entry point that returns an error leaves NO staged search open on the handle: dhr_search_finish fails half-way (the host
+    allocation hook of test_allocation_failures_with_a_device: DHR_ERR_NOMEM, nothing on the device fails), so its workspace is half-consumed
+    and a second dhr_search_finish must be refused like one without a begin; a fresh begin -> finish on the same handle gives the oracle's result."""
+    import torch
+    from dhr_amd import synth, _lib
+    from dhr_amd import dist as D
+    lib = _lib.load()
+    cv, ci, qv, qi = synth.make_pair(57, 40_000, 8, 64, 8)
+    q, k = qv.astype(np.float32), 100
+    ix = G.GipIndex(cv, ci)
+    try:
+        ix.set_param(_lib.PARAM_SAMPLE_PERIOD, 4)
+        r = ix.union_rank(k)
+        assert r > 0 and ix.sample_rank(k) == r           # sampled: dhr_search_finish has the main pass to run
+
+        def begin():
+            return D.common_threshold(torch.stack([ix.search_begin(q, qi, k)]), r)
+        tau = begin()
+        lib.dhr_debug_fail_alloc(1)
+        try:
+            with pytest.raises(_lib.DhrError) as e:
+                ix.search_finish(tau)
+        finally:
+            lib.dhr_debug_fail_alloc(0)
+        assert e.value.status == _lib.ERR_NOMEM and "memory" in str(e.value), e.value
+        with pytest.raises(_lib.DhrError, match="dhr_search_finish without a matching dhr_search_begin") as e:
+            ix.search_finish(tau)
+        assert e.value.status == _lib.ERR_INVALID
+        scores, rows, count = ix.search_finish(begin())
+        scores, rows, count = scores.cpu().numpy(), rows.cpu().numpy(), count.cpu().numpy()
+        assert (count >= k).all(), count
+        c32 = cv.astype(np.float32)
+        for i in range(len(q)):
+            O.check_topk(rows[i], scores[i], O.gip_scores_f64(q[i], qi[i], c32, ci), k)
+    finally:
+        ix.close()
+
+
 def test_random_mode_configurations(G, monkeypatch):
     """A slice of tools/stress_modes.py: the entry points beside the plain search (two-stage modes on the device, dhr_score_rows, the
     index file round trip, the one-process sharded search over ragged shards, the shard reduces on the device and on the host) on

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "dhr_internal.h"
+#include "sharded_plan.h"
 
 struct dhr_comm {
   ncclComm_t comm = nullptr;      // RCCL (dhr_comm_create / dhr_comm_wrap), or
@@ -53,6 +54,7 @@ struct dhr_comm {
 namespace {
 
 using namespace dhr;
+using namespace dhr::sharded;      // sharded_plan.h: Block, ListBlock, RankVote, StepPlan -- every block of a step is laid out there
 
 #define SH_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dhr_set_error_message(DHR_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(e_)).c_str()); } while (0)
 #define SH_NCCL(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) return dhr_set_error_message(DHR_ERR_HIP, (std::string(#x) + ": " + ncclGetErrorString(r_)).c_str()); } while (0)
@@ -69,19 +71,13 @@ using namespace dhr;
 //                THIS control flow with world size 2 / 3 over gloo (tests/test_dist_gloo.py) -- until round 4 those tests ran
 //                a torch restatement of it (dhr_amd/dist.py sharded_search_torch, now deleted).
 // ------------------------------------------------------------------------------------------------------------------------------------
-// One rank's share of an all-gather: [payload | status record (16 B)], `stride` bytes apart in the receive buffer.  The status record is what
-// makes a failed step COLLECTIVE (round 6): a rank whose local work failed (a HIP error, out of memory, a failing shard callback) does not leave
+// Every block of an all-gather ends in a status record (Block, sharded_plan.h).  The record is what makes a failed step COLLECTIVE (round 6): a rank whose local work failed (a HIP error, out of memory, a failing shard callback) does not leave
 // the sequence of collectives -- it skips its remaining local work, keeps issuing the step's all-gathers with the agreed sizes, and its status
 // travels in the record of every block it sends.  A transport whose blocks pass through host memory (the caller's host transport, host shards)
 // reads the records right behind each gather and every rank returns from the SAME gather; over RCCL (and in the one-process form) the records are
 // folded on the device into the word that the step's one host read fetches anyway, and every rank returns at the end of the step.  The failing
 // rank returns its own status and message, the others DHR_ERR_PEER naming it.  (Until round 5 the failing rank returned at once and the others
 // waited in their next collective for the transport's timeout.)
-struct Block { size_t payload, stride; };
-inline Block block_of(size_t payload) {
-  payload = (payload + 15) & ~(size_t)15;
-  return {payload, (payload + 16 + 255) & ~(size_t)255};
-}
 // first failing rank of a gathered buffer in HOST memory (0: none)
 inline int host_block_status(const void* blocks, int world, const Block& b, int* who) {
   for (int w = 0; w < world; ++w) {
@@ -108,10 +104,11 @@ struct Backend {
   virtual int union_rank(int i, int k) = 0;
   virtual int begin(int i, const dhr_query_batch* qb, int k, float* sample) = 0;
   virtual int finish(int i, const float* tau, float* ls, int64_t* lr, int32_t* cnt) = 0;
-  virtual int mid_ranks(int i, int k, int* r_local, int* r_union) = 0;   // second agreement (dhr_search_mid_ranks); r_local 0: the shard has no such step
+  // the (local, union) ranks of an optional agreement: MID the second agreement (dhr_search_mid_ranks / dhr_search_mid), PRE the first agreement in
+  // two rounds (dhr_search_pre_ranks / dhr_search_pre / dhr_search_begin_rest); r_local 0: the shard has no such step
+  enum Stage { MID, PRE };
+  virtual int stage_ranks(int i, Stage stage, int k, int* r_local, int* r_union) = 0;
   virtual int mid(int i, const float* tau, int r_local, float* scores) = 0;
-  // first agreement in two rounds (dhr_search_pre_ranks / dhr_search_pre / dhr_search_begin_rest); r_local 0: the shard has no such step
-  virtual int pre_ranks(int i, int k, int* r_local, int* r_union) = 0;
   virtual int pre(int i, const dhr_query_batch* qb, int k, int r_local, float* scores) = 0;
   virtual int begin_rest(int i, const float* tau, float* sample) = 0;
   virtual int search(int i, const dhr_query_batch* qb, int k, float* s, int64_t* r) = 0;
@@ -122,10 +119,10 @@ struct Backend {
   virtual int gather(const std::vector<const void*>& send, const std::vector<void*>& recv, const Block& b) = 0;
   // ... the others fold the records of a gathered buffer into rec[1] (status of the first failing rank) / rec[2] (that rank), on the device
   virtual int fold_status(int i, const void* gathered, const Block& b, int32_t* rec) = 0;
-  virtual int min_over_ranks(int32_t v[12]) = 0;                // element-wise minimum over all processes; one host read
-  // gathered [world] blocks of [Q, r] sorted sample scores -> tau[q] = the ru-th best of the union
-  virtual int union_threshold(int i, const float* gathered, const Block& b, int Q, int r, int ru, float* tau) = 0;
-  virtual int union_threshold2(int i, const float* gathered, const Block& b, int Q, int r, int ru, float* tau) = 0;   // the same, tau[q] = max(tau[q], that)
+  // the 48 bytes of this process's rank vote -> all = [world][48 bytes] in HOST memory (SPMD only); one host read
+  virtual int exchange_vote(const RankVote& mine, int32_t* all) = 0;
+  // gathered [world] blocks of [Q, r] sorted sample scores -> tau[q] = the ru-th best of the union; raise: tau[q] = max(tau[q], that)
+  virtual int union_threshold(int i, const float* gathered, const Block& b, int Q, int r, int ru, float* tau, bool raise) = 0;
   // counts [world] blocks of [Q] -> compact list of failed query ids + their number in rec[0] (a query is complete iff the union holds >= k rows,
   // no shard overflowed (-1) and no shard's share exceeds the gathered prefix kk)
   virtual int flag_failures(int i, const int32_t* counts, const Block& b, int Q, int k, int kk, int32_t* fail_ids, int32_t* rec) = 0;
@@ -136,13 +133,31 @@ struct Backend {
   virtual int read_failed(const std::vector<int32_t*>& rec, const std::vector<int32_t*>& fail_ids, std::vector<int32_t>& ids, int* peer_status, int* peer_rank) = 0;
   virtual int sub_batch(int i, const dhr_query_batch* in, const std::vector<int32_t>& ids, dhr_query_batch* out, int32_t** ids_mem) = 0;
   virtual int scatter(int i, const float* s, const int64_t* r, const int32_t* ids_mem, int F, int k, float* os, int64_t* orow) = 0;
-  virtual int sync(int i) = 0;
 };
 
-int prefix_len(int k, int world) {
-  if (world <= 2) return k;
-  const int kk = ((3 * k + world - 1) / world + 64 + 63) / 64 * 64;
-  return std::min(k, kk);
+// The rank agreement on the wire: ONE exchange of 48 bytes per process, reduced by RankVote::reduce.  No allocation precedes the exchange for up to 64
+// ranks (a rank that could not allocate must still be able to say so: vote_status_only).
+int reduce_over_ranks(Backend& B, RankVote& vote) {
+  if (B.world <= B.n_local) return DHR_OK;         // one process: nobody to agree with
+  int32_t few[64 * RankVote::SLOTS];
+  std::vector<int32_t> many;
+  if (B.world > 64) many.resize((size_t)B.world * RankVote::SLOTS);
+  int32_t* all = B.world > 64 ? many.data() : few;
+  SH_TRY(B.exchange_vote(vote, all));
+  vote.reduce(all, B.world);
+  return DHR_OK;
+}
+// The vote of a rank that has nothing to report but a failure: it takes part in the exchange the others are about to enter (or are waiting in) with its
+// status and zero ranks, so that every rank abandons the step there.  Never throws; keeps the thread's error message.
+void vote_status_only(Backend& B, int status) noexcept {
+  char keep[1024];
+  snprintf(keep, sizeof(keep), "%s", dhr_last_error());
+  try {
+    RankVote vote = RankVote::status_only(status);
+    (void)reduce_over_ranks(B, vote);
+  } catch (...) {
+  }
+  (void)dhr_set_error_message(status, keep);
 }
 
 // host-side pieces shared by both backends ------------------------------------------------------------------------------------------
@@ -186,45 +201,47 @@ struct Step {
   std::vector<int> st;             // first failure of local shard i (DHR_OK: none); its later local work is skipped
   std::vector<int32_t*> rec;       // per local shard: {failed queries, first failing rank's status, that rank, -} in the shard's memory
   char msg[1024];                  // dhr_last_error() of the first local failure (later calls overwrite the thread's record)
-  // What this rank still OWES the other ranks (round 6, second half: a failure OUTSIDE the local work -- a std::bad_alloc in the control flow itself, a block
-  // that cannot be allocated -- used to return at once and leave the others in their next collective until the transport's timeout): the rank agreement
-  // is one exchange of a fixed size; once the ranks are agreed the blocks of the step's all-gathers follow from them (owe(), fixed storage: planning
-  // must not allocate).  leave() pays the debt with this rank's status in every block.
-  Block plan[8];
-  int n_plan = 0, done = 0;        // planned all-gathers; how many of them have been issued
+  std::vector<const void*> send;   // per local shard: the block it sends in the all-gather at hand, and where the [world] blocks arrive (open())
+  std::vector<void*> recv;
+  // What this rank still OWES the others (a failure OUTSIDE the local work -- a std::bad_alloc in the control flow, a block that cannot be allocated -- must
+  // not leave them in their next collective until the transport's timeout): the rank agreement, one exchange of a fixed size, then the all-gathers that
+  // follow from the agreed ranks (StepPlan, fixed storage).  leave() pays the debt with this rank's status in every block.
+  StepPlan plan;
+  int done = 0;                    // how many of the planned all-gathers have been issued
   bool agreed = false;             // the rank agreement has been issued (successfully or not: it is never issued twice)
   bool over = false;               // the step is over on EVERY rank at this point of the sequence (a failure all of them have just read in the same
                                    // exchange) or the transport itself failed: no further collective may be issued
-  explicit Step(Backend& b) : B(b), spmd(b.world > b.n_local), st(b.n_local, DHR_OK), rec(b.n_local, nullptr) { msg[0] = 0; }
-  void owe(const Block& b) { if (n_plan < 8) plan[n_plan++] = b; }
-  // The way out of a step that failed with `status` somewhere the sequence above does not cover: the agreement with the status in v[10] if it is still
-  // owed, else every planned all-gather not yet issued, with the status in its record (host transports end the step on every rank at the first such
-  // gather; with device-side records the others run the plan to its end and read the status there).  Never throws; keeps the thread's error message.
+  explicit Step(Backend& b) : B(b), spmd(b.world > b.n_local), st(b.n_local, DHR_OK), rec(b.n_local, nullptr), send(b.n_local), recv(b.n_local) { msg[0] = 0; }
+  // scratch of local shard i; THE out-of-memory message of the control flow
+  template <class T> int alloc(int i, size_t bytes, T** p) {
+    *p = (T*)B.alloc(i, bytes);
+    return *p ? DHR_OK : dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
+  }
+  // local shard i's block `b` of the all-gather at hand (-> *blk, send[i]) and its receive buffer (-> recv[i])
+  template <class T> int open(int i, const Block& b, T** blk) {
+    SH_TRY(alloc(i, b.stride, blk));
+    send[i] = *blk;
+    return alloc(i, (size_t)B.world * b.stride, &recv[i]);
+  }
+  // The way out of a step that failed with `status`.  SPMD: a local failure never leaves the sequence -- the vote with the status if it is still owed, else
+  // every planned all-gather not yet issued, with the status in its record (host transports end the step on every rank at the first such gather; with
+  // device-side records the others run the plan to its end and read it there).  Nothing once `over` is set.  Never throws; keeps the thread's message.
   void leave(int status) noexcept {
     if (!spmd || status == DHR_OK || over) return;
+    if (!agreed) { agreed = true; vote_status_only(B, status); return; }
     char keep[1024];
     snprintf(keep, sizeof(keep), "%s", dhr_last_error());
     try {
-      if (!agreed) {
-        agreed = true;
-        int32_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, status, 0};
-        (void)B.min_over_ranks(v);
-      } else {
-        std::vector<const void*> send(B.n_local);
-        std::vector<void*> recv(B.n_local);
-        while (done < n_plan) {
-          const Block& b = plan[done];
-          bool ok = true;
-          for (int i = 0; i < B.n_local && ok; ++i) {
-            void* blk = B.alloc(i, b.stride);
-            recv[i] = B.alloc(i, (size_t)B.world * b.stride);
-            ok = blk && recv[i] && B.zero(i, blk, b.stride) == DHR_OK && B.put_status(i, blk, b, st[i] != DHR_OK ? st[i] : status) == DHR_OK;
-            send[i] = blk;
-          }
-          if (!ok) break;
-          ++done;
-          if (B.gather(send, recv, b) != DHR_OK) { over = true; break; }
+      while (done < plan.n) {
+        const Block& b = plan.block(plan.order[done]);
+        bool ok = true;
+        for (int i = 0; i < B.n_local && ok; ++i) {
+          void* blk = nullptr;
+          ok = open(i, b, &blk) == DHR_OK && B.zero(i, blk, b.stride) == DHR_OK && B.put_status(i, blk, b, st[i] != DHR_OK ? st[i] : status) == DHR_OK;
         }
+        if (!ok) break;
+        ++done;
+        if (B.gather(send, recv, b) != DHR_OK) { over = true; break; }
       }
     } catch (...) {
     }
@@ -244,21 +261,20 @@ struct Step {
     return DHR_OK;
   }
   int init() {
-    for (int i = 0; i < B.n_local; ++i) {
-      rec[i] = (int32_t*)B.alloc(i, 256);
-      if (!rec[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-      SH_TRY(B.zero(i, rec[i], 16));
-    }
+    for (int i = 0; i < B.n_local; ++i) { SH_TRY(alloc(i, 256, &rec[i])); SH_TRY(B.zero(i, rec[i], 16)); }
     return DHR_OK;
   }
-  // the all-gather of one block per shard, status records included
-  int gather(const std::vector<const void*>& send, const std::vector<void*>& recv, const Block& b) {
-    if (done < n_plan && (plan[done].stride != b.stride || plan[done].payload != b.payload))
+  // the planned all-gather `name` of the opened blocks, status records included; that it is the NEXT one the plan lists is an internal check
+  int gather(StepPlan::Name name) {
+    if (done >= plan.n || plan.order[done] != name)
       return dhr_set_error_message(DHR_ERR_INTERNAL, "sharded step: an all-gather does not match the step's plan");
+    const Block& b = plan.block(name);
     for (int i = 0; i < B.n_local; ++i) SH_TRY(B.put_status(i, const_cast<void*>(send[i]), b, st[i]));
     ++done;
     const int rc = B.gather(send, recv, b);
-    if (rc != DHR_OK) over = true;                                      // a failure every rank has read in this gather, or a broken transport
+    // host-visible transports end the step on EVERY rank at the first gather that carries a failure (or the transport broke): no collective after it;
+    // device-side records are folded below and read in the step's one host read
+    if (rc != DHR_OK) over = true;
     if (rc == DHR_ERR_PEER && own() != DHR_OK) return own_error();      // this rank is the one that failed
     SH_TRY(rc);
     for (int i = 0; i < B.n_local; ++i) SH_TRY(B.fold_status(i, recv[i], b, rec[i]));
@@ -266,95 +282,175 @@ struct Step {
   }
   // the verdict of a step whose status words travelled on the device (peer_status / peer_rank from the host read)
   int verdict(int peer_status, int peer_rank) const {
-    if (own() != DHR_OK) return own_error();
-    if (peer_status != 0) return peer_error(peer_rank, peer_status);
-    return DHR_OK;
+    return own() != DHR_OK ? own_error() : peer_status != 0 ? peer_error(peer_rank, peer_status) : DHR_OK;
   }
 };
 #define SH_LOCAL(i, expr) SH_TRY(S.local(i, [&]() -> int { return (expr); }))
 
-// local thresholds for a (sub-)batch: every shard searches with k, full lists gathered (ONE all-gather: scores and rows in one block) and
-// merged.  out_* [n_q, k] per local shard.
-// the block of the step's last all-gather: [Q] counts | [Q, kk] scores | [Q, kk] rows
-inline size_t final_off_s(int Q) { return ((size_t)Q * 4 + 15) & ~(size_t)15; }
-inline size_t final_off_r(int Q, int kk) { return (final_off_s(Q) + (size_t)Q * kk * 4 + 15) & ~(size_t)15; }
-inline Block final_block(int Q, int kk) { return block_of(final_off_r(Q, kk) + (size_t)Q * kk * 8); }
-inline Block local_block(int Q, int k) { return block_of((((size_t)Q * k * 4 + 15) & ~(size_t)15) + (size_t)Q * k * 8); }
-int local_path(Step& S, const std::vector<dhr_query_batch>& qb, int k, const std::vector<float*>& out_s, const std::vector<int64_t*>& out_r) {
-  Backend& B = S.B;
-  const int nl = B.n_local, world = B.world, Q = qb[0].n_queries;
-  const size_t off_r = ((size_t)Q * k * 4 + 15) & ~(size_t)15;
-  const Block b = local_block(Q, k);
-  std::vector<const void*> send(nl);
-  std::vector<void*> recv(nl);
-  for (int i = 0; i < nl; ++i) {
-    char* blk = (char*)B.alloc(i, b.stride);
-    recv[i] = B.alloc(i, (size_t)world * b.stride);
-    if (!blk || !recv[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-    SH_LOCAL(i, B.search(i, &qb[i], k, (float*)blk, (int64_t*)(blk + off_r)));
-    send[i] = blk;
-  }
-  SH_TRY(S.gather(send, recv, b));
-  for (int i = 0; i < nl; ++i)
-    SH_LOCAL(i, B.merge(i, Q, k, (const float*)recv[i], (const int64_t*)((const char*)recv[i] + off_r), b, k, out_s[i], out_r[i]));
-  return DHR_OK;
-}
-
-// agree on the sample ranks: all shards must report the same local share r > 0 AND the same union rank ru (local_sample_rank is many-to-one:
-// unequal shard sizes or per-handle sample periods can give equal shares of different union ranks, and the count check of step 4 assumes
-// ONE common threshold column).  Not cached: the answer depends on every rank's shard size and sample period, a communicator outlives the
-// index handles, and a rank that hit a cache the others missed would skip a collective they issue.
-// The ranks of the SECOND agreement (Backend::mid_ranks) ride along: shards whose sizes differ by a tile may compute ranks that differ by one;
-// every shard then uses the LARGEST (a lower threshold: still valid), and the step is skipped when some shard has none.
-// The ranks of the two-round FIRST agreement (Backend::pre_ranks) travel the same way: the largest over the shards, none if some shard has none.
-// v[10] carries the ranks' status so far (a rank whose set-up failed says so here instead of staying away from the exchange).
-int agree_rank(Step& S, int k, int* r_out, int* ru_out, int* rl_mid_out, int* ru_mid_out, int* rl_pre_out, int* ru_pre_out) {
-  Backend& B = S.B;
-  int r = B.sample_rank(0, k);
-  int ru = B.union_rank(0, k);
-  int ml_min = 1 << 30, ml_max = 0, mu_max = 0;
-  int pl_min = 1 << 30, pl_max = 0, pu_max = 0;
-  for (int i = 0; i < B.n_local; ++i) {
-    if (B.sample_rank(i, k) != r || B.union_rank(i, k) != ru) r = 0;
-    int ml = 0, mu = 0;
-    SH_LOCAL(i, B.mid_ranks(i, k, &ml, &mu));
-    if (ml <= 0 || mu <= 0) ml = mu = 0;
-    ml_min = std::min(ml_min, ml); ml_max = std::max(ml_max, ml); mu_max = std::max(mu_max, mu);
-    int pl = 0, pu = 0;
-    SH_LOCAL(i, B.pre_ranks(i, k, &pl, &pu));
-    if (pl <= 0 || pu <= 0) pl = pu = 0;
-    pl_min = std::min(pl_min, pl); pl_max = std::max(pl_max, pl); pu_max = std::max(pu_max, pu);
-  }
-  int32_t v[12] = {r, -r, ru, -ru, ml_min, -ml_max, -mu_max, pl_min, -pl_max, -pu_max, S.own(), 0};
-  S.agreed = true;
-  { const int rc_x = B.min_over_ranks(v); if (rc_x != DHR_OK) { S.over = true; return rc_x; } }
-  if (v[10] != DHR_OK) S.over = true;                 // every rank reads the same v[10] and leaves here
-  if (v[10] != DHR_OK) return S.own() != DHR_OK ? S.own_error() : dhr_set_error_message(DHR_ERR_PEER, "another rank failed while setting up this sharded step; the step was abandoned on every rank");
-  *r_out = (v[0] == r && -v[1] == r && v[2] == ru && -v[3] == ru) ? r : 0;
-  *ru_out = ru;
-  *rl_mid_out = v[4] > 0 ? -v[5] : 0;
-  *ru_mid_out = v[4] > 0 ? -v[6] : 0;
-  *rl_pre_out = v[7] > 0 ? -v[8] : 0;
-  *ru_pre_out = v[7] > 0 ? -v[9] : 0;
-  return DHR_OK;
-}
-// DHR_PARAM_SAMPLE_SHARE is handle state: the sharded entry points set it for their own staged calls and put 1 back on every way out, so
-// that a later dhr_search_begin / finish on the same handle (another shard count, or none) does not inherit a stale share
+// DHR_PARAM_SAMPLE_SHARE is handle state: the sharded entry points set it for their own staged calls and put 1 back on EVERY way out, so that a later
+// dhr_search_begin / finish on the same handle does not inherit a stale share; and a step that failed between begin and finish (arena out of memory, a
+// transport error, a failed mid step) must not leave the handle "pending": dhr_score_rows refuses one.  After a completed step the abort is a no-op.
 struct ShareGuard {
   Backend& B;
-  // (and a step that failed between begin and finish -- arena out of memory, a transport error, a failed mid step -- must not leave the
-  // handle "pending": dhr_score_rows refuses a pending handle; after a completed step this is a no-op)
   ~ShareGuard() { for (int i = 0; i < B.n_local; ++i) { (void)B.set_share(i, 1); B.abort(i); } }
 };
 
 thread_local int g_last_repairs = 0;      // queries the calling thread's last sharded search redid with local thresholds (dhr_debug_sharded_repairs)
 
-static int sharded_body(Step& S, const dhr_query_batch* qb_in, int k, float* const* out_s_in, int64_t* const* out_r_in);
-// The step and its way out: whatever the body returns or throws, a rank that fails does not leave the others waiting (Step::leave).  out_s / out_r: one
-// [Q, k] device (host shards: host) array per LOCAL shard.
+// ---- the steps of the driver (sharded_body), in the order of the sequence at the top of this file ---------------------------------------------------
+// Agree on the ranks: every shard reports (r, ru) and its optional mid / pre ranks, the processes exchange ONE RankVote (sharded_plan.h says what
+// survives).  Not cached: the answer depends on every rank's shard size and sample period, a communicator outlives the index handles, and a rank
+// that hit a cache the others missed would skip a collective they issue.
+int agree_ranks(Step& S, int k, Ranks* agreed) {
+  Backend& B = S.B;
+  std::vector<ShardRanks> mine(B.n_local);
+  for (int i = 0; i < B.n_local; ++i) {
+    mine[i].r = B.sample_rank(i, k);
+    mine[i].ru = B.union_rank(i, k);
+    SH_LOCAL(i, B.stage_ranks(i, Backend::MID, k, &mine[i].rl_mid, &mine[i].ru_mid));
+    SH_LOCAL(i, B.stage_ranks(i, Backend::PRE, k, &mine[i].rl_pre, &mine[i].ru_pre));
+  }
+  RankVote vote = RankVote::pack(mine.data(), B.n_local, S.own());
+  S.agreed = true;
+  { const int rc_x = reduce_over_ranks(B, vote); if (rc_x != DHR_OK) { S.over = true; return rc_x; } }
+  *agreed = vote.unpack();
+  if (agreed->status == DHR_OK) return DHR_OK;
+  S.over = true;                                      // every rank reads the same status and leaves here
+  return S.own() != DHR_OK ? S.own_error() : dhr_set_error_message(DHR_ERR_PEER, "another rank failed while setting up this sharded step; the step was abandoned on every rank");
+}
+
+// One threshold agreement (steps 1a, 1-2 and 2b are this round): every shard's `fill(i, scores)` writes its r_local best scores per query into its
+// block `name` of the plan, the blocks are gathered, and the r_union-th best of the union becomes tau (raise: tau only rises to it).
+template <class Fill>
+int score_round(Step& S, StepPlan::Name name, int r_local, int r_union, bool raise, const std::vector<float*>& tau, Fill&& fill) {
+  Backend& B = S.B;
+  const Block& b = S.plan.block(name);
+  for (int i = 0; i < B.n_local; ++i) {
+    float* scores = nullptr;
+    SH_TRY(S.open(i, b, &scores));
+    SH_LOCAL(i, fill(i, scores));
+  }
+  SH_TRY(S.gather(name));
+  for (int i = 0; i < B.n_local; ++i) SH_LOCAL(i, B.union_threshold(i, (const float*)S.recv[i], b, S.plan.Q, r_local, r_union, tau[i], raise));
+  return DHR_OK;
+}
+
+// 3-5: main passes; ONE all-gather of [counts | list prefixes: scores | rows] per shard, failure flags, reduce
+int main_pass(Step& S, const std::vector<float*>& tau, std::vector<int32_t*>& fail_ids, float* const* out_s, int64_t* const* out_r) {
+  Backend& B = S.B;
+  const ListBlock& L = S.plan.final_;
+  const int nl = B.n_local, Q = S.plan.Q, k = S.plan.k, kk = S.plan.kk;
+  for (int i = 0; i < nl; ++i) {
+    char* blk = nullptr;
+    SH_TRY(S.open(i, L.b, &blk));
+    SH_TRY(S.alloc(i, (size_t)Q * 4, &fail_ids[i]));
+    float* ls = L.scores(blk);                   // kk == k: the full lists ARE the prefixes, straight into the block
+    int64_t* lr = L.rows(blk);
+    if (kk < k) { SH_TRY(S.alloc(i, (size_t)Q * k * 4, &ls)); SH_TRY(S.alloc(i, (size_t)Q * k * 8, &lr)); }
+    SH_LOCAL(i, B.finish(i, tau[i], ls, lr, L.counts(blk)));
+    if (kk < k) SH_LOCAL(i, B.prefix(i, ls, lr, k, kk, Q, L.scores(blk), L.rows(blk)));
+  }
+  SH_TRY(S.gather(StepPlan::FINAL));
+  for (int i = 0; i < nl; ++i) {
+    SH_LOCAL(i, B.flag_failures(i, L.counts(S.recv[i]), L.b, Q, k, kk, fail_ids[i], S.rec[i]));
+    SH_LOCAL(i, B.merge(i, Q, kk, L.scores(S.recv[i]), L.rows(S.recv[i]), L.b, k, out_s[i], out_r[i]));
+  }
+  return DHR_OK;
+}
+
+// local thresholds for a (sub-)batch: every shard searches with k, full lists gathered (ONE all-gather: scores and rows in one block, `name` of the
+// plan) and merged.  out_* [L.Q, k] per local shard.
+int local_path(Step& S, StepPlan::Name name, const ListBlock& L, const std::vector<dhr_query_batch>& qb, float* const* out_s, int64_t* const* out_r) {
+  Backend& B = S.B;
+  const int nl = B.n_local, k = L.L;
+  for (int i = 0; i < nl; ++i) {
+    char* blk = nullptr;
+    SH_TRY(S.open(i, L.b, &blk));
+    SH_LOCAL(i, B.search(i, &qb[i], k, L.scores(blk), L.rows(blk)));
+  }
+  SH_TRY(S.gather(name));
+  for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.merge(i, L.Q, k, L.scores(S.recv[i]), L.rows(S.recv[i]), L.b, k, out_s[i], out_r[i]));
+  return DHR_OK;
+}
+
+// 6, second half: the failed queries `ids` (unrepresentative sample, skewed shards) as a sub-batch with local thresholds, gathered at full length and
+// scattered into the result.  Ends with the step's second (and last) host read.
+int repair(Step& S, const dhr_query_batch* qb_in, std::vector<int32_t>& ids, float* const* out_s, int64_t* const* out_r) {
+  Backend& B = S.B;
+  const int nl = B.n_local, k = S.plan.k, F = (int)ids.size();
+  S.plan.add_repair(F);                                  // the repair step's all-gather (every rank read the same F)
+  std::sort(ids.begin(), ids.end());                     // the ids come out of an atomic append on the device: sorted, every rank and shard holds the same order
+  std::vector<dhr_query_batch> sub(nl, *qb_in);
+  std::vector<float*> fs(nl);
+  std::vector<int64_t*> fr(nl);
+  std::vector<int32_t*> ids_mem(nl);
+  for (int i = 0; i < nl; ++i) {
+    SH_LOCAL(i, B.sub_batch(i, qb_in, ids, &sub[i], &ids_mem[i]));
+    SH_TRY(S.alloc(i, (size_t)F * k * 4, &fs[i]));
+    SH_TRY(S.alloc(i, (size_t)F * k * 8, &fr[i]));
+    if (S.st[i] != DHR_OK) sub[i].n_queries = F;            // (a shard that failed before it built its sub-batch still sizes its blocks by F)
+  }
+  for (int i = 0; i < nl; ++i) SH_TRY(B.zero(i, S.rec[i], 16));
+  SH_TRY(local_path(S, StepPlan::REPAIR, S.plan.repair, sub, fs.data(), fr.data()));
+  for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.scatter(i, fs[i], fr[i], ids_mem[i], F, k, out_s[i], out_r[i]));
+  int peer_status = 0, peer_rank = 0;
+  std::vector<int32_t> none;
+  SH_TRY(B.read_failed(S.rec, {}, none, &peer_status, &peer_rank));      // (no ids to read; synchronises every local shard)
+  return S.verdict(peer_status, peer_rank);
+}
+
+// The driver: one sharded step, as the sequence at the top of this file.  The step has exactly ONE host read (read_failed), plus one more only when a
+// repair step runs; nothing here synchronises a stream, allocates device memory outside the arenas or copies synchronously.
+int sharded_body(Step& S, const dhr_query_batch* qb_in, int k, float* const* out_s, int64_t* const* out_r) {
+  Backend& B = S.B;
+  const int nl = B.n_local, Q = qb_in->n_queries;
+  ShareGuard share_guard{B};                                            // share back to 1, pending staged search aborted: on every way out
+  std::vector<dhr_query_batch> qb(nl, *qb_in);
+  for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.set_share(i, B.world));    // a shard chases only its share of the union's rank
+  Ranks ranks;
+  SH_TRY(agree_ranks(S, k, &ranks));
+  // Between the agreement and this line nothing may fail or allocate: from here on Step::leave knows the all-gathers this rank owes.
+  S.plan = StepPlan(Q, k, B.world, ranks);
+  const StepPlan& P = S.plan;
+  SH_TRY(S.init());
+  std::vector<int32_t*> fail_ids(nl, nullptr);
+  std::vector<int32_t> ids;
+  // BEFORE the first gather: the read behind the last planned one must not allocate (a rank that failed THERE would not know whether the others repair)
+  ids.reserve((size_t)Q);
+  int peer_status = 0, peer_rank = 0;
+  if (!P.sampled) {                // shards that cannot be sampled alike: local thresholds for the whole batch
+    SH_TRY(local_path(S, StepPlan::LOCAL, P.local, qb, out_s, out_r));
+    SH_TRY(B.read_failed(S.rec, fail_ids, ids, &peer_status, &peer_rank));
+    return S.verdict(peer_status, peer_rank);
+  }
+  std::vector<float*> tau(nl);
+  for (int i = 0; i < nl; ++i) SH_TRY(S.alloc(i, (size_t)Q * 4, &tau[i]));
+  if (P.has_pre) {
+    // 1a: the first part of every shard's sample, a first common threshold from the union of the parts, the rest of the samples filtered at it
+    std::vector<float*> tau0(nl);
+    for (int i = 0; i < nl; ++i) SH_TRY(S.alloc(i, (size_t)Q * 4, &tau0[i]));
+    SH_TRY(score_round(S, StepPlan::PRE, P.r_pre, P.ru0, false, tau0, [&](int i, float* scores) { return B.pre(i, &qb[i], k, P.r_pre, scores); }));
+    SH_TRY(score_round(S, StepPlan::SAMPLE, P.r, P.ru, false, tau, [&](int i, float* scores) { return B.begin_rest(i, tau0[i], scores); }));
+  } else      // 1-2: sampled passes, common thresholds
+    SH_TRY(score_round(S, StepPlan::SAMPLE, P.r, P.ru, false, tau, [&](int i, float* scores) { return B.begin(i, &qb[i], k, scores); }));
+  // 2b: second agreement.  Every shard runs the first slice of its main pass with tau and reports its best scores seen so far; the threshold of the rest
+  // of the pass only rises to the union's (the counts are taken against it).  What 1a and 2b buy: DESIGN.md section 5.
+  if (P.has_mid) SH_TRY(score_round(S, StepPlan::MID, P.r_mid, P.ru2, true, tau, [&](int i, float* scores) { return B.mid(i, tau[i], P.r_mid, scores); }));
+  SH_TRY(main_pass(S, tau, fail_ids, out_s, out_r));
+  // 6: the one host read; identical on every rank (it is a function of the gathered counts and status records)
+  SH_TRY(B.read_failed(S.rec, fail_ids, ids, &peer_status, &peer_rank));
+  if (peer_status != 0) return S.verdict(peer_status, peer_rank);      // a failure from before the last gather: every rank reads the same record
+  g_last_repairs = (int)ids.size();
+  // (a failure of THIS rank behind the last gather -- its reduce -- is unknown to the others: without a repair step there is no collective left
+  // and it just reports it; with one it keeps to the sequence and its status travels in that gather)
+  if (ids.empty()) return S.verdict(0, 0);
+  return repair(S, qb_in, ids, out_s, out_r);
+}
+
+// The step and its way out: whatever the body returns or throws, a failing rank does not leave the others waiting (Step::leave).  out_s / out_r: one [Q, k]
+// device (host shards: host) array per LOCAL shard.
 int sharded_core(Backend& B, const dhr_query_batch* qb_in, int k, float* const* out_s, int64_t* const* out_r) {
   g_last_repairs = 0;
-  const bool spmd = B.world > B.n_local;
   int rc;
   try {
     Step S(B);
@@ -369,183 +465,18 @@ int sharded_core(Backend& B, const dhr_query_batch* qb_in, int k, float* const* 
   } catch (...) {          // the step's own state could not be built: nothing has been exchanged yet
     rc = dhr::on_exception();
   }
-  if (spmd) {
-    char keep[1024];
-    snprintf(keep, sizeof(keep), "%s", dhr_last_error());
-    try {
-      int32_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, rc, 0};
-      (void)B.min_over_ranks(v);
-    } catch (...) {
-    }
-    (void)dhr_set_error_message(rc, keep);
-  }
+  if (B.world > B.n_local) vote_status_only(B, rc);
   return rc;
-}
-static int sharded_body(Step& S, const dhr_query_batch* qb_in, int k, float* const* out_s_in, int64_t* const* out_r_in) {
-  Backend& B = S.B;
-  const int nl = B.n_local, world = B.world, Q = qb_in->n_queries;
-  ShareGuard share_guard{B};
-  const std::vector<float*> out_s(out_s_in, out_s_in + nl);
-  const std::vector<int64_t*> out_r(out_r_in, out_r_in + nl);
-  std::vector<dhr_query_batch> qb(nl, *qb_in);
-  for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.set_share(i, world));      // a shard chases only its share of the union's rank
-  int r = 0, ru_all = 0, rl_mid = 0, ru_mid = 0, rl_pre = 0, ru_pre = 0;
-  SH_TRY(agree_rank(S, k, &r, &ru_all, &rl_mid, &ru_mid, &rl_pre, &ru_pre));
-  // the all-gathers this step owes from here on (Step::leave): nothing below may fail before they are on record
-  const int kk_plan = prefix_len(k, world);
-  if (r <= 0) S.owe(local_block(Q, k));
-  else {
-    if (rl_pre > 0 && ru_pre > 0) S.owe(block_of((size_t)Q * rl_pre * 4));
-    S.owe(block_of((size_t)Q * r * 4));
-    if (rl_mid > 0 && ru_mid > 0) S.owe(block_of((size_t)Q * rl_mid * 4));
-    S.owe(final_block(Q, kk_plan));
-  }
-  SH_TRY(S.init());
-  std::vector<int32_t*> fail_ids(nl, nullptr);
-  std::vector<int32_t> ids;
-  ids.reserve((size_t)Q);          // (the read behind the last planned all-gather must not allocate: a rank that failed THERE would not know whether the
-                                   // others go on to a repair step -- until then it was the one gap a random failure could hit: tests/test_dist_gloo.py)
-  int peer_status = 0, peer_rank = 0;
-  if (r <= 0) {
-    // shards that cannot be sampled alike: local thresholds for the whole batch
-    SH_TRY(local_path(S, qb, k, out_s, out_r));
-    SH_TRY(B.read_failed(S.rec, fail_ids, ids, &peer_status, &peer_rank));
-    return S.verdict(peer_status, peer_rank);
-  }
-  const int ru = std::min<int>(ru_all, world * r);      // rank of the union that defines the threshold; the lists are r long
-
-  // 1-2: sampled passes, common thresholds
-  const Block b_sample = block_of((size_t)Q * r * 4);
-  std::vector<const void*> send(nl);
-  std::vector<void*> recv(nl);
-  std::vector<float*> tau(nl);
-  // 1a (round 5): the first part of every shard's sample, a first common threshold from the union of the parts, the rest of the samples
-  // filtered at it -- eight sampled runs that each started from nothing rescored 3.2 k rows per query between them, the unsharded search's one
-  // run 0.7 k.  One more all-gather of [Q, ~17] scores.
-  std::vector<float*> sample_v(nl);
-  for (int i = 0; i < nl; ++i) {
-    sample_v[i] = (float*)B.alloc(i, b_sample.stride);
-    recv[i] = B.alloc(i, (size_t)world * b_sample.stride);
-    tau[i] = (float*)B.alloc(i, (size_t)Q * 4);
-    if (!sample_v[i] || !recv[i] || !tau[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-  }
-  if (rl_pre > 0 && ru_pre > 0) {
-    const int ru0 = std::min<int>(ru_pre, world * rl_pre);
-    const Block b0 = block_of((size_t)Q * rl_pre * 4);
-    std::vector<const void*> send0(nl);
-    std::vector<void*> recv0(nl);
-    std::vector<float*> tau0(nl);
-    for (int i = 0; i < nl; ++i) {
-      float* seen = (float*)B.alloc(i, b0.stride);
-      recv0[i] = B.alloc(i, (size_t)world * b0.stride);
-      tau0[i] = (float*)B.alloc(i, (size_t)Q * 4);
-      if (!seen || !recv0[i] || !tau0[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-      SH_LOCAL(i, B.pre(i, &qb[i], k, rl_pre, seen));
-      send0[i] = seen;
-    }
-    SH_TRY(S.gather(send0, recv0, b0));
-    for (int i = 0; i < nl; ++i) {
-      SH_LOCAL(i, B.union_threshold(i, (const float*)recv0[i], b0, Q, rl_pre, ru0, tau0[i]));
-      SH_LOCAL(i, B.begin_rest(i, tau0[i], sample_v[i]));
-      send[i] = sample_v[i];
-    }
-  } else
-    for (int i = 0; i < nl; ++i) {
-      SH_LOCAL(i, B.begin(i, &qb[i], k, sample_v[i]));
-      send[i] = sample_v[i];
-    }
-  SH_TRY(S.gather(send, recv, b_sample));
-  for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.union_threshold(i, (const float*)recv[i], b_sample, Q, r, ru, tau[i]));
-  // 2b: second agreement.  Every shard runs the first slice of its main pass with tau and reports its best scores seen so far; the union of
-  // what the shards have seen is a scattered fraction f of the corpus, and its (k f + 6 sigma + 4)-th best score is the threshold of the rest
-  // of the pass (the shard keeps the larger of the two; the counts below are taken against it).  A 1/8 shard of the 8.8 M-row benchmark
-  // rescores ~360 instead of ~490 rows per query in its main pass for one more all-gather of [Q, ~60] scores.
-  if (rl_mid > 0 && ru_mid > 0) {
-    const int ru2 = std::min<int>(ru_mid, world * rl_mid);
-    const Block b2 = block_of((size_t)Q * rl_mid * 4);
-    std::vector<const void*> send2(nl);
-    std::vector<void*> recv2(nl);
-    for (int i = 0; i < nl; ++i) {
-      float* seen = (float*)B.alloc(i, b2.stride);
-      recv2[i] = B.alloc(i, (size_t)world * b2.stride);
-      if (!seen || !recv2[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-      SH_LOCAL(i, B.mid(i, tau[i], rl_mid, seen));
-      send2[i] = seen;
-    }
-    SH_TRY(S.gather(send2, recv2, b2));
-    for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.union_threshold2(i, (const float*)recv2[i], b2, Q, rl_mid, ru2, tau[i]));
-  }
-  // 3-5: main passes; ONE all-gather of [counts | list prefixes: scores | rows] per shard (round 6; until then the counts travelled in a
-  // collective of their own, and scores and rows in one each), failure flags, reduce
-  const int kk = prefix_len(k, world);
-  const size_t off_s = final_off_s(Q), off_r = final_off_r(Q, kk);
-  const Block bl = final_block(Q, kk);
-  std::vector<const void*> send_l(nl);
-  std::vector<void*> recv_l(nl);
-  for (int i = 0; i < nl; ++i) {
-    char* blk = (char*)B.alloc(i, bl.stride);
-    recv_l[i] = B.alloc(i, (size_t)world * bl.stride);
-    fail_ids[i] = (int32_t*)B.alloc(i, (size_t)Q * 4);
-    if (!blk || !recv_l[i] || !fail_ids[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-    float* ps = (float*)(blk + off_s);
-    int64_t* pr = (int64_t*)(blk + off_r);
-    if (kk == k) {
-      SH_LOCAL(i, B.finish(i, tau[i], ps, pr, (int32_t*)blk));          // the full lists ARE the prefixes: straight into the block
-    } else {
-      float* ls = (float*)B.alloc(i, (size_t)Q * k * 4);
-      int64_t* lr = (int64_t*)B.alloc(i, (size_t)Q * k * 8);
-      if (!ls || !lr) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-      SH_LOCAL(i, B.finish(i, tau[i], ls, lr, (int32_t*)blk));
-      SH_LOCAL(i, B.prefix(i, ls, lr, k, kk, Q, ps, pr));
-    }
-    send_l[i] = blk;
-  }
-  SH_TRY(S.gather(send_l, recv_l, bl));
-  for (int i = 0; i < nl; ++i) {
-    SH_LOCAL(i, B.flag_failures(i, (const int32_t*)recv_l[i], bl, Q, k, kk, fail_ids[i], S.rec[i]));
-    SH_LOCAL(i, B.merge(i, Q, kk, (const float*)((const char*)recv_l[i] + off_s), (const int64_t*)((const char*)recv_l[i] + off_r), bl, k, out_s[i], out_r[i]));
-  }
-  // 6: the one host read; identical on every rank (it is a function of the gathered counts and status records).  The ids come out of an
-  // atomic append on the device: sorted, so that every rank (and every local shard) holds the same order.
-  SH_TRY(B.read_failed(S.rec, fail_ids, ids, &peer_status, &peer_rank));
-  if (peer_status != 0) return S.verdict(peer_status, peer_rank);      // a failure from before the last gather: every rank reads the same record
-  const int F = (int)ids.size();
-  g_last_repairs = F;
-  // (a failure of THIS rank behind the last gather -- its reduce -- is unknown to the others: without a repair step there is no collective left
-  // and it just reports it; with one it keeps to the sequence below and its status travels in that gather)
-  if (F == 0) return S.verdict(0, 0);
-  S.owe(local_block(F, k));                              // the repair step's all-gather (every rank read the same F)
-  std::sort(ids.begin(), ids.end());
-  // failed queries (unrepresentative sample, skewed shards): sub-batch with local thresholds, gathered at full length, scattered into the result
-  std::vector<dhr_query_batch> sub(nl, *qb_in);
-  std::vector<float*> fs(nl);
-  std::vector<int64_t*> fr(nl);
-  std::vector<int32_t*> ids_mem(nl);
-  for (int i = 0; i < nl; ++i) {
-    SH_LOCAL(i, B.sub_batch(i, qb_in, ids, &sub[i], &ids_mem[i]));
-    fs[i] = (float*)B.alloc(i, (size_t)F * k * 4);
-    fr[i] = (int64_t*)B.alloc(i, (size_t)F * k * 8);
-    if (!fs[i] || !fr[i]) return dhr_set_error_message(DHR_ERR_HIP, "out of memory in the sharded search");
-    if (S.st[i] != DHR_OK) sub[i].n_queries = F;            // (a shard that failed before it built its sub-batch still sizes its blocks by F)
-  }
-  for (int i = 0; i < nl; ++i) SH_TRY(B.zero(i, S.rec[i], 16));
-  SH_TRY(local_path(S, sub, k, fs, fr));
-  for (int i = 0; i < nl; ++i) SH_LOCAL(i, B.scatter(i, fs[i], fr[i], ids_mem[i], F, k, out_s[i], out_r[i]));
-  std::vector<int32_t*> no_ids(nl, nullptr);
-  std::vector<int32_t> none;
-  SH_TRY(B.read_failed(S.rec, no_ids, none, &peer_status, &peer_rank));      // (synchronises every local shard)
-  return S.verdict(peer_status, peer_rank);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // HipBackend
-__global__ void column_kernel(const float* __restrict__ in, int ld, int col, int n, float* __restrict__ out) {
+// out[i] = column `col` of in [n, ld]; raise: out[i] = max(out[i], that)
+__global__ void column_kernel(const float* __restrict__ in, int ld, int col, int n, float* __restrict__ out, bool raise) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[(int64_t)i * ld + col];
-}
-__global__ void column_max_kernel(const float* __restrict__ in, int ld, int col, int n, float* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = fmaxf(out[i], in[(int64_t)i * ld + col]);
+  if (i >= n) return;
+  const float v = in[(int64_t)i * ld + col];
+  out[i] = raise ? fmaxf(out[i], v) : v;
 }
 // counts [world][Q] -> compact list of failed query ids, their number
 // the status records of a gathered buffer -> rec[1] / rec[2] = status / rank of the first failing rank (kept once set)
@@ -623,22 +554,25 @@ struct ShardCtx {
 struct HipBackend : Backend {
   std::vector<ShardCtx> sh;
   dhr_comm* comm = nullptr;       // SPMD (n_local == 1, world > 1): RCCL or the caller's host transport; null: one process, gathers are device copies
-  std::vector<std::vector<char>> host_v, host_i;      // host sub-batches of the repair step (shared by the local shards)
+  std::vector<std::vector<char>> host_v, host_i;      // host sub-batch of the repair step (shared by the local shards)
+  dhr_query_batch host_sub;
 
+  // makes shard i's device current: what every method that enqueues on the shard's stream opens with
+  int use(int i) { SH_HIP(hipSetDevice(sh[i].device)); return DHR_OK; }
   void* alloc(int i, size_t bytes) override { (void)hipSetDevice(sh[i].device); return sh[i].arena->get(bytes); }
   int zero(int i, void* p, size_t bytes) override {
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     SH_HIP(hipMemsetAsync(p, 0, bytes, sh[i].stream));
     return DHR_OK;
   }
   int put_status(int i, void* block, const Block& b, int status) override {
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     SH_HIP(hipMemsetD32Async((hipDeviceptr_t)((char*)block + b.payload), status, 4, sh[i].stream));
     return DHR_OK;
   }
   int fold_status(int i, const void* gathered, const Block& b, int32_t* rec) override {
     if (comm && comm->cb) return DHR_OK;             // the host transport read the records behind the gather already
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     hipLaunchKernelGGL(fold_status_kernel, dim3(1), dim3(64), 0, sh[i].stream, (const char*)gathered, world, b.stride, b.payload, rec);
     return DHR_OK;
   }
@@ -646,42 +580,18 @@ struct HipBackend : Backend {
   void abort(int i) override { dhr_internal_search_abort(sh[i].ix); }
   int sample_rank(int i, int k) override { return dhr_search_sample_rank(sh[i].ix, k); }
   int union_rank(int i, int k) override { return dhr_search_union_rank(sh[i].ix, k); }
-  int begin(int i, const dhr_query_batch* qb, int k, float* sample) override {
-    SH_HIP(hipSetDevice(sh[i].device));
-    return dhr_internal_search_begin_async(sh[i].ix, qb, k, sample, sh[i].stream);
-  }
-  int finish(int i, const float* tau, float* ls, int64_t* lr, int32_t* cnt) override {
-    SH_HIP(hipSetDevice(sh[i].device));
-    return dhr_internal_search_finish_async(sh[i].ix, tau, ls, lr, cnt, DHR_MEM_DEVICE, sh[i].stream);
-  }
-  int mid_ranks(int i, int k, int* r_local, int* r_union) override {
+  int begin(int i, const dhr_query_batch* qb, int k, float* sample) override { SH_TRY(use(i)); return dhr_internal_search_begin_async(sh[i].ix, qb, k, sample, sh[i].stream); }
+  int finish(int i, const float* tau, float* ls, int64_t* lr, int32_t* cnt) override { SH_TRY(use(i)); return dhr_internal_search_finish_async(sh[i].ix, tau, ls, lr, cnt, DHR_MEM_DEVICE, sh[i].stream); }
+  int stage_ranks(int i, Stage stage, int k, int* r_local, int* r_union) override {
     int32_t a = 0, b = 0;
-    (void)dhr_search_mid_ranks(sh[i].ix, k, &a, &b);
+    (void)(stage == MID ? dhr_search_mid_ranks : dhr_search_pre_ranks)(sh[i].ix, k, &a, &b);
     *r_local = a; *r_union = b;
     return DHR_OK;
   }
-  int mid(int i, const float* tau, int r_local, float* scores) override {
-    SH_HIP(hipSetDevice(sh[i].device));
-    return dhr_internal_search_mid_async(sh[i].ix, tau, r_local, scores, sh[i].stream);
-  }
-  int pre_ranks(int i, int k, int* r_local, int* r_union) override {
-    int32_t a = 0, b = 0;
-    (void)dhr_search_pre_ranks(sh[i].ix, k, &a, &b);
-    *r_local = a; *r_union = b;
-    return DHR_OK;
-  }
-  int pre(int i, const dhr_query_batch* qb, int k, int r_local, float* scores) override {
-    SH_HIP(hipSetDevice(sh[i].device));
-    return dhr_internal_search_pre_async(sh[i].ix, qb, k, r_local, scores, sh[i].stream);
-  }
-  int begin_rest(int i, const float* tau, float* sample) override {
-    SH_HIP(hipSetDevice(sh[i].device));
-    return dhr_internal_search_begin_rest_async(sh[i].ix, tau, sample, sh[i].stream);
-  }
-  int search(int i, const dhr_query_batch* qb, int k, float* s, int64_t* r) override {
-    SH_HIP(hipSetDevice(sh[i].device));
-    return dhr_search(sh[i].ix, qb, k, s, r, DHR_MEM_DEVICE, sh[i].stream);
-  }
+  int mid(int i, const float* tau, int r_local, float* scores) override { SH_TRY(use(i)); return dhr_internal_search_mid_async(sh[i].ix, tau, r_local, scores, sh[i].stream); }
+  int pre(int i, const dhr_query_batch* qb, int k, int r_local, float* scores) override { SH_TRY(use(i)); return dhr_internal_search_pre_async(sh[i].ix, qb, k, r_local, scores, sh[i].stream); }
+  int begin_rest(int i, const float* tau, float* sample) override { SH_TRY(use(i)); return dhr_internal_search_begin_rest_async(sh[i].ix, tau, sample, sh[i].stream); }
+  int search(int i, const dhr_query_batch* qb, int k, float* s, int64_t* r) override { SH_TRY(use(i)); return dhr_search(sh[i].ix, qb, k, s, r, DHR_MEM_DEVICE, sh[i].stream); }
   int gather(const std::vector<const void*>& send, const std::vector<void*>& recv, const Block& b) override {
     const size_t bytes = b.stride;
     if (comm && comm->dead) return dhr_set_error_message(DHR_ERR_INVALID, "the communicator was aborted (dhr_comm_abort)");
@@ -713,72 +623,53 @@ struct HipBackend : Backend {
     for (int i = 1; i < n_local; ++i) one_stream = one_stream && sh[i].stream == sh[0].stream && sh[i].device == sh[0].device;
     if (!one_stream) for (int i = 0; i < n_local; ++i) SH_HIP(hipStreamSynchronize(sh[i].stream));
     for (int d = 0; d < n_local; ++d) {
-      SH_HIP(hipSetDevice(sh[d].device));
+      SH_TRY(use(d));
       for (int s = 0; s < n_local; ++s)
         SH_HIP(hipMemcpyAsync((char*)recv[d] + (size_t)s * bytes, send[s], bytes, hipMemcpyDefault, sh[d].stream));
     }
     if (!one_stream) for (int i = 0; i < n_local; ++i) SH_HIP(hipStreamSynchronize(sh[i].stream));
     return DHR_OK;
   }
-  int min_over_ranks(int32_t v[12]) override {
-    if (!comm || world <= 1) return DHR_OK;
+  int exchange_vote(const RankVote& mine, int32_t* all) override {
     if (comm->dead) return dhr_set_error_message(DHR_ERR_INVALID, "the communicator was aborted (dhr_comm_abort)");
-    int32_t few[64 * 12];                            // (no allocation in front of the exchange for up to 64 ranks: Step::leave)
-    std::vector<int32_t> many;
-    if (world > 64) many.resize((size_t)world * 12);
-    int32_t* all = world > 64 ? many.data() : few;
     if (comm->cb) {                                  // host transport: the values are host memory already
-      if (comm->cb(comm->cb_user, v, all, 48) != 0) return dhr_set_error_message(DHR_ERR_INTERNAL, "the caller's all-gather callback failed");
-    } else {                                         // (no status record on this exchange: v[10] is the status)
-      SH_HIP(hipSetDevice(sh[0].device));
-      int32_t* d = (int32_t*)sh[0].arena->get(64 + (size_t)world * 48);
-      if (!d) return dhr_set_error_message(DHR_ERR_HIP, "out of device memory");
-      SH_HIP(hipMemcpyAsync(d, v, 48, hipMemcpyHostToDevice, sh[0].stream));
-      SH_NCCL(ncclAllGather(d, d + 16, 48, ncclInt8, comm->comm, sh[0].stream));
-      SH_HIP(hipMemcpyAsync(all, d + 16, (size_t)world * 48, hipMemcpyDeviceToHost, sh[0].stream));
-      SH_HIP(hipStreamSynchronize(sh[0].stream));
+      if (comm->cb(comm->cb_user, mine.v, all, 48) != 0) return dhr_set_error_message(DHR_ERR_INTERNAL, "the caller's all-gather callback failed");
+      return DHR_OK;
     }
-    for (int w = 0; w < world; ++w)
-      for (int j = 0; j < 12; ++j) v[j] = std::min(v[j], all[(size_t)w * 12 + j]);
+    SH_TRY(use(0));                                  // (no status record on this exchange: the vote carries the status)
+    int32_t* d = (int32_t*)sh[0].arena->get(64 + (size_t)world * 48);
+    if (!d) return dhr_set_error_message(DHR_ERR_HIP, "out of device memory");
+    SH_HIP(hipMemcpyAsync(d, mine.v, 48, hipMemcpyHostToDevice, sh[0].stream));
+    SH_NCCL(ncclAllGather(d, d + 16, 48, ncclInt8, comm->comm, sh[0].stream));
+    SH_HIP(hipMemcpyAsync(all, d + 16, (size_t)world * 48, hipMemcpyDeviceToHost, sh[0].stream));
+    SH_HIP(hipStreamSynchronize(sh[0].stream));
     return DHR_OK;
   }
-  // the r best of [world] sorted score lists per query, lists b.stride bytes apart
-  int merge_scores(int i, const float* gathered, const Block& b, int Q, int r, int ru, float** merged_out) {
-    SH_HIP(hipSetDevice(sh[i].device));
+  // the ru-th best of [world] sorted score lists per query, lists b.stride bytes apart
+  int union_threshold(int i, const float* gathered, const Block& b, int Q, int r, int ru, float* tau, bool raise) override {
+    SH_TRY(use(i));
     float* merged = (float*)sh[i].arena->get((size_t)Q * ru * 4);
     if (!merged) return dhr_set_error_message(DHR_ERR_HIP, "out of device memory in the sharded search");
     if (((int64_t)world * r + ru) * 4 > 160 * 1024 || world > 64)
       return dhr_set_error_message(DHR_ERR_UNSUPPORTED, "the sample lists of one query do not fit the LDS");
     SH_HIP(launch_merge_lists(Q, world, r, gathered, nullptr, ru, merged, nullptr, sh[i].stream, (int64_t)(b.stride / 4), 0));
-    *merged_out = merged;
-    return DHR_OK;
-  }
-  int union_threshold(int i, const float* gathered, const Block& b, int Q, int r, int ru, float* tau) override {
-    float* merged = nullptr;
-    SH_TRY(merge_scores(i, gathered, b, Q, r, ru, &merged));
-    hipLaunchKernelGGL(column_kernel, dim3((Q + 255) / 256), dim3(256), 0, sh[i].stream, merged, ru, ru - 1, Q, tau);
-    return DHR_OK;
-  }
-  int union_threshold2(int i, const float* gathered, const Block& b, int Q, int r, int ru, float* tau) override {
-    float* merged = nullptr;
-    SH_TRY(merge_scores(i, gathered, b, Q, r, ru, &merged));
-    hipLaunchKernelGGL(column_max_kernel, dim3((Q + 255) / 256), dim3(256), 0, sh[i].stream, merged, ru, ru - 1, Q, tau);
+    hipLaunchKernelGGL(column_kernel, dim3((Q + 255) / 256), dim3(256), 0, sh[i].stream, merged, ru, ru - 1, Q, tau, raise);
     return DHR_OK;
   }
   int flag_failures(int i, const int32_t* counts, const Block& b, int Q, int k, int kk, int32_t* fail_ids, int32_t* rec) override {
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     hipLaunchKernelGGL(fail_kernel, dim3((Q + 255) / 256), dim3(256), 0, sh[i].stream, counts, b.stride, world, Q, k, kk, fail_ids, rec);
     return DHR_OK;
   }
   int prefix(int i, const float* s, const int64_t* r, int k, int kk, int Q, float* os, int64_t* orow) override {
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     const int64_t n = (int64_t)Q * kk;
     hipLaunchKernelGGL(prefix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sh[i].stream, s, r, k, kk, Q, os, orow);
     return DHR_OK;
   }
   int merge(int i, int Q, int L, const float* gs, const int64_t* gr, const Block& b, int k, float* os, int64_t* orow) override {
     const ShardCtx& c = sh[i];
-    SH_HIP(hipSetDevice(c.device));
+    SH_TRY(use(i));
     // sorted per-shard lists, one [Q, L] section per rank: rank merge in the LDS when the lists of a query fit, else the general reduce
     if (world <= 64 && ((int64_t)world * L + k) * 12 <= 160 * 1024) {
       SH_HIP(launch_merge_lists(Q, world, L, gs, gr, k, os, orow, c.stream, (int64_t)(b.stride / 4), (int64_t)(b.stride / 8)));
@@ -796,28 +687,25 @@ struct HipBackend : Backend {
   }
   int read_failed(const std::vector<int32_t*>& rec, const std::vector<int32_t*>& fail_ids, std::vector<int32_t>& ids, int* peer_status, int* peer_rank) override {
     int32_t h[4] = {0, 0, 0, 0};
-    SH_HIP(hipSetDevice(sh[0].device));
+    SH_TRY(use(0));
     SH_HIP(hipMemcpyAsync(h, rec[0], 16, hipMemcpyDeviceToHost, sh[0].stream));
     for (int i = 0; i < n_local; ++i) SH_HIP(hipStreamSynchronize(sh[i].stream));
     *peer_status = h[1]; *peer_rank = h[2];
-    const int32_t nf = fail_ids[0] ? h[0] : 0;
+    const int32_t nf = !fail_ids.empty() && fail_ids[0] ? h[0] : 0;
     ids.resize((size_t)nf);
     if (nf > 0) SH_HIP(hipMemcpy(ids.data(), fail_ids[0], (size_t)nf * 4, hipMemcpyDeviceToHost));
     return DHR_OK;
   }
   int sub_batch(int i, const dhr_query_batch* in, const std::vector<int32_t>& ids, dhr_query_batch* out, int32_t** ids_mem) override {
     const int F = (int)ids.size();
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     int32_t* d_ids = (int32_t*)sh[i].arena->get((size_t)F * 4);
     if (!d_ids) return dhr_set_error_message(DHR_ERR_HIP, "out of device memory in the sharded search");
     SH_HIP(hipMemcpyAsync(d_ids, ids.data(), (size_t)F * 4, hipMemcpyHostToDevice, sh[i].stream));
     *ids_mem = d_ids;
     if (in->mem_kind == DHR_MEM_HOST) {          // host batch: gathered on the host once, shared by the local shards
-      if (host_v.empty()) { host_v.resize(1); host_i.resize(1); dhr_query_batch tmp; host_sub_batch(in, ids, host_v[0], host_i[0], &tmp); }
-      *out = *in;
-      out->n_queries = F;
-      out->value = host_v[0].data();
-      out->index = in->index ? host_i[0].data() : nullptr;
+      if (host_v.empty()) { host_v.resize(1); host_i.resize(1); host_sub_batch(in, ids, host_v[0], host_i[0], &host_sub); }
+      *out = host_sub;
       return DHR_OK;
     }
     // device batch: the caller's arrays live on ONE device; gather there (shard 0's context must be that device for SPMD, and in the
@@ -840,12 +728,11 @@ struct HipBackend : Backend {
     return DHR_OK;
   }
   int scatter(int i, const float* s, const int64_t* r, const int32_t* ids_mem, int F, int k, float* os, int64_t* orow) override {
-    SH_HIP(hipSetDevice(sh[i].device));
+    SH_TRY(use(i));
     const int64_t n = (int64_t)F * k;
     hipLaunchKernelGGL(scatter_result_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sh[i].stream, s, r, ids_mem, F, k, os, orow);
     return DHR_OK;
   }
-  int sync(int i) override { SH_HIP(hipSetDevice(sh[i].device)); SH_HIP(hipStreamSynchronize(sh[i].stream)); return DHR_OK; }
 };
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -866,24 +753,26 @@ struct HostBackend : Backend {
   int set_share(int, int s) override { share = s; return DHR_OK; }
   int sample_rank(int, int k) override { return shard->sample_rank(shard->user, k, share); }
   int union_rank(int, int k) override { return shard->union_rank(shard->user, k); }
-  int begin(int, const dhr_query_batch* qb, int k, float* sample) override { return shard->begin(shard->user, qb, k, share, sample) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "host shard: begin failed"); }
-  int finish(int, const float* tau, float* ls, int64_t* lr, int32_t* cnt) override { return shard->finish(shard->user, tau, ls, lr, cnt) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "host shard: finish failed"); }
-  int mid_ranks(int, int k, int* r_local, int* r_union) override {
+  // the status of a shard callback (0: fine)
+  static int cb_status(int rc, const char* what) {
+    if (rc == 0) return DHR_OK;
+    char buf[64];
+    snprintf(buf, sizeof(buf), "host shard: %s failed", what);
+    return dhr_set_error_message(DHR_ERR_INTERNAL, buf);
+  }
+  int begin(int, const dhr_query_batch* qb, int k, float* sample) override { return cb_status(shard->begin(shard->user, qb, k, share, sample), "begin"); }
+  int finish(int, const float* tau, float* ls, int64_t* lr, int32_t* cnt) override { return cb_status(shard->finish(shard->user, tau, ls, lr, cnt), "finish"); }
+  int stage_ranks(int, Stage stage, int k, int* r_local, int* r_union) override {
     int32_t a = 0, b = 0;
-    if (shard->mid_ranks && shard->mid) (void)shard->mid_ranks(shard->user, k, share, &a, &b);
+    if (stage == MID) { if (shard->mid_ranks && shard->mid) (void)shard->mid_ranks(shard->user, k, share, &a, &b); }
+    else if (shard->pre_ranks && shard->pre && shard->begin_rest) (void)shard->pre_ranks(shard->user, k, share, &a, &b);
     *r_local = a; *r_union = b;
     return DHR_OK;
   }
-  int mid(int, const float* tau, int r_local, float* scores) override { return shard->mid(shard->user, tau, r_local, scores) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "host shard: mid failed"); }
-  int pre_ranks(int, int k, int* r_local, int* r_union) override {
-    int32_t a = 0, b = 0;
-    if (shard->pre_ranks && shard->pre && shard->begin_rest) (void)shard->pre_ranks(shard->user, k, share, &a, &b);
-    *r_local = a; *r_union = b;
-    return DHR_OK;
-  }
-  int pre(int, const dhr_query_batch* qb, int k, int r_local, float* scores) override { return shard->pre(shard->user, qb, k, share, r_local, scores) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "host shard: pre failed"); }
-  int begin_rest(int, const float* tau, float* sample) override { return shard->begin_rest(shard->user, tau, sample) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "host shard: begin_rest failed"); }
-  int search(int, const dhr_query_batch* qb, int k, float* s, int64_t* r) override { return shard->search(shard->user, qb, k, s, r) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "host shard: search failed"); }
+  int mid(int, const float* tau, int r_local, float* scores) override { return cb_status(shard->mid(shard->user, tau, r_local, scores), "mid"); }
+  int pre(int, const dhr_query_batch* qb, int k, int r_local, float* scores) override { return cb_status(shard->pre(shard->user, qb, k, share, r_local, scores), "pre"); }
+  int begin_rest(int, const float* tau, float* sample) override { return cb_status(shard->begin_rest(shard->user, tau, sample), "begin_rest"); }
+  int search(int, const dhr_query_batch* qb, int k, float* s, int64_t* r) override { return cb_status(shard->search(shard->user, qb, k, s, r), "search"); }
   int gather(const std::vector<const void*>& send, const std::vector<void*>& recv, const Block& b) override {
     if (world == 1) memcpy(recv[0], send[0], b.stride);
     else if (cb(cb_user, send[0], recv[0], (int64_t)b.stride) != 0) return dhr_set_error_message(DHR_ERR_INTERNAL, "the caller's all-gather callback failed");
@@ -891,36 +780,23 @@ struct HostBackend : Backend {
     if (const int st = host_block_status(recv[0], world, b, &who)) return peer_error(who, st);
     return DHR_OK;
   }
-  int min_over_ranks(int32_t v[12]) override {
-    if (world <= 1) return DHR_OK;
-    int32_t few[64 * 12];                            // (no allocation in front of the exchange for up to 64 ranks: Step::leave)
-    std::vector<int32_t> many;
-    if (world > 64) many.resize((size_t)world * 12);
-    int32_t* all = world > 64 ? many.data() : few;
-    if (cb(cb_user, v, all, 48) != 0) return dhr_set_error_message(DHR_ERR_INTERNAL, "the caller's all-gather callback failed");
-    for (int w = 0; w < world; ++w)
-      for (int j = 0; j < 12; ++j) v[j] = std::min(v[j], all[(size_t)w * 12 + j]);
-    return DHR_OK;
+  int exchange_vote(const RankVote& mine, int32_t* all) override {
+    return cb(cb_user, mine.v, all, 48) == 0 ? DHR_OK : dhr_set_error_message(DHR_ERR_INTERNAL, "the caller's all-gather callback failed");
   }
   // [world] sections of [Q, L] floats / int64, b.stride bytes apart -> the dense [world, Q, L] arrays dhr_merge_topk_lists_host takes
   void densify(const void* g, const Block& b, size_t section_bytes, std::vector<char>& out) const {
     out.resize((size_t)world * section_bytes);
     for (int w = 0; w < world; ++w) memcpy(out.data() + (size_t)w * section_bytes, (const char*)g + (size_t)w * b.stride, section_bytes);
   }
-  int union_threshold(int, const float* gathered, const Block& b, int Q, int r, int ru, float* tau) override {
+  int union_threshold(int, const float* gathered, const Block& b, int Q, int r, int ru, float* tau, bool raise) override {
     std::vector<float> merged((size_t)Q * ru);
     std::vector<char> dense;
     densify(gathered, b, (size_t)Q * r * 4, dense);
     SH_TRY(dhr_merge_topk_lists_host(Q, world, r, (const float*)dense.data(), nullptr, ru, merged.data(), nullptr));
-    for (int q = 0; q < Q; ++q) tau[q] = merged[(size_t)q * ru + (ru - 1)];
-    return DHR_OK;
-  }
-  int union_threshold2(int, const float* gathered, const Block& b, int Q, int r, int ru, float* tau) override {
-    std::vector<float> merged((size_t)Q * ru);
-    std::vector<char> dense;
-    densify(gathered, b, (size_t)Q * r * 4, dense);
-    SH_TRY(dhr_merge_topk_lists_host(Q, world, r, (const float*)dense.data(), nullptr, ru, merged.data(), nullptr));
-    for (int q = 0; q < Q; ++q) tau[q] = std::max(tau[q], merged[(size_t)q * ru + (ru - 1)]);
+    for (int q = 0; q < Q; ++q) {
+      const float v = merged[(size_t)q * ru + (ru - 1)];
+      tau[q] = raise ? std::max(tau[q], v) : v;
+    }
     return DHR_OK;
   }
   int flag_failures(int, const int32_t* counts, const Block& b, int Q, int k, int kk, int32_t* fail_ids, int32_t* rec) override {
@@ -942,7 +818,7 @@ struct HostBackend : Backend {
   }
   int read_failed(const std::vector<int32_t*>& rec, const std::vector<int32_t*>& fail_ids, std::vector<int32_t>& ids, int* peer_status, int* peer_rank) override {
     *peer_status = 0; *peer_rank = 0;                 // (host-visible blocks: a failure ended the step at its gather)
-    if (fail_ids[0]) ids.assign(fail_ids[0], fail_ids[0] + rec[0][0]); else ids.clear();
+    if (!fail_ids.empty() && fail_ids[0]) ids.assign(fail_ids[0], fail_ids[0] + rec[0][0]); else ids.clear();
     return DHR_OK;
   }
   int sub_batch(int, const dhr_query_batch* in, const std::vector<int32_t>& ids, dhr_query_batch* out, int32_t** ids_mem) override {
@@ -959,9 +835,16 @@ struct HostBackend : Backend {
     }
     return DHR_OK;
   }
-  int sync(int) override { return DHR_OK; }
 };
 
+// ---- what the two device entry points share ---------------------------------------------------------------------------------------------------------
+// Where a local shard builds its [Q, k] result: shard 0 straight in the caller's arrays when those are device memory (direct), else in the shard's arena
+int stage_result(const ShardCtx& c, bool direct, int Q, int k, float* out_scores, int64_t* out_rows, float** ds, int64_t** dr) {
+  if (direct) { *ds = out_scores; *dr = out_rows; return DHR_OK; }
+  *ds = (float*)c.arena->get((size_t)Q * k * 4);
+  *dr = (int64_t*)c.arena->get((size_t)Q * k * 8);
+  return *ds && *dr ? DHR_OK : dhr_set_error_message(DHR_ERR_HIP, "out of device memory");
+}
 int deliver(const ShardCtx& c, int Q, int k, const float* ds, const int64_t* dr, float* out_scores, int64_t* out_rows, int mem_kind) {
   if (mem_kind == DHR_MEM_HOST) {
     SH_HIP(hipMemcpyAsync(out_scores, ds, (size_t)Q * k * 4, hipMemcpyDeviceToHost, c.stream));
@@ -969,6 +852,17 @@ int deliver(const ShardCtx& c, int Q, int k, const float* ds, const int64_t* dr,
   }
   SH_HIP(hipStreamSynchronize(c.stream));
   return DHR_OK;
+}
+// The way out of both, whatever `rc` the call has come to: shard 0's result to its destination, then every shard's stream drained and what its arena
+// spilled released (the arena grows for the next call).
+int finish_call(HipBackend& B, int rc, int Q, int k, const float* ds, const int64_t* dr, float* out_scores, int64_t* out_rows, int mem_kind) {
+  if (rc == DHR_OK) { (void)hipSetDevice(B.sh[0].device); rc = deliver(B.sh[0], Q, k, ds, dr, out_scores, out_rows, mem_kind); }
+  for (const ShardCtx& c : B.sh) {
+    (void)hipSetDevice(c.device);
+    (void)hipStreamSynchronize(c.stream);
+    c.arena->finish();
+  }
+  return rc;
 }
 
 }  // namespace
@@ -1055,6 +949,7 @@ extern "C" int dhr_search_sharded_host(const dhr_host_shard* shard, int32_t worl
 
 extern "C" int dhr_search_sharded(dhr_index* shard, dhr_comm* comm, const dhr_query_batch* qb, int32_t k, float* out_scores, int64_t* out_rows,
                                   int32_t out_mem_kind, void* stream) try {
+  // TODO(ADVICE 2): these per-rank checks return BEFORE the rank agreement, so the other ranks wait in it; they should answer it (vote_status_only)
   if (!shard || !comm || !qb || !out_scores || !out_rows || k <= 0 || !DHR_MEM_KIND_OK(out_mem_kind)) return dhr_set_error_message(DHR_ERR_INVALID, "bad argument");
   if (comm->dead) return dhr_set_error_message(DHR_ERR_INVALID, "the communicator was aborted (dhr_comm_abort)");
   const int device = dhr_index_device(shard);
@@ -1072,34 +967,13 @@ extern "C" int dhr_search_sharded(dhr_index* shard, dhr_comm* comm, const dhr_qu
   int rc = DHR_OK;
   try {
     sh.push_back({shard, device, (hipStream_t)stream, &arena});
-    if (out_mem_kind == DHR_MEM_HOST) {
-      ds = (float*)arena.get((size_t)Q * k * 4);
-      dr = (int64_t*)arena.get((size_t)Q * k * 8);
-      if (!ds || !dr) rc = dhr_set_error_message(DHR_ERR_HIP, "out of device memory");
-    }
+    rc = stage_result(sh[0], out_mem_kind == DHR_MEM_DEVICE, Q, k, out_scores, out_rows, &ds, &dr);
   } catch (...) {
     rc = dhr::on_exception();
   }
-  if (rc != DHR_OK) {
-    if (sh.size() == 1 && B.comm) {
-      char keep[1024];
-      snprintf(keep, sizeof(keep), "%s", dhr_last_error());
-      try {
-        int32_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, rc, 0};
-        (void)B.min_over_ranks(v);
-      } catch (...) {
-      }
-      (void)hipStreamSynchronize((hipStream_t)stream);
-      (void)dhr_set_error_message(rc, keep);
-    }
-    arena.finish();
-    return rc;
-  }
-  rc = sharded_core(B, qb, k, &ds, &dr);
-  if (rc == DHR_OK) rc = deliver(sh[0], Q, k, ds, dr, out_scores, out_rows, out_mem_kind);
-  else (void)hipStreamSynchronize((hipStream_t)stream);
-  arena.finish();
-  return rc;
+  if (rc != DHR_OK && sh.size() == 1 && B.comm) vote_status_only(B, rc);
+  if (rc == DHR_OK) rc = sharded_core(B, qb, k, &ds, &dr);
+  return finish_call(B, rc, Q, k, ds, dr, out_scores, out_rows, out_mem_kind);
 } DHR_CATCH_STATUS
 
 extern "C" int dhr_search_sharded_local(dhr_index** shards, int32_t n_shards, const dhr_query_batch* qb, int32_t k, float* out_scores,
@@ -1131,18 +1005,11 @@ extern "C" int dhr_search_sharded_local(dhr_index** shards, int32_t n_shards, co
   int rc = DHR_OK;
   for (int i = 0; i < n_shards && rc == DHR_OK; ++i) {
     if (hipSetDevice(sh[i].device) != hipSuccess) rc = dhr_set_error_message(DHR_ERR_HIP, "hipSetDevice failed");
-    if (i == 0 && out_mem_kind == DHR_MEM_DEVICE) { os[i] = out_scores; orow[i] = out_rows; continue; }
-    os[i] = (float*)arenas[i].get((size_t)Q * k * 4);
-    orow[i] = (int64_t*)arenas[i].get((size_t)Q * k * 8);
-    if (!os[i] || !orow[i]) rc = dhr_set_error_message(DHR_ERR_HIP, "out of device memory");
+    else rc = stage_result(sh[i], i == 0 && out_mem_kind == DHR_MEM_DEVICE, Q, k, out_scores, out_rows, &os[i], &orow[i]);
   }
   if (rc == DHR_OK) rc = sharded_core(B, qb, k, os.data(), orow.data());
-  if (rc == DHR_OK) { (void)hipSetDevice(sh[0].device); rc = deliver(sh[0], Q, k, os[0], orow[0], out_scores, out_rows, out_mem_kind); }
-  for (int i = 0; i < n_shards; ++i) {
-    (void)hipSetDevice(sh[i].device);
-    (void)hipStreamSynchronize(sh[i].stream);
-    arenas[i].finish();
-    if (own[i]) (void)hipStreamDestroy(own[i]);
-  }
+  rc = finish_call(B, rc, Q, k, os[0], orow[0], out_scores, out_rows, out_mem_kind);
+  for (int i = 0; i < n_shards; ++i)
+    if (own[i]) { (void)hipSetDevice(sh[i].device); (void)hipStreamDestroy(own[i]); }
   return rc;
 } DHR_CATCH_STATUS

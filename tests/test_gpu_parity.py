@@ -2245,6 +2245,37 @@ def test_search_sharded_local_c_abi(G, kind, gated_image):
             s.close()
 
 
+def test_search_sharded_local_prefix_and_repair(G):
+    """Five shards and k = 300: the lists of the last all-gather travel as PREFIXES (prefix_len: kk = 256 < k, the device prefix kernel), and on
+    the structured corpus -- every high-scoring row sits in a sample tile of its shard -- the common threshold comes out too high, the count
+    check fails every query and the device repair path redoes them; the result equals the unsharded search bit for bit.  528 tiles per shard:
+    the fewest that keep a shard sampleable at period 16 (>= 32 * 16 tiles behind the head) with every shard starting on a multiple of 16 tiles."""
+    import torch
+    from dhr_amd import _lib, dist as D
+    ns, k, period = 5, 300, 16
+    n = ns * 528 * 256
+    cv, qv = _structured_corpus(n, 0, period)
+    q32 = qv.astype(np.float32)
+    full = G.GipIndex(cv, None)
+    fs, fr = full.search(q32, None, k)
+    full.close()
+    shards = []
+    for sh in range(ns):
+        lo, hi = G.shard_bounds(n, ns, sh)
+        assert lo % (period * 256) == 0
+        shards.append(G.GipIndex(cv[lo:hi], None, row_offset=lo))
+        shards[-1].set_param(_lib.PARAM_SAMPLE_PERIOD, period)
+    try:
+        ss, sr = D.search_sharded_local(shards, torch.from_numpy(q32).cuda(), None, k)      # device-resident batch: the repair gathers on the device
+        repairs = _lib.load().dhr_debug_sharded_repairs()
+        np.testing.assert_array_equal(sr.cpu().numpy(), fr)
+        np.testing.assert_array_equal(ss.cpu().numpy(), fs)
+        assert repairs > 0
+    finally:
+        for s in shards:
+            s.close()
+
+
 def test_search_sharded_rccl_single_rank(G):
     """dhr_comm_* + dhr_search_sharded through a real RCCL communicator of world size 1 (all this one-GPU box can hold): the
     collective entry point, its scratch arena and the result delivery; equals dhr_search."""

@@ -19,6 +19,7 @@
 //   term_weight_head_backward_kernel  the gather: dw[b][t] = grad[b][v] where tok[b][v] == t (v = ids[b][t] inside the vocabulary), else zero.
 // Everything is enqueued on the caller's stream; nothing is allocated.
 #include "host_stage.h"
+#include "op_dispatch.h"
 #include "lexical_common.h"
 
 namespace {
@@ -235,13 +236,10 @@ extern "C" int dhr_aggregate_train(int32_t device, int32_t mem_kind, const void*
   a.n_pairs = full ? a.W / 2 : (a.W + 1) / 2;
   a.batch = batch; a.out = out; a.out_f32 = out_dtype == DHR_VAL_F32; a.ld_out = ld_out; a.route = route; a.ld_route = ld_route;
   const dim3 grid((unsigned)((a.n_pairs + a.PB - 1) / a.PB), (unsigned)std::min<int64_t>(batch, 65535));
-#define AGG_FWD(T_)                                                                                                           \
-  do {                                                                                                                        \
-    if (full) hipLaunchKernelGGL((aggregate_route_kernel<T_, true>), grid, dim3(256), 0, s, (const T_*)lexical, a);           \
-    else hipLaunchKernelGGL((aggregate_route_kernel<T_, false>), grid, dim3(256), 0, s, (const T_*)lexical, a);               \
-  } while (0)
-  if (value_dtype == DHR_VAL_F32) AGG_FWD(float); else AGG_FWD(_Float16);
-#undef AGG_FWD
+  with_value_type(value_dtype, [&](auto t) { with_flag(full != 0, [&](auto f) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((aggregate_route_kernel<T, decltype(f)::value>), grid, dim3(256), 0, s, (const T*)lexical, a);
+  }); });
   HIP_TRY(hipGetLastError());
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -263,17 +261,11 @@ extern "C" int dhr_aggregate_backward(int32_t device, int32_t mem_kind, const vo
   const bool vec = vocab >= BC && (int64_t)vocab * es % 4 == 0 && ((uintptr_t)grad_lexical | (uintptr_t)(ld_grad * es)) % 4 == 0;
   const int base = geo.remove > 0 ? geo.remove : 0;
   const dim3 grid((unsigned)((vocab + 256 * BC - 1) / (256 * BC)), (unsigned)std::min<int64_t>(batch, 65535));
-#define AGG_BWD(T_, F_, V_)                                                                                                                   \
-  hipLaunchKernelGGL((aggregate_backward_kernel<T_, F_, V_>), grid, dim3(256), 0, s, (const T_*)grad_out, ld_grad_out, route, ld_route, batch, \
-                     vocab, base, geo.W, (T_*)grad_lexical, ld_grad)
-#define AGG_BWD_T(T_)                                                              \
-  do {                                                                             \
-    if (full) { if (vec) AGG_BWD(T_, true, true); else AGG_BWD(T_, true, false); } \
-    else { if (vec) AGG_BWD(T_, false, true); else AGG_BWD(T_, false, false); }    \
-  } while (0)
-  if (grad_dtype == DHR_VAL_F32) AGG_BWD_T(float); else AGG_BWD_T(_Float16);
-#undef AGG_BWD_T
-#undef AGG_BWD
+  with_value_type(grad_dtype, [&](auto t) { with_flag(full != 0, [&](auto f) { with_flag(vec, [&](auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((aggregate_backward_kernel<T, decltype(f)::value, decltype(v)::value>), grid, dim3(256), 0, s, (const T*)grad_out, ld_grad_out,
+                       route, ld_route, batch, vocab, base, geo.W, (T*)grad_lexical, ld_grad);
+  }); }); });
   HIP_TRY(hipGetLastError());
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -293,17 +285,12 @@ extern "C" int dhr_term_weight_head(int32_t device, int32_t mem_kind, const void
   // the int16 row of tok takes multi-dword stores when every row starts at a multiple of 4 bytes (a workgroup's columns start at a multiple of 8)
   const bool vec = ((uintptr_t)out_tokens | (uintptr_t)(ld_tokens * 2)) % 4 == 0;
   const dim3 grid((unsigned)((vocab + CH - 1) / CH), (unsigned)std::min<int64_t>(batch, 65535));
-#define TW_FWD(I_, W_, V_)                                                                                                                       \
-  hipLaunchKernelGGL((term_weight_head_kernel<I_, W_, V_>), grid, dim3(256), 0, s, (const I_*)input_ids + skip_tokens, ld_ids,                    \
-                     (const W_*)term_weights, ld_weights, batch, n_tokens, vocab, out_reps, ld_reps, out_tokens, ld_tokens)
-#define TW_FWD_W(I_)                                                                      \
-  do {                                                                                    \
-    if (value_dtype == DHR_VAL_F32) { if (vec) TW_FWD(I_, float, true); else TW_FWD(I_, float, false); } \
-    else { if (vec) TW_FWD(I_, _Float16, true); else TW_FWD(I_, _Float16, false); }       \
-  } while (0)
-  if (id_bytes == 8) TW_FWD_W(int64_t); else TW_FWD_W(int32_t);
-#undef TW_FWD_W
-#undef TW_FWD
+  with_id_type(id_bytes, [&](auto i) { with_value_type(value_dtype, [&](auto w) { with_flag(vec, [&](auto v) {
+    using I = typename decltype(i)::type;
+    using W = typename decltype(w)::type;
+    hipLaunchKernelGGL((term_weight_head_kernel<I, W, decltype(v)::value>), grid, dim3(256), 0, s, (const I*)input_ids + skip_tokens, ld_ids,
+                       (const W*)term_weights, ld_weights, batch, n_tokens, vocab, out_reps, ld_reps, out_tokens, ld_tokens);
+  }); }); });
   HIP_TRY(hipGetLastError());
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -321,16 +308,12 @@ extern "C" int dhr_term_weight_head_backward(int32_t device, int32_t mem_kind, c
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)std::min<int64_t>((batch * n_tokens + 255) / 256, 4096));
-#define TW_BWD(I_, W_)                                                                                                                            \
-  hipLaunchKernelGGL((term_weight_head_backward_kernel<I_, W_>), grid, dim3(256), 0, s, (const I_*)input_ids + skip_tokens, ld_ids, batch, n_tokens, \
-                     vocab, grad_reps, ld_grad_reps, tokens, ld_tokens, (W_*)grad_weights, ld_grad_weights)
-#define TW_BWD_W(I_)                                                                  \
-  do {                                                                                \
-    if (grad_dtype == DHR_VAL_F32) TW_BWD(I_, float); else TW_BWD(I_, _Float16);      \
-  } while (0)
-  if (id_bytes == 8) TW_BWD_W(int64_t); else TW_BWD_W(int32_t);
-#undef TW_BWD_W
-#undef TW_BWD
+  with_id_type(id_bytes, [&](auto i) { with_value_type(grad_dtype, [&](auto w) {
+    using I = typename decltype(i)::type;
+    using W = typename decltype(w)::type;
+    hipLaunchKernelGGL((term_weight_head_backward_kernel<I, W>), grid, dim3(256), 0, s, (const I*)input_ids + skip_tokens, ld_ids, batch, n_tokens,
+                       vocab, grad_reps, ld_grad_reps, tokens, ld_tokens, (W*)grad_weights, ld_grad_weights);
+  }); });
   HIP_TRY(hipGetLastError());
   return DHR_OK;
 } DHR_CATCH_STATUS

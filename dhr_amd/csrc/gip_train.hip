@@ -11,6 +11,7 @@
 //   densify_bwd_kernel    the whole [batch, vocab] gradient row of densify in one pass: dv at the group the index names, zero elsewhere.
 // Every sum has a fixed order (no atomics): two runs on the same inputs are bit-identical.  Products and sums are fp32.
 #include "host_stage.h"
+#include "op_dispatch.h"
 
 namespace {
 
@@ -226,30 +227,24 @@ FwdPlan plan_fwd(int64_t n_q, int64_t n_p, int dims, bool may_split) {
 struct Sides {
   const void *qv, *qi, *pv, *pi;
   int64_t ld_qv, ld_qi, ld_pv, ld_pi, n_q, n_p;
-  int dims, val_f32, idx_dt, group;
+  int dims, val_dt, idx_dt, group;
 };
 
-#define GIP_DISPATCH(CALL)                                                                  \
-  do {                                                                                      \
-    if (x.val_f32) {                                                                        \
-      if (x.idx_dt == DHR_IDX_U8) { CALL(float, uint8_t); }                                 \
-      else if (x.idx_dt == DHR_IDX_I8) { CALL(float, int8_t); }                             \
-      else { CALL(float, int16_t); }                                                        \
-    } else {                                                                                \
-      if (x.idx_dt == DHR_IDX_U8) { CALL(_Float16, uint8_t); }                              \
-      else if (x.idx_dt == DHR_IDX_I8) { CALL(_Float16, int8_t); }                          \
-      else { CALL(_Float16, int16_t); }                                                     \
-    }                                                                                       \
-  } while (0)
+// f(tag of the value type, tag of the index type) of the two sides
+template <class F>
+auto with_side_types(const Sides& x, F&& f) {
+  return with_value_type(x.val_dt, [&](auto v) { return with_index_type(x.idx_dt, [&](auto i) { return f(v, i); }); });
+}
 
 hipError_t launch_scores(const Sides& x, float* out, int64_t ld_out, void* ws, int64_t ws_bytes, hipStream_t s) {
   if (x.group > 0) {
     const dim3 grid((unsigned)((x.n_p + 3) / 4));
-#define GIP_PAIR_FWD(TV, TI)                                                                                                               \
-  hipLaunchKernelGGL((gip_pair_fwd_kernel<TV, TI>), grid, dim3(256), 0, s, (const TV*)x.qv, x.ld_qv, (const TI*)x.qi, x.ld_qi, (const TV*)x.pv, \
-                     x.ld_pv, (const TI*)x.pi, x.ld_pi, x.n_p, x.group, x.dims, out, ld_out)
-    GIP_DISPATCH(GIP_PAIR_FWD);
-#undef GIP_PAIR_FWD
+    with_side_types(x, [&](auto v, auto i) {
+      using TV = typename decltype(v)::type;
+      using TI = typename decltype(i)::type;
+      hipLaunchKernelGGL((gip_pair_fwd_kernel<TV, TI>), grid, dim3(256), 0, s, (const TV*)x.qv, x.ld_qv, (const TI*)x.qi, x.ld_qi, (const TV*)x.pv,
+                         x.ld_pv, (const TI*)x.pi, x.ld_pi, x.n_p, x.group, x.dims, out, ld_out);
+    });
     return hipGetLastError();
   }
   FwdPlan pl = plan_fwd(x.n_q, x.n_p, x.dims, ws != nullptr);
@@ -258,11 +253,12 @@ hipError_t launch_scores(const Sides& x, float* out, int64_t ld_out, void* ws, i
   if (pl.slices > 1) { a.out = (float*)ws; a.ld_out = x.n_p; a.slice_stride = x.n_q * x.n_p; }
   const int tq = pl.small ? 16 : 32, tp = pl.small ? 16 : 64;
   const dim3 grid((unsigned)((x.n_p + tp - 1) / tp), (unsigned)((x.n_q + tq - 1) / tq), (unsigned)pl.slices);
-#define GIP_FWD(TV, TI)                                                                         \
-  if (pl.small) hipLaunchKernelGGL((gip_fwd_kernel<TV, TI, 1, 1>), grid, dim3(256), 0, s, a);   \
-  else hipLaunchKernelGGL((gip_fwd_kernel<TV, TI, 2, 4>), grid, dim3(256), 0, s, a)
-  GIP_DISPATCH(GIP_FWD);
-#undef GIP_FWD
+  with_side_types(x, [&](auto v, auto i) { with_flag(pl.small != 0, [&](auto small) {
+    using TV = typename decltype(v)::type;
+    using TI = typename decltype(i)::type;
+    constexpr int RQ = decltype(small)::value ? 1 : 2, RP = decltype(small)::value ? 1 : 4;   // the thread tile: 16 x 16 or 32 x 64 per workgroup
+    hipLaunchKernelGGL((gip_fwd_kernel<TV, TI, RQ, RP>), grid, dim3(256), 0, s, a);
+  }); });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || pl.slices == 1) return e;
   const unsigned blocks = (unsigned)std::min<int64_t>((x.n_q * x.n_p + 255) / 256, 4096);
@@ -276,44 +272,43 @@ hipError_t launch_bwd_side(const void* own_i, int64_t ld_oi, int64_t n_own, cons
   const int d_blocks = (dims + 63) / 64;
   const int R = (n_own + 3) / 4 * d_blocks >= 256 ? 4 : (n_own + 1) / 2 * d_blocks >= 256 ? 2 : 1;   // four-wave workgroups against the device's 256 CUs
   const dim3 grid((unsigned)((n_own + R - 1) / R), (unsigned)d_blocks);
-#define GIP_BWD(R_)                                                                                                                     \
-  hipLaunchKernelGGL((gip_bwd_kernel<TV, TI, R_>), grid, dim3(256), 0, s, (const TI*)own_i, ld_oi, n_own, (const TV*)oth_v, ld_tv, (const TI*)oth_i, \
-                     ld_ti, n_oth, dims, G, gs_own, gs_oth, out, ld_out)
-  if (R == 4) GIP_BWD(4); else if (R == 2) GIP_BWD(2); else GIP_BWD(1);
-#undef GIP_BWD
+  with_int<4, 2, 1>(R, [&](auto r) {
+    hipLaunchKernelGGL((gip_bwd_kernel<TV, TI, decltype(r)::value>), grid, dim3(256), 0, s, (const TI*)own_i, ld_oi, n_own, (const TV*)oth_v, ld_tv,
+                       (const TI*)oth_i, ld_ti, n_oth, dims, G, gs_own, gs_oth, out, ld_out);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_scores_bwd(const Sides& x, const float* G, int64_t ld_g, float* dq, int64_t ld_dq, float* dp, int64_t ld_dp, hipStream_t s) {
   if (x.group > 0) {
     const dim3 grid((unsigned)x.n_p, (unsigned)((x.dims + 63) / 64), 2);       // n_p >= n_q rows cover both sides
-#define GIP_PAIR_BWD(TV, TI)                                                                                                                 \
-  hipLaunchKernelGGL((gip_pair_bwd_kernel<TV, TI>), grid, dim3(64), 0, s, (const TV*)x.qv, x.ld_qv, (const TI*)x.qi, x.ld_qi, x.n_q, (const TV*)x.pv, \
-                     x.ld_pv, (const TI*)x.pi, x.ld_pi, x.group, x.dims, G, ld_g, dq, ld_dq, dp, ld_dp)
-    GIP_DISPATCH(GIP_PAIR_BWD);
-#undef GIP_PAIR_BWD
+    with_side_types(x, [&](auto v, auto i) {
+      using TV = typename decltype(v)::type;
+      using TI = typename decltype(i)::type;
+      hipLaunchKernelGGL((gip_pair_bwd_kernel<TV, TI>), grid, dim3(64), 0, s, (const TV*)x.qv, x.ld_qv, (const TI*)x.qi, x.ld_qi, x.n_q,
+                         (const TV*)x.pv, x.ld_pv, (const TI*)x.pi, x.ld_pi, x.group, x.dims, G, ld_g, dq, ld_dq, dp, ld_dp);
+    });
     return hipGetLastError();
   }
-  hipError_t e = hipSuccess;
-#define GIP_BWD_SIDES(TV, TI)                                                                                                                \
-  if (dq) e = launch_bwd_side<TV, TI>(x.qi, x.ld_qi, x.n_q, x.pv, x.ld_pv, x.pi, x.ld_pi, x.n_p, x.dims, G, ld_g, 1, dq, ld_dq, s);           \
-  if (dp && e == hipSuccess) e = launch_bwd_side<TV, TI>(x.pi, x.ld_pi, x.n_p, x.qv, x.ld_qv, x.qi, x.ld_qi, x.n_q, x.dims, G, 1, ld_g, dp, ld_dp, s)
-  GIP_DISPATCH(GIP_BWD_SIDES);
-#undef GIP_BWD_SIDES
-  return e;
+  return with_side_types(x, [&](auto v, auto i) {
+    using TV = typename decltype(v)::type;
+    using TI = typename decltype(i)::type;
+    hipError_t e = hipSuccess;
+    if (dq) e = launch_bwd_side<TV, TI>(x.qi, x.ld_qi, x.n_q, x.pv, x.ld_pv, x.pi, x.ld_pi, x.n_p, x.dims, G, ld_g, 1, dq, ld_dq, s);
+    if (dp && e == hipSuccess) e = launch_bwd_side<TV, TI>(x.pi, x.ld_pi, x.n_p, x.qv, x.ld_qv, x.qi, x.ld_qi, x.n_q, x.dims, G, 1, ld_g, dp, ld_dp, s);
+    return e;
+  });
 }
 
 hipError_t launch_densify_bwd(const float* dv, int64_t ld_dv, const void* idx, int idx_dt, int64_t ld_idx, int64_t batch, int remove, int dims,
-                              int n_groups, void* out, int out_f32, int64_t ld_out, hipStream_t s) {
+                              int n_groups, void* out, int out_dt, int64_t ld_out, hipStream_t s) {
   const dim3 grid((unsigned)((dims + 255) / 256), (unsigned)std::min<int64_t>(batch, 65535));
-#define DENSIFY_BWD(TI, TO) \
-  hipLaunchKernelGGL((densify_bwd_kernel<TI, TO>), grid, dim3(256), 0, s, dv, ld_dv, (const TI*)idx, ld_idx, batch, remove, dims, n_groups, (TO*)out, ld_out)
-  if (out_f32) {
-    if (idx_dt == DHR_IDX_U8) DENSIFY_BWD(uint8_t, float); else if (idx_dt == DHR_IDX_I8) DENSIFY_BWD(int8_t, float); else DENSIFY_BWD(int16_t, float);
-  } else {
-    if (idx_dt == DHR_IDX_U8) DENSIFY_BWD(uint8_t, _Float16); else if (idx_dt == DHR_IDX_I8) DENSIFY_BWD(int8_t, _Float16); else DENSIFY_BWD(int16_t, _Float16);
-  }
-#undef DENSIFY_BWD
+  with_value_type(out_dt, [&](auto o) { with_index_type(idx_dt, [&](auto i) {
+    using TO = typename decltype(o)::type;
+    using TI = typename decltype(i)::type;
+    hipLaunchKernelGGL((densify_bwd_kernel<TI, TO>), grid, dim3(256), 0, s, dv, ld_dv, (const TI*)idx, ld_idx, batch, remove, dims, n_groups, (TO*)out,
+                       ld_out);
+  }); });
   return hipGetLastError();
 }
 
@@ -330,13 +325,13 @@ int check_sides(const void* qv, int64_t ld_qv, const void* qi, int64_t ld_qi, in
   if (group > 0 && n_p != n_q * group)
     return set_error(DHR_ERR_INVALID, "pairwise scores: " + std::to_string(n_p) + " passage rows for " + std::to_string(n_q) + " queries x " +
                                           std::to_string(group) + " passages");
-  x = Sides{qv, qi, pv, pi, ld_qv, ld_qi, ld_pv, ld_pi, n_q, n_p, dims, value_dtype == DHR_VAL_F32, index_dtype, group};
+  x = Sides{qv, qi, pv, pi, ld_qv, ld_qi, ld_pv, ld_pi, n_q, n_p, dims, value_dtype, index_dtype, group};
   return DHR_OK;
 }
 
 // stages the four input arrays of a host call; x then points at the device copies
 hipError_t stage_sides(Sides& x, DevMem m[4], hipStream_t s) {
-  const int ves = x.val_f32 ? 4 : 2, xes = idx_esize(x.idx_dt);
+  const int ves = val_esize(x.val_dt), xes = idx_esize(x.idx_dt);
   hipError_t e;
   if ((e = stage_in(m[0], x.qv, x.ld_qv, x.n_q, x.dims, ves, s)) != hipSuccess || (e = stage_in(m[1], x.qi, x.ld_qi, x.n_q, x.dims, xes, s)) != hipSuccess ||
       (e = stage_in(m[2], x.pv, x.ld_pv, x.n_p, x.dims, ves, s)) != hipSuccess || (e = stage_in(m[3], x.pi, x.ld_pi, x.n_p, x.dims, xes, s)) != hipSuccess)
@@ -434,7 +429,7 @@ extern "C" int dhr_densify_backward(int32_t device, int32_t mem_kind, const floa
   hipStream_t s = (hipStream_t)stream;
   if (mem_kind == DHR_MEM_DEVICE) {
     HIP_TRY(launch_densify_bwd(grad_value, ld_grad_value, index, index_dtype, ld_index, batch, remove_dims, dims, n_groups, grad_lexical,
-                               grad_dtype == DHR_VAL_F32, ld_grad, s));
+                               grad_dtype, ld_grad, s));
     return DHR_OK;
   }
   // host arrays: stage blocks of rows through the device
@@ -448,7 +443,7 @@ extern "C" int dhr_densify_backward(int32_t device, int32_t mem_kind, const floa
     HIP_TRY(stage_in(m_dv, grad_value + lo * ld_grad_value, ld_grad_value, rows, dims, 4, s));
     HIP_TRY(stage_in(m_idx, (const char*)index + lo * ld_index * xes, ld_index, rows, dims, xes, s));
     HIP_TRY(launch_densify_bwd((const float*)m_dv.p, dims, m_idx.p, index_dtype, dims, rows, remove_dims, dims, n_groups, m_out.p,
-                               grad_dtype == DHR_VAL_F32, vocab, s));
+                               grad_dtype, vocab, s));
     HIP_TRY(stage_out((char*)grad_lexical + lo * ld_grad * oes, ld_grad, m_out.p, rows, vocab, oes, s));
     HIP_TRY(hipStreamSynchronize(s));
   }

@@ -1,6 +1,7 @@
 // Host code shared by the op translation units (gip_train, maxsim, train_loss, lexical*, aggretriever_train, densify in api.hip): the dtype
 // checks of the C ABI and the staging of host arrays through the device.  A staged call owns its device copies in DevMem objects, enqueues
-// every copy on the caller's stream and synchronises that stream itself before it returns.
+// every copy on the caller's stream and synchronises that stream itself before it returns.  The step from a code that passed these checks to a
+// C++ type is op_dispatch.h (with_value_type, with_index_type, ...), which the launchers that pick a kernel instance include next to this header.
 #pragma once
 #include "dhr_state.h"
 

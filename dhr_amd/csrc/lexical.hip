@@ -14,6 +14,7 @@
 // first token and the first group (torch.max on the device), aggregate(full) is pos * (pos > neg) - neg * (pos <= neg) with its signs of zero.
 // NaN and +inf logits are out of scope (an unmasked row must hold a finite value).
 #include "host_stage.h"
+#include "op_dispatch.h"
 #include "lexical_common.h"
 
 namespace {
@@ -146,17 +147,10 @@ hipError_t launch_fold(const void* logits, int in_dtype, int mode, const FoldArg
   a.PB = 256 / a.GS;
   a.n_pairs = mode == MODE_AGG_FULL ? a.W / 2 : (a.W + 1) / 2;
   const dim3 grid((unsigned)((a.n_pairs + a.PB - 1) / a.PB), (unsigned)std::min<int64_t>(a.batch, 65535));
-#define DHR_FOLD(T_, M_) hipLaunchKernelGGL((lexical_fold_kernel<T_, M_>), grid, dim3(256), 0, s, (const T_*)logits, a)
-#define DHR_FOLD_MODES(T_)                                 \
-  switch (mode) {                                          \
-    case MODE_RAW: DHR_FOLD(T_, MODE_RAW); break;          \
-    case MODE_DENSIFY: DHR_FOLD(T_, MODE_DENSIFY); break;  \
-    case MODE_AGG_FULL: DHR_FOLD(T_, MODE_AGG_FULL); break; \
-    default: DHR_FOLD(T_, MODE_AGG_SEMI); break;           \
-  }
-  if (in_dtype == DHR_VAL_F32) { DHR_FOLD_MODES(float) } else if (in_dtype == DHR_VAL_BF16) { DHR_FOLD_MODES(__bf16) } else { DHR_FOLD_MODES(_Float16) }
-#undef DHR_FOLD_MODES
-#undef DHR_FOLD
+  with_value_type_bf16(in_dtype, [&](auto t) { with_int<MODE_RAW, MODE_DENSIFY, MODE_AGG_FULL, MODE_AGG_SEMI>(mode, [&](auto m) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((lexical_fold_kernel<T, decltype(m)::value>), grid, dim3(256), 0, s, (const T*)logits, a);
+  }); });
   return hipGetLastError();
 }
 
@@ -214,15 +208,11 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   a.val_f32 = out_value_dtype == DHR_VAL_F32; a.idx_i16 = index_dtype == DHR_IDX_I16;
   auto run = [&](const void* lg, int64_t ldb, int64_t ldt, const float* w, int64_t ldw, const float* m, int64_t ldm, int64_t rows, float4* stats,
                  void* val, int64_t ldv, void* idx, int64_t ldi, const void* c, int64_t ldc) -> hipError_t {
-    if (logits_dtype == DHR_VAL_F32)
-      hipLaunchKernelGGL(lexical_stats_kernel<float>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const float*)lg, ldb, ldt, T, vocab, w, ldw, m,
-                         ldm, stats);
-    else if (logits_dtype == DHR_VAL_BF16)
-      hipLaunchKernelGGL(lexical_stats_kernel<__bf16>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const __bf16*)lg, ldb, ldt, T, vocab, w, ldw,
-                         m, ldm, stats);
-    else
-      hipLaunchKernelGGL(lexical_stats_kernel<_Float16>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const _Float16*)lg, ldb, ldt, T, vocab, w,
-                         ldw, m, ldm, stats);
+    with_value_type_bf16(logits_dtype, [&](auto t) {
+      using TIN = typename decltype(t)::type;
+      hipLaunchKernelGGL(lexical_stats_kernel<TIN>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const TIN*)lg, ldb, ldt, T, vocab, w, ldw, m, ldm,
+                         stats);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     FoldArgs f = a;

@@ -96,7 +96,7 @@ extern "C" int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t m
   ProjArgs a{};
   a.hid = (const _Float16*)hidden; a.ld_hb = ld_batch; a.ld_ht = ld_token;
   a.wgt = (const _Float16*)weight; a.ld_w = ld_weight;
-  a.bias = bias; a.bias_f32 = bias_dtype == DHR_VAL_F32; a.bias_f16 = bias_dtype == DHR_VAL_F16;
+  a.bias = bias; dtype_flags(bias_dtype, a.bias_f32, a.bias_f16);
   a.tw = term_weights; a.ld_tw = ld_weights; a.mask = mask; a.ld_mask = ld_mask;
   a.B = batch; a.T = n_tokens; a.H = hidden_dim; a.V = vocab;
   a.vec_h = (uintptr_t)hidden % 16 == 0 && ld_batch % 8 == 0 && ld_token % 8 == 0;
@@ -108,16 +108,7 @@ extern "C" int dhr_lexical_proj_head(int32_t device, int32_t mem_kind, int32_t m
   const bool direct = mode == MODE_RAW;                  // fp32 reps are the output itself
   a.reps = direct ? (float*)out_value : (float*)(ws + l.reps);
   a.ld_reps = direct ? ld_value : vocab;
-  const int64_t BT = batch * n_tokens;
-  hipLaunchKernelGGL(proj_count_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(proj_scan_kernel, dim3(1), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(proj_fill_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
-  const dim3 g_stats((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), g_fold((unsigned)l.n_ntiles, (unsigned)((batch + a.group - 1) / a.group));
-  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL(proj_stats_kernel<__bf16>, g_stats, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(proj_stats_kernel<_Float16>, g_stats, dim3(256), 0, s, a);
-  hipLaunchKernelGGL(proj_combine_kernel, dim3((unsigned)((BT + 255) / 256)), dim3(256), 0, s, a);
-  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL((proj_fold_kernel<__bf16, false>), g_fold, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((proj_fold_kernel<_Float16, false>), g_fold, dim3(256), 0, s, a);
+  launch_forward<false>(value_dtype, a, s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(dhr::lexical_record_from_reps(direct ? nullptr : a.reps, vocab, mode, batch, vocab, geo.out_cols, geo.W, geo.n_groups, geo.remove, out_value,
                                         out_value_dtype == DHR_VAL_F32, ld_value, out_index, index_dtype == DHR_IDX_I16, ld_index, cls,

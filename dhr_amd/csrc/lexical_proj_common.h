@@ -4,6 +4,7 @@
 // the staging moves bytes, the fragment layouts of v_mfma_f32_32x32x16_f16 and _bf16 are the same, so tiling, walk and reduction order are common.
 #pragma once
 #include "lexical_common.h"
+#include "op_dispatch.h"
 
 // Internal linkage on purpose: each translation unit that includes this header compiles its own copy of the kernels below, the non-template
 // ones (count, scan, fill, statistics, combine) included.  The duplication costs code size only and keeps the launches free of cross-unit symbols.
@@ -49,6 +50,9 @@ struct ProjArgs {
   float* pwin;
   int64_t ld_pwin;
 };
+
+// the dtype of the bias, or of an output of the training backward, as the flag pair the kernels read: fp32, fp16, neither (then it is E)
+inline void dtype_flags(int val_dtype, int& f32, int& f16) { f32 = val_dtype == DHR_VAL_F32; f16 = val_dtype == DHR_VAL_F16; }
 
 __global__ void __launch_bounds__(64) proj_count_kernel(ProjArgs a) {
   const int64_t b = blockIdx.x;
@@ -422,6 +426,20 @@ inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 inline int proj_stats_split(int64_t BT, int n_ntiles) {
   const int64_t m_tiles = std::max<int64_t>(1, (BT + TM - 1) / TM);
   return (int)std::min<int64_t>(std::min<int64_t>(MAX_SPLIT, n_ntiles), std::max<int64_t>(1, (FILL_WGS + m_tiles - 1) / m_tiles));
+}
+
+// the forward of both heads on a filled ProjArgs: compaction of the unmasked rows, statistics, combine, fold (TRAIN: with tok and pwin).
+// value_dtype is DHR_VAL_F16 or DHR_VAL_BF16; the caller asks hipGetLastError()
+template <bool TRAIN>
+void launch_forward(int value_dtype, const ProjArgs& a, hipStream_t s) {
+  const int64_t BT = a.B * a.T;
+  hipLaunchKernelGGL(proj_count_kernel, dim3((unsigned)a.B), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(proj_scan_kernel, dim3(1), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(proj_fill_kernel, dim3((unsigned)a.B), dim3(64), 0, s, a);
+  const dim3 g_stats((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), g_fold((unsigned)a.n_ntiles, (unsigned)((a.B + a.group - 1) / a.group));
+  with_half_type(value_dtype, [&](auto t) { hipLaunchKernelGGL(proj_stats_kernel<typename decltype(t)::type>, g_stats, dim3(256), 0, s, a); });
+  hipLaunchKernelGGL(proj_combine_kernel, dim3((unsigned)((BT + 255) / 256)), dim3(256), 0, s, a);
+  with_half_type(value_dtype, [&](auto t) { hipLaunchKernelGGL((proj_fold_kernel<typename decltype(t)::type, TRAIN>), g_fold, dim3(256), 0, s, a); });
 }
 
 }  // namespace

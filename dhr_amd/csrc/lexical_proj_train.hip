@@ -25,6 +25,7 @@
 // anywhere, every sum in a fixed order -- two runs are bit-identical.  dbias is the fp32 sum of the unrounded dx.
 // Everything is enqueued on the caller's stream; nothing is allocated.  NaN / inf inputs are out of scope.
 #include "host_stage.h"
+#include "op_dispatch.h"
 #include "lexical_proj_common.h"
 
 namespace {
@@ -402,7 +403,7 @@ ProjArgs proj_args(const Layout& l, const void* hidden, int64_t batch, int32_t n
   ProjArgs a{};
   a.hid = (const _Float16*)hidden + (int64_t)skip_tokens * ld_token; a.ld_hb = ld_batch; a.ld_ht = ld_token;
   a.wgt = (const _Float16*)weight; a.ld_w = ld_weight;
-  a.bias = bias; a.bias_f32 = bias_dtype == DHR_VAL_F32; a.bias_f16 = bias_dtype == DHR_VAL_F16;
+  a.bias = bias; dtype_flags(bias_dtype, a.bias_f32, a.bias_f16);
   a.tw = term_weights; a.ld_tw = ld_weights; a.mask = mask; a.ld_mask = ld_mask;
   a.B = batch; a.T = n_tokens; a.H = hidden_dim; a.V = vocab;
   a.vec_h = (uintptr_t)a.hid % 16 == 0 && ld_batch % 8 == 0 && ld_token % 8 == 0;
@@ -416,15 +417,15 @@ ProjArgs proj_args(const Layout& l, const void* hidden, int64_t batch, int32_t n
 
 // One launch per slab of H: up to MAX_CHUNKS 64-column chunks fit the registers; a wider H (above 768) is cut into equal slabs, each of
 // which computes x again.  dbias belongs to the first slab; where it is all that is wanted (no out), the later slabs have nothing to write.
-template <typename E, int PASS>
-void launch_grad(int hidden_dim, dim3 grid, hipStream_t s, const ProjArgs& a, GradArgs q) {
+template <int PASS>
+void launch_grad(int value_dtype, int hidden_dim, dim3 grid, hipStream_t s, const ProjArgs& a, GradArgs q) {
   const int n_chunks = (hidden_dim + BK - 1) / BK;
   const int n_slabs = (n_chunks + MAX_CHUNKS - 1) / MAX_CHUNKS, per = (n_chunks + n_slabs - 1) / n_slabs;
   for (int c = 0; c < n_chunks; c += per) {
     q.c_lo = c; q.c_n = std::min(per, n_chunks - c);
-    if (per <= 2) hipLaunchKernelGGL((proj_grad_kernel<E, PASS, 2>), grid, dim3(256), 0, s, a, q);
-    else if (per <= 6) hipLaunchKernelGGL((proj_grad_kernel<E, PASS, 6>), grid, dim3(256), 0, s, a, q);
-    else hipLaunchKernelGGL((proj_grad_kernel<E, PASS, MAX_CHUNKS>), grid, dim3(256), 0, s, a, q);
+    with_half_type(value_dtype, [&](auto t) { with_int<2, 6, MAX_CHUNKS>(per <= 2 ? 2 : per <= 6 ? 6 : MAX_CHUNKS, [&](auto n) {
+      hipLaunchKernelGGL((proj_grad_kernel<typename decltype(t)::type, PASS, decltype(n)::value>), grid, dim3(256), 0, s, a, q);
+    }); });
     if (!q.out) break;
     q.dbias = nullptr;
   }
@@ -461,16 +462,7 @@ extern "C" int dhr_lexical_proj_train(int32_t device, int32_t mem_kind, const vo
   a.reps = out_reps; a.ld_reps = ld_reps;
   a.tok = out_tokens; a.ld_tok = ld_tokens;
   a.pwin = out_pwin; a.ld_pwin = ld_pwin;
-  const int64_t BT = batch * n_tokens;
-  hipLaunchKernelGGL(proj_count_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(proj_scan_kernel, dim3(1), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(proj_fill_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
-  const dim3 g_stats((unsigned)((BT + TM - 1) / TM), (unsigned)a.n_split), g_fold((unsigned)l.n_ntiles, (unsigned)((batch + a.group - 1) / a.group));
-  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL(proj_stats_kernel<__bf16>, g_stats, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(proj_stats_kernel<_Float16>, g_stats, dim3(256), 0, s, a);
-  hipLaunchKernelGGL(proj_combine_kernel, dim3((unsigned)((BT + 255) / 256)), dim3(256), 0, s, a);
-  if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL((proj_fold_kernel<__bf16, true>), g_fold, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((proj_fold_kernel<_Float16, true>), g_fold, dim3(256), 0, s, a);
+  launch_forward<true>(value_dtype, a, s);
   HIP_TRY(hipGetLastError());
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -514,14 +506,12 @@ extern "C" int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const
   for (int64_t lo = 0; lo < batch; lo += 65535) {           // (grid y limit)
     const unsigned rows = (unsigned)std::min<int64_t>(65535, batch - lo);
     float* dw = grad_term_weights ? grad_term_weights + lo * ld_grad_term_weights : nullptr;
-    if (small)
-      hipLaunchKernelGGL(proj_route_sum_kernel<RT_SMALL>, dim3((unsigned)((T + RT_SMALL - 1) / RT_SMALL), rows), dim3(256), 0, s,
-                         grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, pwin + lo * ld_pwin, ld_pwin,
-                         term_weights + lo * ld_weights, ld_weights, mask + lo * ld_mask, ld_mask, T, vocab, D + lo * T, dw, ld_grad_term_weights);
-    else
-      hipLaunchKernelGGL(proj_route_sum_kernel<RT_BIG>, dim3((unsigned)((T + RT_BIG - 1) / RT_BIG), rows), dim3(256), 0, s,
-                         grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, pwin + lo * ld_pwin, ld_pwin,
-                         term_weights + lo * ld_weights, ld_weights, mask + lo * ld_mask, ld_mask, T, vocab, D + lo * T, dw, ld_grad_term_weights);
+    with_int<RT_SMALL, RT_BIG>(small ? RT_SMALL : RT_BIG, [&](auto r) {
+      constexpr int RT = decltype(r)::value;
+      hipLaunchKernelGGL(proj_route_sum_kernel<RT>, dim3((unsigned)((T + RT - 1) / RT), rows), dim3(256), 0, s, grad_reps + lo * ld_grad_reps,
+                         ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, pwin + lo * ld_pwin, ld_pwin, term_weights + lo * ld_weights, ld_weights,
+                         mask + lo * ld_mask, ld_mask, T, vocab, D + lo * T, dw, ld_grad_term_weights);
+    });
   }
   HIP_TRY(hipGetLastError());
   GradArgs q{};
@@ -531,23 +521,22 @@ extern "C" int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const
     hipLaunchKernelGGL(proj_zero_rows_kernel, dim3((unsigned)(batch * (skip_tokens + T))), dim3(256), 0, s, a, grad_hidden,
                        (int)(grad_hidden_dtype == DHR_VAL_F32), ld_grad_batch, ld_grad_token, (int)skip_tokens);
     q.out = (char*)grad_hidden + (int64_t)skip_tokens * ld_grad_token * es;
-    q.out_f32 = grad_hidden_dtype == DHR_VAL_F32; q.out_f16 = grad_hidden_dtype == DHR_VAL_F16; q.ld_ob = ld_grad_batch; q.ld_ot = ld_grad_token;
+    dtype_flags(grad_hidden_dtype, q.out_f32, q.out_f16); q.ld_ob = ld_grad_batch; q.ld_ot = ld_grad_token;
     q.partial = (float*)((char*)workspace + l.partial); q.n_split = l.grad_split;
-    if (value_dtype == DHR_VAL_BF16) launch_grad<__bf16, 2>(hidden_dim, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)l.grad_split), s, a, q);
-    else launch_grad<_Float16, 2>(hidden_dim, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)l.grad_split), s, a, q);
+    launch_grad<2>(value_dtype, hidden_dim, dim3((unsigned)((BT + TM - 1) / TM), (unsigned)l.grad_split), s, a, q);
     if (l.grad_split > 1) {
       const dim3 g_comb((unsigned)BT, (unsigned)((hidden_dim + 255) / 256));
-      if (value_dtype == DHR_VAL_BF16) hipLaunchKernelGGL(proj_grad_combine_kernel<__bf16>, g_comb, dim3(256), 0, s, a, q);
-      else hipLaunchKernelGGL(proj_grad_combine_kernel<_Float16>, g_comb, dim3(256), 0, s, a, q);
+      with_half_type(value_dtype, [&](auto t) {
+        hipLaunchKernelGGL(proj_grad_combine_kernel<typename decltype(t)::type>, g_comb, dim3(256), 0, s, a, q);
+      });
     }
     HIP_TRY(hipGetLastError());
   }
   if (grad_weight || grad_bias) {                          // pass 3
-    q.out = grad_weight; q.out_f32 = grad_weight_dtype == DHR_VAL_F32; q.out_f16 = grad_weight_dtype == DHR_VAL_F16; q.ld_ob = ld_grad_weight; q.ld_ot = 0;
-    q.dbias = grad_bias; q.dbias_f32 = grad_bias_dtype == DHR_VAL_F32; q.dbias_f16 = grad_bias_dtype == DHR_VAL_F16;
+    q.out = grad_weight; dtype_flags(grad_weight_dtype, q.out_f32, q.out_f16); q.ld_ob = ld_grad_weight; q.ld_ot = 0;
+    q.dbias = grad_bias; dtype_flags(grad_bias_dtype, q.dbias_f32, q.dbias_f16);
     q.partial = nullptr; q.n_split = 1;
-    if (value_dtype == DHR_VAL_BF16) launch_grad<__bf16, 3>(hidden_dim, dim3((unsigned)((vocab + TM - 1) / TM)), s, a, q);
-    else launch_grad<_Float16, 3>(hidden_dim, dim3((unsigned)((vocab + TM - 1) / TM)), s, a, q);
+    launch_grad<3>(value_dtype, hidden_dim, dim3((unsigned)((vocab + TM - 1) / TM)), s, a, q);
     HIP_TRY(hipGetLastError());
   }
   return DHR_OK;

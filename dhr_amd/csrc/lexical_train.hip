@@ -20,6 +20,7 @@
 // Both passes take the model's full [B, L, V] logits and skip_tokens (the reference drops token 0): the gradient of the whole tensor is
 // written, so autograd never pads the gradient of a [:, 1:] view.  Everything is enqueued on the caller's stream; nothing is allocated.
 #include "host_stage.h"
+#include "op_dispatch.h"
 #include "lexical_common.h"
 
 namespace {
@@ -216,19 +217,17 @@ extern "C" int dhr_lexical_head_train(int32_t device, int32_t mem_kind, const vo
   const int T = n_tokens;
   float4* stats = (float4*)workspace;
   const dim3 g_stats((unsigned)(batch * T)), g_fold((unsigned)((vocab + 511) / 512), (unsigned)std::min<int64_t>(batch, 65535));
-#define LEX_TRAIN_FWD(T_)                                                                                                                        \
-  do {                                                                                                                                           \
-    const T_* x = (const T_*)logits + (int64_t)skip_tokens * ld_token;                                                                           \
-    hipLaunchKernelGGL(lexical_stats_kernel<T_>, g_stats, dim3(256), 0, s, x, ld_batch, ld_token, T, vocab, term_weights, ld_weights, mask,       \
-                       ld_mask, stats);                                                                                                          \
-    HIP_TRY(hipGetLastError());                                                                                                                  \
-    hipLaunchKernelGGL(lexical_fold_tok_kernel<T_>, g_fold, dim3(256), 0, s, x, ld_batch, ld_token, T, vocab, batch, (const float4*)stats,        \
-                       out_reps, ld_reps, out_tokens, ld_tokens);                                                                                \
-  } while (0)
-  if (value_dtype == DHR_VAL_F32) LEX_TRAIN_FWD(float); else if (value_dtype == DHR_VAL_BF16) LEX_TRAIN_FWD(__bf16); else LEX_TRAIN_FWD(_Float16);
-#undef LEX_TRAIN_FWD
-  HIP_TRY(hipGetLastError());
-  return DHR_OK;
+  return with_value_type_bf16(value_dtype, [&](auto t) -> int {
+    using TIN = typename decltype(t)::type;
+    const TIN* x = (const TIN*)logits + (int64_t)skip_tokens * ld_token;
+    hipLaunchKernelGGL(lexical_stats_kernel<TIN>, g_stats, dim3(256), 0, s, x, ld_batch, ld_token, T, vocab, term_weights, ld_weights, mask, ld_mask,
+                       stats);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(lexical_fold_tok_kernel<TIN>, g_fold, dim3(256), 0, s, x, ld_batch, ld_token, T, vocab, batch, (const float4*)stats, out_reps,
+                       ld_reps, out_tokens, ld_tokens);
+    HIP_TRY(hipGetLastError());
+    return DHR_OK;
+  });
 } DHR_CATCH_STATUS
 
 extern "C" int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const void* logits, int32_t value_dtype, int64_t batch, int32_t n_tokens,
@@ -254,39 +253,33 @@ extern "C" int dhr_lexical_head_backward(int32_t device, int32_t mem_kind, const
   const bool vec = vocab >= DC && (int64_t)vocab * es % 4 == 0 &&
                    ((uintptr_t)logits | (uintptr_t)grad_logits | (uintptr_t)(ld_batch * es) | (uintptr_t)(ld_token * es) | (uintptr_t)(ld_grad_batch * es) |
                     (uintptr_t)(ld_grad_token * es) | (uintptr_t)tokens | (uintptr_t)(ld_tokens * 2)) % 4 == 0;
+  const bool small = (int64_t)((T + RT_BIG - 1) / RT_BIG) * batch < 512;
+  const int rt = small ? RT_SMALL : RT_BIG;
   for (int64_t lo = 0; lo < batch; lo += 65535) {           // (grid y / z limits)
     const int64_t rows = std::min<int64_t>(65535, batch - lo);
-    const bool small = (int64_t)((T + RT_BIG - 1) / RT_BIG) * batch < 512;
-    const int rt = small ? RT_SMALL : RT_BIG;
     const dim3 g_sum((unsigned)((T + rt - 1) / rt), (unsigned)rows);
     const dim3 g_dx((unsigned)((vocab + 256 * DC - 1) / (256 * DC)), (unsigned)((L + DT - 1) / DT), (unsigned)rows);
-#define LEX_TRAIN_BWD(T_)                                                                                                                        \
-  do {                                                                                                                                           \
-    const T_* x = (const T_*)logits + lo * ld_batch;                                                                                             \
-    if (small)                                                                                                                                   \
-      hipLaunchKernelGGL((lexical_route_sum_kernel<T_, RT_SMALL>), g_sum, dim3(256), 0, s, x + (int64_t)skip_tokens * ld_token, ld_batch, ld_token, \
-                         T, vocab, stats + lo * T, grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, A + lo * T,    \
-                         grad_weights ? grad_weights + lo * ld_grad_weights : nullptr, ld_grad_weights);                                         \
-    else                                                                                                                                         \
-      hipLaunchKernelGGL((lexical_route_sum_kernel<T_, RT_BIG>), g_sum, dim3(256), 0, s, x + (int64_t)skip_tokens * ld_token, ld_batch, ld_token,  \
-                         T, vocab, stats + lo * T, grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, A + lo * T,    \
-                         grad_weights ? grad_weights + lo * ld_grad_weights : nullptr, ld_grad_weights);                                         \
-    HIP_TRY(hipGetLastError());                                                                                                                  \
-    if (grad_logits) {                                                                                                                           \
-      T_* d = (T_*)grad_logits + lo * ld_grad_batch;                                                                                             \
-      if (vec)                                                                                                                                   \
-        hipLaunchKernelGGL((lexical_dx_kernel<T_, true>), g_dx, dim3(256), 0, s, x, ld_batch, ld_token, skip_tokens, T, vocab, stats + lo * T,     \
-                           (const float*)A + lo * T, grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, d,          \
-                           ld_grad_batch, ld_grad_token);                                                                                        \
-      else                                                                                                                                       \
-        hipLaunchKernelGGL((lexical_dx_kernel<T_, false>), g_dx, dim3(256), 0, s, x, ld_batch, ld_token, skip_tokens, T, vocab, stats + lo * T,    \
-                           (const float*)A + lo * T, grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens, d,          \
-                           ld_grad_batch, ld_grad_token);                                                                                        \
-      HIP_TRY(hipGetLastError());                                                                                                                \
-    }                                                                                                                                            \
-  } while (0)
-    if (value_dtype == DHR_VAL_F32) LEX_TRAIN_BWD(float); else if (value_dtype == DHR_VAL_BF16) LEX_TRAIN_BWD(__bf16); else LEX_TRAIN_BWD(_Float16);
-#undef LEX_TRAIN_BWD
+    rc = with_value_type_bf16(value_dtype, [&](auto t) -> int {
+      using TIN = typename decltype(t)::type;
+      const TIN* x = (const TIN*)logits + lo * ld_batch;
+      with_int<RT_SMALL, RT_BIG>(rt, [&](auto r) {
+        hipLaunchKernelGGL((lexical_route_sum_kernel<TIN, decltype(r)::value>), g_sum, dim3(256), 0, s, x + (int64_t)skip_tokens * ld_token, ld_batch,
+                           ld_token, T, vocab, stats + lo * T, grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens,
+                           A + lo * T, grad_weights ? grad_weights + lo * ld_grad_weights : nullptr, ld_grad_weights);
+      });
+      HIP_TRY(hipGetLastError());
+      if (grad_logits) {
+        TIN* d = (TIN*)grad_logits + lo * ld_grad_batch;
+        with_flag(vec, [&](auto v) {
+          hipLaunchKernelGGL((lexical_dx_kernel<TIN, decltype(v)::value>), g_dx, dim3(256), 0, s, x, ld_batch, ld_token, skip_tokens, T, vocab,
+                             stats + lo * T, (const float*)A + lo * T, grad_reps + lo * ld_grad_reps, ld_grad_reps, tokens + lo * ld_tokens, ld_tokens,
+                             d, ld_grad_batch, ld_grad_token);
+        });
+        HIP_TRY(hipGetLastError());
+      }
+      return DHR_OK;
+    });
+    if (rc) return rc;
   }
   return DHR_OK;
 } DHR_CATCH_STATUS

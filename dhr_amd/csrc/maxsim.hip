@@ -16,6 +16,7 @@
 // Every sum has a fixed order that depends on the shape alone (no atomics): two runs are bit-identical, and a pair's score does not depend on
 // which other pairs are scored.  Products and sums are fp32.
 #include "host_stage.h"
+#include "op_dispatch.h"
 
 namespace {
 
@@ -349,12 +350,12 @@ Side make_side(const void* x, int64_t ld_tok, int64_t ld_batch, int64_t n, int l
 
 struct Problem {
   Side q, p;
-  int D, f32, group;
+  int D, val_dt, group;
   int64_t cols;
 };
 
 hipError_t launch_fwd(const Problem& x, float* out, int64_t ld_out, int16_t* arg, hipStream_t s) {
-  const int kc = ROW_BYTES / (x.f32 ? 4 : 2);
+  const int kc = ROW_BYTES / val_esize(x.val_dt);
   FwdArgs a{x.q, x.p, x.D, x.group, (x.D + kc - 1) / kc, out, ld_out, arg, x.cols};
   a.q.vec &= 1; a.p.vec &= 1;
   const bool multi = a.n_chunks > 1;
@@ -363,48 +364,35 @@ hipError_t launch_fwd(const Problem& x, float* out, int64_t ld_out, int16_t* arg
   const int nq = x.group == 0 && ((x.q.n + 7) / 8) * x.p.n >= FWD_FILL ? 2 : 1;
   const int per_wg = 4 * nq;
   const dim3 grid((unsigned)x.p.n, x.group > 0 ? 1u : (unsigned)((x.q.n + per_wg - 1) / per_wg));
-#define MAXSIM_FWD(T)                                                                                     \
-  do {                                                                                                    \
-    if (nq == 2) {                                                                                        \
-      if (multi) hipLaunchKernelGGL((maxsim_fwd_kernel<T, 2, true>), grid, dim3(256), 0, s, a);           \
-      else hipLaunchKernelGGL((maxsim_fwd_kernel<T, 2, false>), grid, dim3(256), 0, s, a);                \
-    } else {                                                                                              \
-      if (multi) hipLaunchKernelGGL((maxsim_fwd_kernel<T, 1, true>), grid, dim3(256), 0, s, a);           \
-      else hipLaunchKernelGGL((maxsim_fwd_kernel<T, 1, false>), grid, dim3(256), 0, s, a);                \
-    }                                                                                                     \
-  } while (0)
-  if (x.f32) MAXSIM_FWD(float); else MAXSIM_FWD(_Float16);
-#undef MAXSIM_FWD
+  with_value_type(x.val_dt, [&](auto t) { with_int<2, 1>(nq, [&](auto n) { with_flag(multi, [&](auto m) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((maxsim_fwd_kernel<T, decltype(n)::value, decltype(m)::value>), grid, dim3(256), 0, s, a);
+  }); }); });
   return hipGetLastError();
 }
 
-hipError_t launch_bwd(const Problem& x, const int16_t* arg, const float* G, int64_t ld_g, void* dq, void* dp, int grad_f32, hipStream_t s) {
+hipError_t launch_bwd(const Problem& x, const int16_t* arg, const float* G, int64_t ld_g, void* dq, void* dp, int grad_dt, hipStream_t s) {
   BwdArgs a{x.q, x.p, x.D, x.group, arg, x.cols, G, ld_g, dq, dp};
   // the dq gathers read 4 columns at once: 8 bytes of fp16, 16 of fp32
-  a.p.vec = aligned(x.p.x, x.p.ld_tok, x.p.ld_batch, x.f32 ? 4 : 2, x.f32 ? 16 : 8);
-#define MAXSIM_BWD(KERNEL, GRID, BLOCK, ...)                                                            \
-  do {                                                                                                  \
-    if (x.f32) {                                                                                        \
-      if (grad_f32) hipLaunchKernelGGL((KERNEL<float, float>), GRID, BLOCK, 0, s, __VA_ARGS__);         \
-      else hipLaunchKernelGGL((KERNEL<float, _Float16>), GRID, BLOCK, 0, s, __VA_ARGS__);               \
-    } else {                                                                                            \
-      if (grad_f32) hipLaunchKernelGGL((KERNEL<_Float16, float>), GRID, BLOCK, 0, s, __VA_ARGS__);      \
-      else hipLaunchKernelGGL((KERNEL<_Float16, _Float16>), GRID, BLOCK, 0, s, __VA_ARGS__);            \
-    }                                                                                                   \
-  } while (0)
+  a.p.vec = aligned(x.p.x, x.p.ld_tok, x.p.ld_batch, val_esize(x.val_dt), 4 * val_esize(x.val_dt));
+  // f(tag of the input type, tag of the gradient type)
+  auto with_types = [&](auto&& f) { with_value_type(x.val_dt, [&](auto t) { with_value_type(grad_dt, [&](auto o) { f(t, o); }); }); };
   if (dq) {
     int tpr = 1;
     while (tpr * 4 < x.D) tpr *= 2;                      // D <= 1024: at most 256
     const dim3 grid((unsigned)(x.q.n * x.q.len));
-    MAXSIM_BWD(maxsim_bwd_q_kernel, grid, dim3(256), a, tpr);
+    with_types([&](auto t, auto o) {
+      hipLaunchKernelGGL((maxsim_bwd_q_kernel<typename decltype(t)::type, typename decltype(o)::type>), grid, dim3(256), 0, s, a, tpr);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (dp) {
     const dim3 grid((unsigned)x.p.n, (unsigned)((x.p.len + BWD_P_ROWS - 1) / BWD_P_ROWS), (unsigned)((x.D + BWD_P_COLS - 1) / BWD_P_COLS));
-    MAXSIM_BWD(maxsim_bwd_p_kernel, grid, dim3(64), a);
+    with_types([&](auto t, auto o) {
+      hipLaunchKernelGGL((maxsim_bwd_p_kernel<typename decltype(t)::type, typename decltype(o)::type>), grid, dim3(64), 0, s, a);
+    });
   }
-#undef MAXSIM_BWD
   return hipGetLastError();
 }
 
@@ -423,10 +411,10 @@ int check_problem(int32_t mem_kind, const void* q, int64_t ld_q_tok, int64_t ld_
   if (Lp > MAX_LP) return set_error(DHR_ERR_UNSUPPORTED, "maxsim scores: more than 32767 passage tokens (the winning token is an int16)");
   if (A > MAX_BATCH || B > MAX_BATCH || Lq > MAX_LQ || A * Lq >= ((int64_t)1 << 31))
     return set_error(DHR_ERR_UNSUPPORTED, "maxsim scores: more than 131072 rows on a side, 65536 query tokens or 2^31 query tokens in all");
-  const int es = value_dtype == DHR_VAL_F32 ? 4 : 2;
+  const int es = val_esize(value_dtype);
   x.q = make_side(q, ld_q_tok, ld_q_batch, A, (int)Lq, es);
   x.p = make_side(p, ld_p_tok, ld_p_batch, B, (int)Lp, es);
-  x.D = D; x.f32 = value_dtype == DHR_VAL_F32; x.group = group;
+  x.D = D; x.val_dt = value_dtype; x.group = group;
   x.cols = group > 0 ? group : B;
   return DHR_OK;
 }
@@ -458,7 +446,7 @@ extern "C" int dhr_maxsim_scores(int32_t device, int32_t mem_kind, const void* q
     HIP_TRY(launch_fwd(x, out, ld_out, arg, s));
     return DHR_OK;
   }
-  const int es = x.f32 ? 4 : 2;
+  const int es = val_esize(x.val_dt);
   DevMem m_q, m_p, m_out, m_arg;
   HIP_TRY(stage_side(m_q, x.q, D, es, s));
   HIP_TRY(stage_side(m_p, x.p, D, es, s));
@@ -487,7 +475,7 @@ extern "C" int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, cons
   if (!dq && !dp) return DHR_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  const int gf32 = grad_dtype == DHR_VAL_F32, ges = gf32 ? 4 : 2;
+  const int ges = val_esize(grad_dtype);
   const size_t dq_bytes = (size_t)(A * Lq * D * ges), dp_bytes = (size_t)(B * Lp * D * ges);
   if (A == 0 || B == 0) {                               // no scored pair: the side that has rows gets zeros
     void* dst = dq ? dq : dp;
@@ -497,10 +485,10 @@ extern "C" int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, cons
     return DHR_OK;
   }
   if (mem_kind == DHR_MEM_DEVICE) {
-    HIP_TRY(launch_bwd(x, arg, grad_out, ld_grad, dq, dp, gf32, s));
+    HIP_TRY(launch_bwd(x, arg, grad_out, ld_grad, dq, dp, grad_dtype, s));
     return DHR_OK;
   }
-  const int es = x.f32 ? 4 : 2;
+  const int es = val_esize(x.val_dt);
   DevMem m_q, m_p, m_arg, m_g, m_dq, m_dp;
   HIP_TRY(stage_side(m_q, x.q, D, es, s));
   HIP_TRY(stage_side(m_p, x.p, D, es, s));
@@ -508,7 +496,7 @@ extern "C" int dhr_maxsim_scores_backward(int32_t device, int32_t mem_kind, cons
   HIP_TRY(stage_in(m_g, grad_out, ld_grad, A, x.cols, 4, s));
   if (dq) HIP_TRY(dev_alloc(m_dq, (int64_t)dq_bytes));
   if (dp) HIP_TRY(dev_alloc(m_dp, (int64_t)dp_bytes));
-  HIP_TRY(launch_bwd(x, (const int16_t*)m_arg.p, (const float*)m_g.p, x.cols, m_dq.p, m_dp.p, gf32, s));
+  HIP_TRY(launch_bwd(x, (const int16_t*)m_arg.p, (const float*)m_g.p, x.cols, m_dq.p, m_dp.p, grad_dtype, s));
   if (dq) HIP_TRY(hipMemcpyAsync(dq, m_dq.p, dq_bytes, hipMemcpyDeviceToHost, s));
   if (dp) HIP_TRY(hipMemcpyAsync(dp, m_dp.p, dp_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

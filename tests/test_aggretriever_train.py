@@ -378,6 +378,55 @@ def test_aggregate_forward_is_bit_identical_to_the_encoding_op_and_views_are_rea
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["float32", "float16"])
+@pytest.mark.parametrize("dims,full", [(1, True), (3, False)])
+def test_aggregate_backward_of_rows_shorter_than_one_vector(dtype, dims, full):
+    """vocab = 6 is below the 8 columns a thread of the backward owns, so the row takes the element-wise stores whatever its dtype (an fp32
+    row is never misaligned otherwise): three groups of 2 signed columns / two groups of 3, multiples of 0.25, against the restatement."""
+    import torch
+    from dhr_amd import aggretriever_train as AT
+    rng = np.random.default_rng(71)
+    B, vocab = 3, 6
+    assert remove_of(2 * dims if full else dims) == 0
+    x4 = rng.integers(-12, 13, (B, vocab))
+    x4[0, :2] = x4[0, 2:4]                                                                         # an equal maximum in two groups
+    G4 = rng.integers(-8, 9, (B, dims))
+    tdt = getattr(torch, dtype)
+    x = (torch.from_numpy(x4).to("cuda", tdt) / 4).requires_grad_(True)
+    out, route = AT.aggregate(x, dims, full, return_route=True)
+    out.backward(torch.from_numpy(G4).to("cuda", tdt) / 4)
+    t = agg_truth(x4 / 4.0, dims, full, G4 / 4.0)
+    assert out.dtype == tdt and x.grad.dtype == tdt and tuple(x.grad.shape) == (B, vocab)
+    assert (_np(out) == t["out"]).all() and np.array_equal(route.cpu().numpy(), t["route"])
+    assert np.array_equal(_np(x.grad), t["dreps"]) and x.grad.any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("id_dtype", ["int64", "int32"])
+@pytest.mark.parametrize("w_dtype", ["float32", "float16"])
+@pytest.mark.parametrize("vocab", [4100, 4101])
+def test_term_weight_head_of_every_id_and_weight_dtype_on_even_and_odd_rows(id_dtype, w_dtype, vocab):
+    """int64 / int32 ids with fp32 / fp16 weights; the rows of the int16 token tensor start at a multiple of 4 bytes (vocab even) or do not
+    (vocab odd: the element-wise stores); the vocabulary spans two workgroups of columns.  Forward, tokens and dL/dw against the restatement."""
+    import torch
+    from dhr_amd import aggretriever_train as AT
+    rng = np.random.default_rng(73)
+    B, L = 3, 12
+    ids = rng.integers(0, vocab, (B, L)).astype(np.int64)
+    ids[0, 3] = ids[0, 7]                                                                          # a repeated id
+    ids[1, 5], ids[2, 6] = vocab - 1, 4096                                                         # the last column, the first of the second block
+    w_np = (rng.permutation(B * (L - 1)).reshape(B, L - 1) - 10).astype(np.float32) / 8          # distinct multiples of 1/8, some negative
+    G = (rng.integers(-8, 9, (B, vocab)) / 4.0).astype(np.float32)
+    truth = head_truth(ids, w_np, vocab, 1, G)
+    w = torch.from_numpy(w_np).to("cuda", getattr(torch, w_dtype)).requires_grad_(True)
+    reps, tok = AT.term_weight_reps(torch.from_numpy(ids).to("cuda", getattr(torch, id_dtype)), w, vocab=vocab, return_tokens=True)
+    reps.backward(torch.from_numpy(G).cuda())
+    assert reps.dtype == torch.float32 and tok.dtype == torch.int16 and tok.is_contiguous() and w.grad.dtype == w.dtype
+    assert np.array_equal(_np(reps), truth["reps"]) and np.array_equal(tok.cpu().numpy(), truth["tok"])
+    assert np.array_equal(_np(w.grad), truth["dw"]) and w.grad.any()
+
+
+@pytest.mark.gpu
 def test_eager_composition_on_the_device():
     import torch
     from dhr_amd import aggretriever_train as AT

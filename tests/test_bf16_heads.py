@@ -33,7 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = {k: os.path.join(ROOT, "tests", "golden", k + "_golden.npz") for k in ("lexical", "lexical_train", "lexical_proj", "lexical_proj_train")}
 UB16, SUBB16 = 2.0 ** -8, 2.0 ** -126
 U16, SUB16 = 2.0 ** -11, 2.0 ** -25                      # (fp16, where a gradient comes back in fp16)
-LOGITS = [(5, 70, 762, 11), (3, 150, 1030, 12), (33, 40, 515, 13), (2, 9, 202, 14)]          # B, T, V, seed
+LOGITS = [(5, 70, 762, 11), (3, 150, 1030, 12), (33, 40, 515, 13), (2, 9, 202, 14),          # B, T, V, seed
+          (512, 2, 8, 15), (512, 2, 9, 15)]       # 512 workgroups of 16 tokens in the backward's reduction pass; 16- and 18-byte bf16 rows
 BF16 = _lib.VAL_BF16 if hasattr(_lib, "VAL_BF16") else 2
 
 

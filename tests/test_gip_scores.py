@@ -369,6 +369,75 @@ def test_gip_scores_on_strided_record_views():
             assert (out[:, n_p:] == -1.0).all()
 
 
+# (n_q, passages per query (group > 0) or passage rows, group, dims): what the launchers of gip_train.hip decide by the shape alone
+ARM_SHAPES = {"list, 16 x 16 tiles, one gradient row per thread": (5, 11, 0, 24),
+              "pairwise": (7, 3, 3, 40),
+              "list, 32 x 64 tiles, two (dq) and four (dp) gradient rows per thread": (512, 1024, 0, 64)}
+_ARM_CASES = {}
+
+
+def _arm_case(name):
+    """-> (qv, qi, pv, pi, Gs, truth of truth_scores), made once and left unchanged: values in multiples of 2^-6 and G in multiples of 2^-4
+    (exact in fp16), groups in [0, 100), or in [0, 4) at 64 dims so that the long gradient sums have many terms (every index dtype holds them)"""
+    if name not in _ARM_CASES:
+        n_q, n, group, dims = ARM_SHAPES[name]
+        n_p = n_q * n if group else n
+        rng = np.random.default_rng([19, n_q, n_p, dims])
+        qv, pv = (np.round(rng.uniform(-3, 3, (rows, dims)) * 64) / 64 for rows in (n_q, n_p))
+        qi, pi = (rng.integers(0, 100 if dims < 64 else 4, (rows, dims)) for rows in (n_q, n_p))
+        pairs = pairs_of("pair" if group else "list", n_q, n_p)
+        Gs = _random_g(rng, (n_q, group if group else n_p), True)
+        G = np.zeros((n_q, n_p))
+        G[pairs] = Gs.reshape(-1)
+        t = truth_scores(qv, qi, pv, pi, G, pairs)
+        _ARM_CASES[name] = (qv, qi, pv, pi, Gs, pairs, tuple(x[pairs].reshape(Gs.shape) for x in t[:2]) + t[2:])
+    return _ARM_CASES[name]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("idt", ["uint8", "int8", "int16"])
+@pytest.mark.parametrize("vdt", ["float32", "float16"])
+@pytest.mark.parametrize("name", list(ARM_SHAPES))
+def test_every_value_and_index_type_at_every_launch_shape(name, vdt, idt):
+    """Both value types with each of the three index types through gip_scores and its backward, at a shape for every arm the launchers pick:
+    the small and the large forward tile, the pairwise kernels, and one, two and four gradient rows per thread (512 and 1024 rows of 64 dims
+    on the differentiated side).  Scores and both gradients inside the bounds of the restatement."""
+    import torch
+    from dhr_amd import gip_scores as GS
+    n_q, n, group, dims = ARM_SHAPES[name]
+    qv, qi, pv, pi, Gs, pairs, (S, bS, dq, bq, dp, bp) = _arm_case(name)
+    tv, ti = getattr(torch, vdt), getattr(torch, idt)
+    tqv, tpv = (torch.from_numpy(x).to("cuda", tv).requires_grad_(True) for x in (qv, pv))
+    tqi, tpi = (torch.from_numpy(x).to("cuda", ti) for x in (qi, pi))
+    s = GS.gip_scores(tqv, tqi, tpv, tpi, group)
+    what = f"{name} {vdt} {idt}"
+    assert s.dtype == torch.float32 and tuple(s.shape) == Gs.shape
+    assert_within(s.detach().cpu().numpy(), S, bS, what + " scores")
+    s.backward(torch.from_numpy(Gs).cuda())
+    for side, x, d, b in (("dq", tqv, dq, bq), ("dp", tpv, dp, bp)):
+        assert x.grad.dtype == tv and x.grad.any()
+        assert_within(x.grad.cpu().numpy(), d, b, f"{what} {side}", fp16=vdt == "float16")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("idt", ["uint8", "int8", "int16"])
+@pytest.mark.parametrize("odt", ["float32", "float16"])
+def test_densify_backward_of_every_index_and_output_type(idt, odt):
+    """dL/dvalue [5, 24] in multiples of 2^-6 and groups below 7 of each index dtype -> dL/dreps [5, 10 + 7 * 24] in fp32 and in fp16:
+    the scatter of the restatement, exactly (densify itself produces uint8 or int16 groups only)."""
+    import torch
+    from dhr_amd import gip_scores as GS
+    rng = np.random.default_rng(23)
+    B, dims, groups, remove = 5, 24, 7, 10
+    vocab = remove + groups * dims
+    dv = np.round(rng.uniform(-3, 3, (B, dims)) * 64) / 64
+    idx = rng.integers(0, groups, (B, dims))
+    got = GS._densify_bwd(torch.from_numpy(dv).float().cuda(), torch.from_numpy(idx).to("cuda", getattr(torch, idt)), vocab, dims, remove,
+                          getattr(torch, odt))
+    assert got.dtype == getattr(torch, odt) and tuple(got.shape) == (B, vocab)
+    assert np.array_equal(got.cpu().numpy().astype(np.float64), scatter(dv, idx, vocab, dims, remove)) and got.any()
+
+
 @pytest.mark.gpu
 def test_fused_equals_composed_and_runs_are_bit_identical():
     import torch

@@ -299,6 +299,12 @@ RANDOM = [  # B, L, V, logits dtype, weights dtype, strided base, positive weigh
     (5, 2, 203, "float32", "float16", False, False),
     (3, 32, 30522, "float16", "float32", True, False),
     (3, 12, 203, "float16", "float16", True, True),
+    # ceil(T / 16) * B = 512 workgroups: the backward's reduction pass takes 16 tokens per workgroup.  Rows of 8 columns take the multi-dword
+    # accesses of the streaming pass, the 18-byte fp16 rows of 9 columns and rows below 8 columns (any dtype) the element-wise ones
+    (512, 3, 8, "float16", "float32", False, False),
+    (512, 3, 9, "float16", "float32", False, False),
+    (512, 3, 8, "float32", "float32", False, False),
+    (512, 3, 7, "float32", "float32", False, False),
 ]
 
 

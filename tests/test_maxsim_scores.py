@@ -268,11 +268,39 @@ def test_goldens_on_gpu_bit_equal():
                     assert np.array_equal(got, want), f"{key} {dtype} {req}: {what}, {int((got != want).sum())} entries differ"
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype,grad", [("float32", "float16"), ("float16", "float32")])
+def test_goldens_with_gradients_in_the_other_dtype(dtype, grad):
+    """The torch wrapper asks for gradients in the dtype of the inputs; the library also writes fp16 gradients of fp32 inputs and fp32
+    gradients of fp16 inputs.  The listwise fixture cases through the two entry points on host arrays: the same bits as above."""
+    lib = _lib.load()
+    code = {"float32": _lib.VAL_F32, "float16": _lib.VAL_F16}
+    for key, z, q, p, n, mode in golden_cases():
+        if mode != "list":
+            continue
+        (A, Lq, D), (B, Lp, _) = q.shape, p.shape
+        hq, hp, G = (np.ascontiguousarray(x, dtype=d) for x, d in ((q, dtype), (p, dtype), (z[key + "_G"], np.float32)))
+        out, arg = np.zeros((A, B), np.float32), np.zeros((A, B, Lq), np.int16)
+        dq, dp = np.zeros((A, Lq, D), grad), np.zeros((B, Lp, D), grad)
+        sides = (hq.ctypes.data, D, Lq * D, A, Lq, hp.ctypes.data, D, Lp * D, B, Lp, D, code[dtype], 0)
+        assert lib.dhr_maxsim_scores(0, _lib.MEM_HOST, *sides, out.ctypes.data, B, arg.ctypes.data, None) == _lib.DHR_OK, lib.dhr_last_error()
+        assert lib.dhr_maxsim_scores_backward(0, _lib.MEM_HOST, *sides, arg.ctypes.data, G.ctypes.data, B, dq.ctypes.data, dp.ctypes.data, code[grad],
+                                              None) == _lib.DHR_OK, lib.dhr_last_error()
+        assert np.array_equal(out, z[key + "_scores"]), f"{key} {dtype}: scores"
+        for got, want, what in ((dq, z[key + "_gq"] / 128.0, "dq"), (dp, z[key + "_gp"] / 128.0, "dp")):
+            assert np.array_equal(got.astype(np.float32), want.astype(grad).astype(np.float32)), f"{key} {dtype} -> {grad}: {what}"
+
+
 # (A, B, Lq, Lp, D) -> the seed of each dtype, chosen on the CPU so that no winner is ambiguous and no fp16 gradient subnormal (both asserted
 # below from the float64 restatement alone)
 RANDOM_CASES = [((3, 8, 31, 149, 128), {"float16": 1, "float32": 1}),
                 ((2, 4, 33, 65, 768), {"float16": 327, "float32": 0}),
-                ((5, 5, 7, 300, 24), {"float16": 0, "float32": 0})]
+                ((5, 5, 7, 300, 24), {"float16": 0, "float32": 0}),
+                # ceil(A / 8) * B = 512 workgroups: two queries per wave, with D inside one 256-byte chunk of both dtypes, above one fp16 chunk
+                # (128 columns) and above one fp32 chunk only (64 columns)
+                ((64, 64, 2, 2, 8), {"float16": 0, "float32": 0}),
+                ((64, 64, 2, 2, 130), {"float16": 1, "float32": 0}),
+                ((64, 64, 2, 2, 66), {"float16": 1, "float32": 0})]
 
 
 def _random_case(shape, dtype, seed):

@@ -1,5 +1,5 @@
 // State shared by the host-side translation units of the library (round 6 split of api.hip, 2 583 lines):
-//   index_build.hip   dhr_index_create / destroy / parameters / info, the index file
+//   index_build.hip   dhr_index_create / destroy / parameters / info, the index file (over index_layout.h: the layout of an index, its column steps and bucket deal; included there alone -- two op files have a function `layout` of their own)
 //   search_core.hip   workspace, query preparation, the phase controller (search_core)
 //   api.hip           the search entry points (dhr_search, dhr_search_rerank, the staged calls), dhr_score_rows, densify, PQ training, debug hooks, shard reduce
 #pragma once

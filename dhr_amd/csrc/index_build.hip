@@ -5,6 +5,8 @@
 #include <unistd.h>
 
 #include "dhr_state.h"
+#include "index_layout.h"
+static_assert(layout::TILE_ROWS == TILE_ROWS && layout::TILE_K == TILE_K && layout::SP_STAGE_A == SP_STAGE_A && layout::S8_STAGE_A == S8_STAGE_A && layout::SP_DENSE == SP_DENSE && layout::HEAVY_KEY_STRIDE == HEAVY_KEY_STRIDE, "index_layout.h restates the tile geometry of dhr_internal.h");
 
 extern "C" void dhr_index_destroy(dhr_index* ix) try {
   if (!ix) return;
@@ -21,15 +23,6 @@ extern "C" void dhr_index_destroy(dhr_index* ix) try {
 
 static int g_opt_dense_i8 = -1;      // -1: gated indexes with ungated columns only; 0: never; 1: dense-only indexes too
 static int g_opt_gated_i8 = -1;      // int8 image of the gated half: -1 by corpus size (>= GATED_I8_MIN_ROWS rows; _NARROW where the ungated half is narrower than half the gated one), 0 never, 1 wherever the layout allows it
-// The int8 gated image takes ~30 % off the bound GEMM and lets ~1.5-2x the rows through the filter (its values are rounded UP): the GEMM scales
-// with the rows of the shard, the extra refine / rescoring work with the queries only.  Measured (exact search, ms per step, fp16 / int8 image):
-// 8.84 M x (768+768) 169.7 / 137.1; a 1.1 M-row shard of it 3.5 / 2.9 per eighth of the step; 5.4 M x (768+128) 80.0 / 71.9 and 84.9 / 85.6;
-// 2.7 M 28.5 / 35.7; 0.52 M 27.8 / 44.5; 58 k 2.9 / 3.7.
-// Break-even: ~2 M rows where the ungated half is as wide as the gated one (0.66 ps saved per (query, row) pair against ~1.4 us of extra
-// refine / rescoring per query), ~5 M rows with a narrow ungated half (0.35 ps per pair); a SHARD of a sharded search collects only its share
-// of the candidates, so it breaks even 8x earlier -- hence 1 M / 4 M.
-constexpr int64_t GATED_I8_MIN_ROWS = 1000000, GATED_I8_MIN_ROWS_NARROW = 4000000;
-constexpr int64_t DENSE_ONLY_I8_MIN_ROWS = 1000000;      // dense-only indexes: the int8 image by default from this many rows (if its margin is small enough, dhr_index_create)
 extern "C" int dhr_set_option(int32_t option, int64_t value) try {
   if (option == DHR_OPT_DENSE_I8) { g_opt_dense_i8 = value < 0 ? -1 : (value != 0); return DHR_OK; }
   if (option == DHR_OPT_GATED_I8) { g_opt_gated_i8 = value < 0 ? -1 : (value != 0); return DHR_OK; }
@@ -45,7 +38,7 @@ extern "C" int dhr_index_get_info(const dhr_index* ix, int32_t what, double* out
     case DHR_INFO_ROW_NORM_MAX: *out = ix->dmax; return DHR_OK;
     case DHR_INFO_GATED_I8: *out = ix->gated_i8 ? 1.0 : 0.0; return DHR_OK;
     case DHR_INFO_GEMM_KERNEL: *out = (double)ix->last_gemm_kernel; return DHR_OK;
-    case DHR_INFO_TILE_BYTES: *out = (double)((size_t)ix->n_tiles * ((size_t)ix->ts * (ix->gated_i8 ? S8_STAGE_A : SP_STAGE_A) + (size_t)ix->td * SP_DENSE)); return DHR_OK;
+    case DHR_INFO_TILE_BYTES: *out = (double)layout::tile_bytes(ix->n_tiles, ix->ts, ix->td, ix->gated_i8); return DHR_OK;
   }
   return set_error(DHR_ERR_INVALID, "unknown info id");
 } DHR_CATCH_STATUS
@@ -150,301 +143,180 @@ static int build_tiles(dhr_index* ix, hipStream_t s) {
   return DHR_OK;
 }
 
-// Per-slice index-value -> bucket table, balanced by value MASS (greedy: heaviest value first into the lightest bucket;
-// values that never occur with a non-zero entry are dealt round-robin).
-static void build_bucket_map(const std::vector<float>& hist, int d_dlr, int nb, std::vector<uint8_t>& map) {
-  map.assign((size_t)d_dlr * 256, 0);
-  std::vector<int> order(256);
-  std::vector<double> load(nb);
-  for (int j = 0; j < d_dlr; ++j) {
-    const float* h = &hist[(size_t)j * 256];
-    for (int v = 0; v < 256; ++v) order[v] = v;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return h[a] > h[b]; });
-    std::fill(load.begin(), load.end(), 0);
-    int rr = 0;
-    for (int v : order) {
-      int best = 0;
-      if (h[v] == 0) best = rr++ % nb;                   // unseen values: round robin
-      else
-        for (int b = 1; b < nb; ++b)
-          if (load[b] < load[best]) best = b;
-      map[(size_t)j * 256 + v] = (uint8_t)best;
-      load[best] += h[v];
-    }
-  }
+// What a build holds until it reaches its end: every early return and every exception releases the scratch and the half-built handle
+struct Build {
+  dhr_index* ix = nullptr; layout::IndexLayout L; hipStream_t s = nullptr; const dhr_index_desc* d = nullptr;      // d: the CALLER's descriptor and widths: only the step that reads the caller's arrays (step_ingest) uses it
+  void* stage = nullptr; uint32_t* d_flags = nullptr;
+  uint32_t flags[4] = {0, 0, 0, 0};       // what scan_rows_kernel left, as bit patterns: max ||d||^2, any negative gated value, largest ungated / gated |value|
+  ~Build() { (void)hipFree(stage); (void)hipFree(d_flags); if (ix) dhr_index_destroy(ix); }
+};
+#define STEP(call) do { const int _rc = (call); if (_rc != DHR_OK) return _rc; } while (0)
+using layout::bits_to_float;
+// One device array of a build; the `counted` ones are the index that dhr_index_device_bytes reports
+template <class T> static int dev_array(dhr_index* ix, T** p, size_t bytes, bool counted, const char* what) {
+  if (hipMalloc((void**)p, bytes) != hipSuccess) return set_error(DHR_ERR_HIP, "hipMalloc of " + std::to_string(bytes) + " bytes for " + what + " failed");
+  ix->index_bytes += counted ? (int64_t)bytes : 0;
+  return DHR_OK;
 }
-
-extern "C" int dhr_index_create(const dhr_index_desc* d_user, dhr_index** out) try {
-  if (!d_user || !out) return set_error(DHR_ERR_INVALID, "null argument");
-  // --emb_dim that is not a multiple of 8: the library appends zero slices (dhr_index::dlr_pad); below, `d` is the descriptor with
-  // the padded width -- only the two places that READ the caller's arrays (the index copy, ingest) use the caller's widths
-  dhr_index_desc d_padded = *d_user;
-  const int dlr_pad = (d_user->d_dlr > 0 && d_user->index != nullptr && d_user->d_dlr % 8) ? 8 - d_user->d_dlr % 8 : 0;
-  if (d_user->ld_value < (int64_t)d_user->d_dlr + d_user->d_cls) return set_error(DHR_ERR_INVALID, "bad value pointer / ld_value");
-  if (d_user->index && d_user->index_dtype != DHR_IDX_NONE && d_user->ld_index < d_user->d_dlr) return set_error(DHR_ERR_INVALID, "bad ld_index");
-  d_padded.d_dlr += dlr_pad;
-  if (dlr_pad) { d_padded.ld_value = std::max<int64_t>(d_padded.ld_value, (int64_t)d_padded.d_dlr + d_padded.d_cls); d_padded.ld_index = std::max<int64_t>(d_padded.ld_index, d_padded.d_dlr); }
-  const dhr_index_desc* d = &d_padded;
+// Largest finite |value| of columns [first, first + n) of the device copy (bit patterns: layout::ungated_steps / gated_steps read them)
+static int scan_col_max(const Build& b, int first, int n, std::vector<uint32_t>& cm) {
+  DevMem d_cm;
+  cm.assign((size_t)n, 0u);
+  HIP_TRY(hipMalloc(&d_cm.p, cm.size() * 4));
+  HIP_TRY(hipMemsetAsync(d_cm.p, 0, cm.size() * 4, b.s));
+  HIP_TRY(launch_col_absmax(b.ix->vals_rm, b.ix->k_rm, b.ix->n_rows, first, n, (uint32_t*)d_cm.p, b.s));
+  HIP_TRY(hipMemcpy(cm.data(), d_cm.p, cm.size() * 4, hipMemcpyDeviceToHost));
+  return DHR_OK;
+}
+static void apply_layout(dhr_index* ix, const layout::IndexLayout& L) {
+  ix->n_rows = L.in.n_rows; ix->n_tiles = L.n_tiles; ix->d_dlr = L.d_dlr; ix->d_cls = L.in.d_cls; ix->dlr_pad = L.dlr_pad; ix->k = L.k; ix->k_rm = L.k_rm;
+  ix->idx_dtype = L.has_idx ? L.in.idx_dtype : DHR_IDX_NONE; ix->n_buckets = L.n_buckets;
+  ix->ts = L.ts; ix->td = L.td; ix->kt = L.kt; ix->ksteps = L.ksteps; ix->dense_i8 = L.dense_i8; ix->gated_i8 = L.gated_i8;
+}
+// corpus copies: the index array as it is (zero slices appended), the values through pass 1 -- row-major device copy, norms and sign scan
+static int step_ingest(Build& b) {
+  dhr_index* ix = b.ix; const dhr_index_desc* d = b.d;
+  STEP(dev_array(ix, &ix->vals_rm, (size_t)ix->n_rows * ix->k_rm * 2, true, "the row-major corpus copy"));
+  STEP(dev_array(ix, &b.d_flags, 16, false, "the scan results"));
+  HIP_TRY(hipMemsetAsync(b.d_flags, 0, 16, b.s));
+  if (b.L.has_idx) {
+    const size_t es = idx_esize(ix->idx_dtype), ib = (size_t)ix->n_rows * ix->d_dlr * es;
+    STEP(dev_array(ix, &ix->c_idx, ib, true, "the index array"));
+    if (ix->dlr_pad) HIP_TRY(hipMemsetAsync(ix->c_idx, 0, ib, b.s));
+    HIP_TRY(hipMemcpy2DAsync(ix->c_idx, ix->d_dlr * es, d->index, d->ld_index * es, d->d_dlr * es, (size_t)ix->n_rows,
+                             d->mem_kind == DHR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, b.s));
+  }
+  const int64_t block_rows = 65536, stage_bytes = std::min<int64_t>(block_rows, ix->n_rows) * ix->k * 2;
+  if (d->mem_kind == DHR_MEM_HOST || ix->dlr_pad > 0) STEP(dev_array(ix, &b.stage, stage_bytes, false, "the staging buffer"));
+  if (ix->dlr_pad > 0) HIP_TRY(hipMemsetAsync(b.stage, 0, stage_bytes, b.s));
+  return ingest(ix, d, b.d_flags, b.stage, block_rows, b.s);
+}
+static int step_scan_results(Build& b) {
+  HIP_TRY(hipMemcpy(b.flags, b.d_flags, 16, hipMemcpyDeviceToHost));
+  b.ix->dmax = std::sqrt(bits_to_float(b.flags[0])) * 1.0005f + 1e-30f;
+  b.ix->abs_mode = b.flags[1] != 0;     // negative gated values: the bound needs |q|.|d| on the gated half
+  return DHR_OK;
+}
+// int8 image of the ungated columns: scale and column steps, the corpus-wide maxima of the row error and norm that the filter margin pays for, and -- a dense-only
+// index on trial -- the verdict: a rejected trial continues as the fp16 layout
+static int step_ungated_i8(Build& b) {
+  dhr_index* ix = b.ix; if (!ix->dense_i8) return DHR_OK;
+  const float amax = bits_to_float(b.flags[2]), gmax = bits_to_float(b.flags[3]);
+  ix->i8_scale = std::max(amax > 0.f ? amax / 127.f : 1.f, gmax / 60000.f);      // gated values must fit fp16 in units of the scale
+  std::vector<uint32_t> cm;
+  STEP(scan_col_max(b, ix->d_dlr, ix->d_cls, cm));
+  const std::vector<float> cs = layout::ungated_steps(cm, ix->i8_scale);
+  STEP(dev_array(ix, &ix->i8_col_scale, cs.size() * 4, false, "the ungated column steps"));
+  HIP_TRY(hipMemcpy(ix->i8_col_scale, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(b.d_flags, 0, 16, b.s));
+  HIP_TRY(launch_i8_row_err(ix->vals_rm, ix->k_rm, ix->n_rows, ix->d_dlr, ix->d_cls, ix->i8_scale, ix->i8_col_scale, b.d_flags, b.s));
+  uint32_t err[2] = {0, 0};
+  HIP_TRY(hipMemcpy(err, b.d_flags, 8, hipMemcpyDeviceToHost));
+  ix->i8_ec = std::sqrt(bits_to_float(err[0])) * 1.001f; ix->i8_nc = std::sqrt(bits_to_float(err[1])) * 1.001f;
+  if (b.L.dense_only_trial && !layout::trial_keeps_i8(ix->d_cls, ix->i8_ec, ix->i8_nc)) {
+    hipFree(ix->i8_col_scale); ix->i8_col_scale = nullptr; ix->i8_scale = ix->i8_ec = ix->i8_nc = 0.f;
+    apply_layout(ix, b.L = layout::fp16_fallback(b.L));
+  }
+  return DHR_OK;
+}
+// Dense-only int8 index: residual image = the refine level between the filter and the exact rescoring.  The int8 margin is  ||q'|| ec (corpus rounding) + ||q' - q8'|| nc (query rounding); with the residuals the
+// first term is MEASURED per candidate from 384 bytes (four bits per value) instead of bounded, and the candidates that only the corpus half of the margin let through never reach the 1.5 KB rows of the exact rescoring.
+static int step_residual(Build& b) {
+  dhr_index* ix = b.ix; if (!b.L.has_residual(ix->i8_ec)) return DHR_OK;
+  ix->resid_ld = b.L.resid_ld();
+  STEP(dev_array(ix, &ix->resid8, (size_t)ix->n_rows * ix->resid_ld, true, "the residual image"));
+  ix->resid_ec2 = std::sqrt((float)ix->d_cls) * ix->i8_scale / 28.f;       // every residual is within half of 1/14 of its column's step: scale / 28 in the weighted space
+  HIP_TRY(launch_resid_build(ix->vals_rm, ix->k_rm, ix->n_rows, ix->d_dlr, ix->d_cls, ix->i8_col_scale, ix->resid8, ix->resid_ld, b.s));
+  return DHR_OK;
+}
+static int step_alloc_tiles(Build& b) { return dev_array(b.ix, &b.ix->tiles, b.L.tile_bytes(), true, "the corpus tiles"); }
+// int8 image of the gated columns: their steps (layout::gated_steps), the shift range and the row sums that the integer GEMM starts from
+static int step_gated_i8(Build& b) {
+  dhr_index* ix = b.ix; if (!ix->gated_i8) return DHR_OK;
+  std::vector<uint32_t> cm;
+  STEP(scan_col_max(b, 0, ix->d_dlr, cm));
+  const layout::GatedSteps g = layout::gated_steps(cm, bits_to_float(b.flags[3]));
+  ix->g8_sref = g.sref; ix->g8_max_shift = b.L.g8_max_shift();
+  STEP(dev_array(ix, &ix->g8_inv_cs, cm.size() * 4, false, "the gated column steps"));
+  STEP(dev_array(ix, &ix->g8_w, cm.size() * 4, false, "the gated column weights"));
+  HIP_TRY(hipMemcpy(ix->g8_inv_cs, g.inv_cs.data(), cm.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ix->g8_w, g.w.data(), cm.size() * 4, hipMemcpyHostToDevice));
+  STEP(dev_array(ix, &ix->g8_rsum, (size_t)ix->n_tiles * TILE_ROWS * 4, true, "the gated row sums"));
+  HIP_TRY(launch_g8_row_sum(ix->vals_rm, ix->k_rm, ix->n_rows, ix->n_tiles * TILE_ROWS, ix->d_dlr, ix->abs_mode, ix->g8_inv_cs, ix->g8_rsum, b.s));
+  return DHR_OK;
+}
+// bucket maps: all-zero for idx_buckets = 1 (it serves 8- and 16-bit index dtypes alike: bucket_of reads map[j][value & 255]); two buckets of 8-bit index values are dealt by
+// the value mass per (slice, index value) (layout::build_bucket_map); 16-bit ones have no map (value % 2)
+static int step_bucket_maps(Build& b) {
+  dhr_index* ix = b.ix;
+  const size_t mb = (size_t)ix->d_dlr * 256;
+  std::vector<uint8_t> map;
+  if (!b.L.has_idx || (ix->n_buckets > 1 && idx_esize(ix->idx_dtype) != 1)) return DHR_OK;
+  if (ix->n_buckets > 1) {
+    DevMem d_hist;
+    std::vector<float> hist(mb);
+    HIP_TRY(hipMalloc(&d_hist.p, mb * 4));
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, mb * 4, b.s));
+    HIP_TRY(launch_idx_hist((const uint8_t*)ix->c_idx, ix->vals_rm, ix->k_rm, ix->n_rows, ix->d_dlr, (float*)d_hist.p, b.s));
+    HIP_TRY(hipMemcpy(hist.data(), d_hist.p, mb * 4, hipMemcpyDeviceToHost));
+    layout::build_bucket_map(hist, ix->d_dlr, ix->n_buckets, map);
+  } else map.assign(mb, 0);
+  STEP(dev_array(ix, &ix->bucket_map, mb, false, "the bucket map"));
+  HIP_TRY(hipMemcpy(ix->bucket_map, map.data(), mb, hipMemcpyHostToDevice));
+  return DHR_OK;
+}
+static int step_refine_lists(Build& b) {
+  dhr_index* ix = b.ix; if (!b.L.refine_lists()) return DHR_OK;
+  STEP(dev_array(ix, &ix->heavy_key, (size_t)ix->n_rows * HEAVY_KEY_STRIDE * 4, true, "the refine lists"));      // one 6 x HEAVY-byte record per row (layout: dhr_internal.h)
+  ix->heavy_val = (__half*)ix->heavy_key;
+  HIP_TRY(launch_heavy_build(ix->vals_rm, ix->k_rm, ix->c_idx, ix->idx_dtype, ix->n_rows, ix->d_dlr, ix->bucket_map, ix->n_buckets, ix->heavy_key, ix->heavy_val,
+                             ix->gated_i8 ? ix->g8_inv_cs : nullptr, ix->abs_mode ? 1 : 0, b.s));
+  return DHR_OK;
+}
+// The rules of a descriptor, each checked once, in the order in which a descriptor that breaks two of them reports the first (no device is touched)
+static int check_desc(const dhr_index_desc* d, dhr_index** out) {
+  if (!d || !out) return set_error(DHR_ERR_INVALID, "null argument");
+  if (d->ld_value < (int64_t)d->d_dlr + d->d_cls) return set_error(DHR_ERR_INVALID, "bad value pointer / ld_value");
+  const bool has_idx = d->index != nullptr && d->index_dtype != DHR_IDX_NONE;
+  if (has_idx && d->ld_index < d->d_dlr) return set_error(DHR_ERR_INVALID, "bad ld_index");
   *out = nullptr;
   if (d->n_rows <= 0 || d->n_rows >= (int64_t)0xFFFFFF00ll) return set_error(DHR_ERR_INVALID, "n_rows must be in [1, 2^32-256)");
   if (d->d_dlr < 0 || d->d_cls < 0 || d->d_dlr + d->d_cls <= 0) return set_error(DHR_ERR_INVALID, "bad d_dlr/d_cls");
-  if (!d->value || d->ld_value < d->d_dlr + d->d_cls) return set_error(DHR_ERR_INVALID, "bad value pointer / ld_value");
-  const bool has_idx = d->index != nullptr && d->index_dtype != DHR_IDX_NONE;
-  if (has_idx != (d->d_dlr > 0))
-    return set_error(DHR_ERR_INVALID, "an index array is required iff d_dlr > 0 (dense-only: index=NULL, d_dlr=0)");
+  if (!d->value) return set_error(DHR_ERR_INVALID, "bad value pointer / ld_value");
+  if (has_idx != (d->d_dlr > 0)) return set_error(DHR_ERR_INVALID, "an index array is required iff d_dlr > 0 (dense-only: index=NULL, d_dlr=0)");
   if (has_idx && (d->index_dtype < DHR_IDX_U8 || d->index_dtype > DHR_IDX_I16)) return set_error(DHR_ERR_INVALID, "bad index_dtype");
-  if (has_idx && d->ld_index < d->d_dlr) return set_error(DHR_ERR_INVALID, "bad ld_index");
-  if (d->d_dlr + d->d_cls > 8192) return set_error(DHR_ERR_UNSUPPORTED, "more than 8192 columns");
-  if (d->idx_buckets < 0 || d->idx_buckets > 2)
-    return set_error(d->idx_buckets > 2 ? DHR_ERR_UNSUPPORTED : DHR_ERR_INVALID, "idx_buckets must be 0 (default: 2), 1 (ungated bound) or 2: the bucket-split operands of more than two buckets went with the K-step tile layout (round 6)");
+  if (d->d_dlr + layout::dlr_pad_of(d->d_dlr, d->index != nullptr) + d->d_cls > 8192) return set_error(DHR_ERR_UNSUPPORTED, "more than 8192 columns");      // (the padded width)
+  if (d->idx_buckets < 0 || d->idx_buckets > 2) return set_error(d->idx_buckets > 2 ? DHR_ERR_UNSUPPORTED : DHR_ERR_INVALID, "idx_buckets must be 0 (default: 2), 1 (ungated bound) or 2: the bucket-split operands of more than two buckets went with the K-step tile layout (round 6)");
   if (d->mem_kind != DHR_MEM_HOST && d->mem_kind != DHR_MEM_DEVICE) return set_error(DHR_ERR_INVALID, "bad mem_kind");
+  return DHR_OK;
+}
+// The two image options as -1 / 0 / 1: the process option (dhr_set_option), which the environment variable beats (DHR_DENSE_I8: default gated indexes only; DHR_GATED_I8=0 keeps the fp16 gated image)
+static void resolve_options(layout::LayoutInput& in) {
+  auto resolve = [](int v, const char* env) { if (const char* e = getenv(env)) v = atoi(e); return v < 0 ? -1 : (v != 0); };
+  in.want_dense_i8 = resolve(g_opt_dense_i8, "DHR_DENSE_I8"); in.want_gated_i8 = resolve(g_opt_gated_i8, "DHR_GATED_I8");
+}
+extern "C" int dhr_index_create(const dhr_index_desc* d, dhr_index** out) try {
+  STEP(check_desc(d, out));
+  layout::LayoutInput in; resolve_options(in);
+  in.n_rows = d->n_rows; in.d_dlr = d->d_dlr; in.d_cls = d->d_cls; in.index_array = d->index != nullptr; in.idx_dtype = d->index_dtype; in.idx_buckets = d->idx_buckets;
   dhr::alloc_checkpoint();
   HIP_TRY(hipSetDevice(d->device));
-
-  // everything below is released by this guard unless the build reaches its end (early returns and exceptions alike)
-  struct Build {
-    dhr_index* ix = nullptr; void* stage = nullptr; uint32_t* d_flags = nullptr; uint32_t* d_hist = nullptr;
-    ~Build() { (void)hipFree(stage); (void)hipFree(d_flags); (void)hipFree(d_hist); if (ix) dhr_index_destroy(ix); }
-  } build;
-  dhr_index* ix = build.ix = new dhr_index();
-  ix->device = d->device;
-  ix->idx_buckets_req = d->idx_buckets;
+  Build b; b.d = d; b.L = layout::make_layout(in);
+  dhr_index* ix = b.ix = new dhr_index();
+  ix->device = d->device; ix->idx_buckets_req = d->idx_buckets; ix->row_offset = d->row_offset;
   { hipDeviceProp_t pr; HIP_TRY(hipGetDeviceProperties(&pr, d->device)); ix->n_cu = pr.multiProcessorCount; }
-  ix->n_rows = d->n_rows;
-  ix->row_offset = d->row_offset;
-  ix->d_dlr = d->d_dlr;
-  ix->d_cls = d->d_cls;
-  ix->dlr_pad = dlr_pad;
-  ix->k = d->d_dlr + d->d_cls;
-  ix->k_rm = (int)round_up(ix->k, TILE_K);
-  // ONE layout (round 6): stage images -- 2:4 sparse stages of 32 gated slices (two index buckets per slice; idx_buckets = 1: every index
-  // value in bucket 0, the ungated bound) and stages of 32 (fp16) / 64 (int8) ungated columns, an EVEN number of either kind: gated widths that
-  // are no multiple of 64 and odd ungated stage counts are rounded up with all-zero stages (the tile builder and query_prep_kernel write zeros
-  // behind d_dlr / d_cls), so that every index runs on the two 8-wave kernels.  The K-step tile layout (bucket counts above two, their own
-  // kernel) and the 12-wave kernel of odd stage counts were retired.
-  auto even_up = [](int v) { return v + (v & 1); };
-  // int8 image of the ungated columns (process-wide option / DHR_DENSE_I8; default: gated indexes only, where the gated part
-  // dominates the spread of the scores and the int8 margin costs few extra candidates -- DESIGN.md section 6b)
-  int want_i8 = g_opt_dense_i8;
-  if (const char* e = getenv("DHR_DENSE_I8")) want_i8 = atoi(e);
-  bool dense_only_trial = false;
-  if (has_idx) {
-    ix->n_buckets = d->idx_buckets == 1 ? 1 : 2;
-    ix->ts = even_up((d->d_dlr + 31) / 32);
-    ix->dense_i8 = d->d_cls > 0 && (want_i8 < 0 || want_i8 > 0);
-    ix->td = ix->dense_i8 ? 2 * ((d->d_cls + 127) / 128) : even_up((d->d_cls + 31) / 32);     // ungated columns in 32-column fp16 stages or PAIRS of 64-column int8 stages
-    ix->kt = ix->ts * TILE_K + ix->td * 32;            // operand bytes / 2 per row (fp16: logical columns, two bucket columns per gated slice)
-    // gated half as int8 on the 2:4 int8 instruction (gemm_g8.hip): default for large shards whose ungated half (if any)
-    // is the int8 image too; DHR_GATED_I8=0 / dhr_set_option(DHR_OPT_GATED_I8, 0) keeps the fp16 image
-    int want_g8 = g_opt_gated_i8;
-    if (const char* e = getenv("DHR_GATED_I8")) want_g8 = atoi(e);
-    if (want_g8 < 0) want_g8 = d->n_rows >= (2 * d->d_cls >= d->d_dlr ? GATED_I8_MIN_ROWS : GATED_I8_MIN_ROWS_NARROW) ? 1 : 0;
-    ix->gated_i8 = want_g8 != 0 && ix->n_buckets == 2 && (d->d_cls == 0 || ix->dense_i8) && d->d_dlr <= 4096;
-  } else {
-    // dense-only index: the same stage images with no gated stage (ts = 0)
-    ix->n_buckets = 1;
-    ix->ts = 0;
-    // int8 image for a dense-only index: explicitly (option = 1), or -- default, large shards -- on trial: the margin it needs is measured
-    // below (i8_row_err pass) and the fp16 image is kept where it would be too large a share of the spread of the scores
-    dense_only_trial = want_i8 < 0 && d->n_rows >= DENSE_ONLY_I8_MIN_ROWS && d->d_cls >= 128;
-    ix->dense_i8 = want_i8 > 0 || dense_only_trial;
-    ix->td = ix->dense_i8 ? 2 * ((d->d_cls + 127) / 128) : even_up((d->d_cls + 31) / 32);
-    ix->kt = ix->td * 32;
-  }
-  ix->ksteps = (ix->kt + TILE_K - 1) / TILE_K;
-  ix->idx_dtype = has_idx ? d->index_dtype : DHR_IDX_NONE;
-  ix->n_tiles = (d->n_rows + TILE_ROWS - 1) / TILE_ROWS;
-  hipStream_t s = nullptr;
-  void*& stage = build.stage;
-  uint32_t*& d_flags = build.d_flags;
-  uint32_t*& d_hist = build.d_hist;
-  int rc = DHR_OK;
-  auto fail = [&](int code) { return code; };        // (the guard above releases the handle and the scratch)
-
-  const size_t rm_bytes = (size_t)ix->n_rows * ix->k_rm * 2;
-  if (hipMalloc((void**)&ix->vals_rm, rm_bytes) != hipSuccess)
-    return fail(set_error(DHR_ERR_HIP, "hipMalloc of " + std::to_string(rm_bytes) + " bytes for the row-major corpus copy failed"));
-  ix->index_bytes = (int64_t)rm_bytes;
-  if (hipMalloc((void**)&d_flags, 16) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMalloc failed"));
-  if (hipMemsetAsync(d_flags, 0, 16, s) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMemsetAsync failed"));
-  // the index array
-  if (has_idx) {
-    const int es = idx_esize(d->index_dtype);
-    const size_t ib = (size_t)d->n_rows * d->d_dlr * es;
-    if (hipMalloc(&ix->c_idx, ib) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMalloc of the index array failed"));
-    ix->index_bytes += (int64_t)ib;
-    if (dlr_pad && hipMemsetAsync(ix->c_idx, 0, ib, s) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMemsetAsync failed"));
-    if (hipMemcpy2DAsync(ix->c_idx, (size_t)d->d_dlr * es, d_user->index, (size_t)d_user->ld_index * es, (size_t)d_user->d_dlr * es,
-                         (size_t)d->n_rows, d->mem_kind == DHR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-                         s) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "copy of the index array failed"));
-  }
-  // pass 1: row-major device copy of the values (+ norms, sign scan)
-  const int64_t block_rows = 65536;
-  if ((d->mem_kind == DHR_MEM_HOST || dlr_pad > 0) &&
-      hipMalloc(&stage, (size_t)std::min<int64_t>(block_rows, d->n_rows) * ix->k * 2) != hipSuccess)
-    return fail(set_error(DHR_ERR_HIP, "hipMalloc of the staging buffer failed"));
-  if (dlr_pad > 0 && hipMemsetAsync(stage, 0, (size_t)std::min<int64_t>(block_rows, d->n_rows) * ix->k * 2, s) != hipSuccess)
-    return fail(set_error(DHR_ERR_HIP, "hipMemsetAsync failed"));
-  if ((rc = ingest(ix, d_user, d_flags, stage, block_rows, s)) != DHR_OK) return fail(rc);
-  uint32_t flags[4] = {0, 0, 0, 0};
-  if (hipMemcpy(flags, d_flags, 16, hipMemcpyDeviceToHost) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMemcpy failed"));
-  float max_sq;
-  memcpy(&max_sq, &flags[0], 4);
-  ix->dmax = std::sqrt(max_sq) * 1.0005f + 1e-30f;
-  ix->abs_mode = flags[1] != 0;     // negative gated values: the bound needs |q|.|d| on the gated half
-  if (ix->dense_i8) {
-    float amax;
-    memcpy(&amax, &flags[2], 4);
-    float gmax;
-    memcpy(&gmax, &flags[3], 4);
-    ix->i8_scale = std::max(amax > 0.f ? amax / 127.f : 1.f, gmax / 60000.f);      // gated values must fit fp16 in units of the scale
-    // per-column steps: column j is quantised in its own step cs_j <= scale, the query side carries cs_j / scale as a weight
-    // (query_prep_kernel) -- a few large columns (outlier dimensions of encoder outputs) then do not push
-    // every other column into a handful of int8 levels
-    std::vector<uint32_t> cm((size_t)ix->d_cls, 0u);
-    {
-      DevMem cmd;
-      uint32_t*& d_cm = (uint32_t*&)cmd.p;
-      if (hipMalloc((void**)&d_cm, cm.size() * 4) != hipSuccess || hipMalloc((void**)&ix->i8_col_scale, cm.size() * 4) != hipSuccess)
-        return fail(set_error(DHR_ERR_HIP, "hipMalloc failed"));
-      if (hipMemsetAsync(d_cm, 0, cm.size() * 4, s) != hipSuccess ||
-          launch_col_absmax(ix->vals_rm, ix->k_rm, ix->n_rows, ix->d_dlr, ix->d_cls, d_cm, s) != hipSuccess ||
-          hipMemcpy(cm.data(), d_cm, cm.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(set_error(DHR_ERR_HIP, "column scan failed"));
-    }
-    std::vector<float> cs(cm.size());
-    for (size_t j = 0; j < cm.size(); ++j) {
-      float m;
-      memcpy(&m, &cm[j], 4);
-      // step of column j = scale * (its largest |value| / the largest of all)^(3/4): the exponent splits a column's dynamic range
-      // between the corpus image (finer steps for small columns) and the query weights (which then stay within ~two orders of
-      // magnitude) -- measured on anisotropic columns the margin is 1.8x smaller than with exponent 1 and 4-6x smaller than with
-      // one step for all columns; on iid columns all exponents are equal (tests/test_i8_bound.py)
-      const float ratio = m > 0.f ? std::min(m / (127.f * ix->i8_scale), 1.f) : 1.f;
-      cs[j] = ix->i8_scale * std::max(std::pow(ratio, 0.75f), 1.f / 1024.f);
-    }
-    if (hipMemcpy(ix->i8_col_scale, cs.data(), cs.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "hipMemcpy failed"));
-    if (hipMemsetAsync(d_flags, 0, 16, s) != hipSuccess ||
-        launch_i8_row_err(ix->vals_rm, ix->k_rm, ix->n_rows, ix->d_dlr, ix->d_cls, ix->i8_scale, ix->i8_col_scale, d_flags, s) != hipSuccess ||
-        hipMemcpy(flags, d_flags, 8, hipMemcpyDeviceToHost) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "int8 row-error pass failed"));
-    float e2, n2;
-    memcpy(&e2, &flags[0], 4); memcpy(&n2, &flags[1], 4);
-    ix->i8_ec = std::sqrt(e2) * 1.001f;
-    ix->i8_nc = std::sqrt(n2) * 1.001f;
-    if (dense_only_trial) {
-      // The filter margin of the int8 image is ~ ||q|| ec (+ ~60 % for the query's own rounding) while the scores of a dense-only index
-      // spread by ~ ||q|| ||d|| / sqrt(d_cls): with sqrt(d_cls) ec / ||d|| = 0.36 (the benchmark's N(0, 0.1) columns: margin 0.6 sigma) the
-      // int8 search lets ~8x the rows through the filter and is still faster (config 2: 85.1 vs 89.1 ms per step: the int8 GEMM takes half
-      // the fp16 one's time and is not held by the package power cap, the extra rescoring of 1.5 KB rows costs less than that); the
-      // candidates grow exponentially with the ratio, so anything much coarser keeps the fp16 image.
-      const float ratio = std::sqrt((float)ix->d_cls) * ix->i8_ec / std::max(ix->i8_nc, 1e-30f);
-      if (!(ratio <= 0.45f)) {
-        ix->dense_i8 = false;
-        hipFree(ix->i8_col_scale); ix->i8_col_scale = nullptr;
-        ix->i8_scale = ix->i8_ec = ix->i8_nc = 0.f;
-        ix->td = ((d->d_cls + 31) / 32 + 1) & ~1;
-        ix->kt = ix->td * 32;
-        ix->ksteps = (ix->kt + TILE_K - 1) / TILE_K;
-      }
-    }
-  }
-  // dense-only int8 index: residual image = the refine level between the filter and the exact rescoring.
-  // The int8 margin is  ||q'|| ec (corpus rounding) + ||q' - q8'|| nc (query rounding); with the residuals the first term is MEASURED per
-  // candidate from 384 bytes (four bits per value) instead of bounded, and the candidates that only the corpus half of the margin let through
-  // never reach the 1.5 KB rows of the exact rescoring.
-  {
-    const int ld = (int)round_up(ix->d_cls, 256) / 2;           // four bits per value
-    if (ix->dense_i8 && ix->d_dlr == 0 && ld <= 512 && ix->i8_ec > 0.f) {
-      const size_t rb = (size_t)ix->n_rows * ld;
-      if (hipMalloc((void**)&ix->resid8, rb) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMalloc of the residual image failed"));
-      ix->index_bytes += (int64_t)rb;
-      ix->resid_ld = ld;
-      if (launch_resid_build(ix->vals_rm, ix->k_rm, ix->n_rows, ix->d_dlr, ix->d_cls, ix->i8_col_scale, ix->resid8, ld, s) != hipSuccess)
-        return fail(set_error(DHR_ERR_HIP, "residual image launch failed"));
-      ix->resid_ec2 = std::sqrt((float)ix->d_cls) * ix->i8_scale / 28.f;       // every residual is within half of 1/14 of its column's step: scale / 28 in the weighted space
-    }
-  }
-  const size_t tile_bytes = (size_t)ix->n_tiles * ((size_t)ix->ts * (ix->gated_i8 ? S8_STAGE_A : SP_STAGE_A) + (size_t)ix->td * SP_DENSE);
-  if (hipMalloc((void**)&ix->tiles, tile_bytes) != hipSuccess)
-    return fail(set_error(DHR_ERR_HIP, "hipMalloc of " + std::to_string(tile_bytes) + " bytes for the corpus tiles failed"));
-  ix->index_bytes += (int64_t)tile_bytes;
-  if (ix->gated_i8) {
-    // steps of the gated columns: s_ref = (largest gated |value|) / 127, column j in s_ref * (its own largest / the largest)^(3/4)
-    // (the exponent splits a small column's range between a finer corpus step and a smaller query weight, as for the ungated columns)
-    float gmax;
-    memcpy(&gmax, &flags[3], 4);
-    std::vector<uint32_t> cm((size_t)ix->d_dlr, 0u);
-    {
-      DevMem cmd;
-      uint32_t*& d_cm = (uint32_t*&)cmd.p;
-      if (hipMalloc((void**)&d_cm, cm.size() * 4) != hipSuccess || hipMalloc((void**)&ix->g8_inv_cs, cm.size() * 4) != hipSuccess ||
-          hipMalloc((void**)&ix->g8_w, cm.size() * 4) != hipSuccess)
-        return fail(set_error(DHR_ERR_HIP, "hipMalloc failed"));
-      if (hipMemsetAsync(d_cm, 0, cm.size() * 4, s) != hipSuccess ||
-          launch_col_absmax(ix->vals_rm, ix->k_rm, ix->n_rows, 0, ix->d_dlr, d_cm, s) != hipSuccess ||
-          hipMemcpy(cm.data(), d_cm, cm.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(set_error(DHR_ERR_HIP, "column scan failed"));
-    }
-    ix->g8_sref = (gmax > 0.f ? gmax : 1.f) * (1.00001f / 127.f);
-    std::vector<float> inv(cm.size()), wj(cm.size());
-    for (size_t j = 0; j < cm.size(); ++j) {
-      float m;
-      memcpy(&m, &cm[j], 4);
-      const float ratio = m > 0.f ? std::min(m / gmax, 1.f) : 1.f;
-      const float f = std::max(std::pow(ratio, 0.75f), 1.f / 1024.f);      // m / (s_ref f) = 127 ratio^(1/4) / 1.00001 <= 127
-      inv[j] = 1.000001f / (ix->g8_sref * f);
-      wj[j] = f * 1.000001f;
-    }
-    if (hipMemcpy(ix->g8_inv_cs, inv.data(), inv.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ix->g8_w, wj.data(), wj.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "hipMemcpy failed"));
-    ix->g8_max_shift = 0;
-    while (ix->g8_max_shift < 7 && 255.0 * 127.0 * (double)(ix->ts * 32) * (double)(2 << ix->g8_max_shift) <= 1073741824.0) ++ix->g8_max_shift;
-    const size_t rb = (size_t)ix->n_tiles * TILE_ROWS * 4;
-    if (hipMalloc((void**)&ix->g8_rsum, rb) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMalloc failed"));
-    ix->index_bytes += (int64_t)rb;
-    if (launch_g8_row_sum(ix->vals_rm, ix->k_rm, ix->n_rows, ix->n_tiles * TILE_ROWS, ix->d_dlr, ix->abs_mode, ix->g8_inv_cs, ix->g8_rsum, s) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "g8_row_sum launch failed"));
-  }
-  // bucket maps from the value mass per (slice, index value)
-  if (has_idx && ix->n_buckets == 1) {
-    // idx_buckets = 1: every index value in bucket 0 (an all-zero map serves 8- and 16-bit index dtypes alike: bucket_of reads map[j][value & 255])
-    const size_t mb = (size_t)d->d_dlr * 256;
-    if (hipMalloc((void**)&ix->bucket_map, mb) != hipSuccess || hipMemsetAsync(ix->bucket_map, 0, mb, s) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "bucket map allocation failed"));
-  }
-  if (has_idx && ix->n_buckets > 1 && idx_esize(d->index_dtype) == 1) {
-    const size_t hb = (size_t)d->d_dlr * 256 * 4;
-    if (hipMalloc((void**)&d_hist, hb) != hipSuccess || hipMemsetAsync(d_hist, 0, hb, s) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "hipMalloc (index histogram) failed"));
-    if (launch_idx_hist((const uint8_t*)ix->c_idx, ix->vals_rm, ix->k_rm, d->n_rows, d->d_dlr, (float*)d_hist, s) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "idx_hist launch failed"));
-    std::vector<float> hist((size_t)d->d_dlr * 256);
-    if (hipMemcpy(hist.data(), d_hist, hb, hipMemcpyDeviceToHost) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "hipMemcpy failed"));
-    std::vector<uint8_t> map;
-    build_bucket_map(hist, d->d_dlr, ix->n_buckets, map);
-    if (hipMalloc((void**)&ix->bucket_map, map.size()) != hipSuccess ||
-        hipMemcpy(ix->bucket_map, map.data(), map.size(), hipMemcpyHostToDevice) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "bucket map upload failed"));
-  }
-  // pass 2: operand tiles
-  if ((rc = build_tiles(ix, s)) != DHR_OK) return fail(rc);
-  if (has_idx && d->d_dlr <= 4096) {
-    const size_t hb = (size_t)d->n_rows * HEAVY_KEY_STRIDE * 4;       // one 6 x HEAVY-byte record per row (layout: dhr_internal.h)
-    if (hipMalloc((void**)&ix->heavy_key, hb) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "hipMalloc of the refine lists failed"));
-    ix->heavy_val = (__half*)ix->heavy_key;
-    ix->index_bytes += (int64_t)hb;
-    if (launch_heavy_build(ix->vals_rm, ix->k_rm, ix->c_idx, ix->idx_dtype, d->n_rows, d->d_dlr, ix->bucket_map, ix->n_buckets,
-                           ix->heavy_key, ix->heavy_val, ix->gated_i8 ? ix->g8_inv_cs : nullptr, ix->abs_mode ? 1 : 0, s) != hipSuccess)
-      return fail(set_error(DHR_ERR_HIP, "heavy_build launch failed"));
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) return fail(set_error(DHR_ERR_HIP, "index build failed on the device"));
-  build.ix = nullptr;          // the caller's from here on
-  *out = ix;
+  apply_layout(ix, b.L);
+  STEP(step_ingest(b));
+  STEP(step_scan_results(b));
+  STEP(step_ungated_i8(b));
+  STEP(step_residual(b));
+  STEP(step_alloc_tiles(b));
+  STEP(step_gated_i8(b));
+  STEP(step_bucket_maps(b));
+  STEP(build_tiles(ix, b.s));        // pass 2: operand tiles (needs the bucket map and abs_mode)
+  STEP(step_refine_lists(b));
+  if (hipStreamSynchronize(b.s) != hipSuccess) return set_error(DHR_ERR_HIP, "index build failed on the device");
+  b.ix = nullptr; *out = ix;          // the caller's from here on
   return DHR_OK;
 } DHR_CATCH_STATUS
 

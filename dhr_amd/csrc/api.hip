@@ -1,5 +1,6 @@
 // Search entry points of the C ABI (include/dhr_hip.h): dhr_search, dhr_search_rerank, the staged calls of the sharded search, dhr_score_rows;
-// densify, PQ training / encoding, debug hooks, shard reduce.  The handle and its build: index_build.hip; the controller (search_core): search_core.hip;
+// densify, PQ training / encoding / decoding, debug hooks, shard reduce.  Host arrays are staged with the vocabulary of host_stage.h; every HIP call
+// whose failure answers DHR_ERR_HIP goes through HIP_TRY.  The handle and its build: index_build.hip; the controller (search_core): search_core.hip;
 // the sharded control flow: sharded.hip; error record, exception classifier: abi.cpp.
 #include "host_stage.h"
 
@@ -10,22 +11,14 @@ dhr_search_stats fresh_stats(const dhr_index* ix, int Q, int k) {
   st.n_rows = ix->n_rows; st.n_queries = Q; st.k = k;
   return st;
 }
-// The sorted top-k keys of the workspace -> the caller's score / row arrays (host arrays are staged through the workspace; the copies are enqueued)
+// The sorted top-k keys of the workspace -> the caller's score / row arrays (host arrays are staged through the workspace's grow-only buffer;
+// the copies are enqueued)
 int emit_results(dhr_index* ix, Workspace& w, int Q, int k, float* out_scores, int64_t* out_rows, int out_mem_kind, hipStream_t s) {
-  float* d_scores = out_scores;
-  int64_t* d_rows = out_rows;
   if (out_mem_kind == DHR_MEM_HOST) {
     const int rc = grow(w.out_stage, w.out_stage_bytes, (size_t)Q * k * 12, w.bytes);
     if (rc != DHR_OK) return rc;
-    d_rows = (int64_t*)w.out_stage;
-    d_scores = (float*)((char*)w.out_stage + (size_t)Q * k * 8);
   }
-  HIP_TRY(launch_emit(w.topk_keys, w.kp, Q, k, ix->row_offset, d_scores, d_rows, s));
-  if (out_mem_kind == DHR_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(out_rows, d_rows, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_scores, d_scores, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-  }
-  return DHR_OK;
+  return emit_topk(w.topk_keys, w.kp, Q, k, ix->row_offset, out_scores, out_rows, out_mem_kind, w.out_stage, s);
 }
 // The timers of one call (its stream must be idle) added to the running stats: a call that opens a search starts them from zero (fresh_stats),
 // one that continues a staged search from the handle's
@@ -33,6 +26,30 @@ void collect_timers(Timer& tm, dhr_search_stats& st) {
   double ms[5] = {0, 0, 0, 0, 0};
   tm.collect(ms);
   st.gemm_ms += ms[T_GEMM]; st.refine_ms += ms[T_REFINE]; st.rescore_ms += ms[T_RESCORE]; st.select_ms += ms[T_SELECT]; st.prep_ms += ms[T_PREP];
+}
+// The frame of a whole search that the caller waits for (dhr_search, dhr_search_rerank): body(timer, stats) enqueues the search and the
+// delivery of its result on s; the frame times it between two events, waits for the stream, collects the timers into the handle's stats -- and
+// drains the handle's streams where the body fails or throws.
+template <typename Body>
+int timed_search(dhr_index* ix, int Q, int k, hipStream_t s, Body&& body) {
+  Events evs;
+  hipEvent_t ev0, ev1;
+  HIP_TRY(evs.add(&ev0)); HIP_TRY(evs.add(&ev1));
+  HIP_TRY(hipEventRecord(ev0, s));
+  Timer tm{ix->profile != 0, s, {}, {}};
+  dhr_search_stats st = fresh_stats(ix, Q, k);
+  Drain drain{ix, s};
+  const int rc = body(tm, st);
+  if (rc != DHR_OK) return rc;
+  HIP_TRY(hipEventRecord(ev1, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  float total = 0.f;
+  hipEventElapsedTime(&total, ev0, ev1);
+  st.total_ms = total;
+  collect_timers(tm, st);
+  ix->stats = st;
+  drain.armed = false;
+  return DHR_OK;
 }
 // Controller without read-backs: the candidate counters live on the device (zero otherwise) and run on over the calls of a staged search.
 // Reads them (synchronises s) and adds what they gained since the last fold of this staged search.
@@ -109,25 +126,10 @@ extern "C" int dhr_search(dhr_index* ix, const dhr_query_batch* qb, int32_t k, f
   hipStream_t s = (hipStream_t)stream;
   const int Q = qb->n_queries;
   staged_set(ix, StagedState::None);          // a plain search overwrites the workspace of any staged search left open on this handle
-  Events evs;
-  hipEvent_t ev0, ev1;
-  HIP_TRY(evs.add(&ev0)); HIP_TRY(evs.add(&ev1));
-  HIP_TRY(hipEventRecord(ev0, s));
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st = fresh_stats(ix, Q, k);
-  Workspace& w = ix->ws;
-  Drain drain{ix, s};
-  if ((rc = search_core(ix, w, qb, k, 0, tm, st, s)) != DHR_OK) return rc;
-  if ((rc = emit_results(ix, w, Q, k, out_scores, out_rows, out_mem_kind, s)) != DHR_OK) return rc;
-  HIP_TRY(hipEventRecord(ev1, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  float total = 0.f;
-  hipEventElapsedTime(&total, ev0, ev1);
-  st.total_ms = total;
-  collect_timers(tm, st);
-  ix->stats = st;
-  drain.armed = false;
-  return DHR_OK;
+  return timed_search(ix, Q, k, s, [&](Timer& tm, dhr_search_stats& st) {
+    const int rc = search_core(ix, ix->ws, qb, k, 0, tm, st, s);
+    return rc != DHR_OK ? rc : emit_results(ix, ix->ws, Q, k, out_scores, out_rows, out_mem_kind, s);
+  });
 } DHR_CATCH_STATUS
 
 // Two-stage approximate GIP on the device (gip_retrieval.py:128-156): stage 1 is an ordinary search of the
@@ -147,52 +149,36 @@ extern "C" int dhr_search_rerank(dhr_index* ix, const dhr_query_batch* qb1, cons
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t s = (hipStream_t)stream;
   const int Q = qb1->n_queries;
-  Events evs;
-  hipEvent_t ev0, ev1;
-  HIP_TRY(evs.add(&ev0)); HIP_TRY(evs.add(&ev1));
-  HIP_TRY(hipEventRecord(ev0, s));
-  Timer tm{ix->profile != 0, s, {}, {}};
-  dhr_search_stats st = fresh_stats(ix, Q, k);
-  Workspace& w = ix->ws;
-  Drain drain{ix, s};
-  // ---- stage 1
-  if ((rc = search_core(ix, w, qb1, k1, 0, tm, st, s)) != DHR_OK) return rc;
-  // ---- stage 2: exact scores of the stage-1 rows under the full batch, top-k of those
-  DevMem rows_mem;          // (releases the scratch on every way out)
-  uint32_t*& d_rows32 = (uint32_t*&)rows_mem.p;
-  HIP_TRY(hipMalloc((void**)&d_rows32, (size_t)Q * k1 * 4));
-  if (launch_keys_to_rows(w.topk_keys, w.kp, Q, k1, d_rows32, s) != hipSuccess) return set_error(DHR_ERR_HIP, "keys_to_rows launch failed");
-  if (w.keys_ld < k1) return set_error(DHR_ERR_INTERNAL, "key buffer smaller than k1");
-  const bool gate2 = ix->d_dlr > 0 && qb2->index != nullptr && qb2->index_dtype != DHR_IDX_NONE;
-  tm.begin(T_PREP);
-  if ((rc = prep_queries(ix, w, qb2, s)) != DHR_OK) return rc;
-  if (hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s) != hipSuccess) return set_error(DHR_ERR_HIP, "memset failed");
-  tm.end();
-  RescoreArgs r = base_rescore_args(ix, w, Q, gate2);
-  r.rows32 = d_rows32; r.ld_rows = k1; r.count_all = (uint32_t)k1; r.max_count = (uint32_t)k1;
-  r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
-  tm.begin(T_RESCORE);
-  if (launch_rescore(r, s) != hipSuccess) return set_error(DHR_ERR_HIP, "rescore launch failed");
-  tm.end();
-  st.candidates_exact += (int64_t)Q * k1;
-  SelectArgs sel{};
-  sel.topk_keys = w.topk_keys; sel.in_keys = w.rs_keys; sel.ld_keys = w.keys_ld; sel.cap = (uint32_t)w.cap;
-  sel.cnt = nullptr; sel.count_all = (uint32_t)k1;
-  sel.k = k; sel.kp = w.kp; sel.sort_n = select_sort_n(w.kp);
-  sel.kps = 64; while (sel.kps < k) sel.kps <<= 1;
-  sel.margin = w.margin; sel.tau = w.tau; sel.thr = w.thr; sel.n_queries = Q;
-  tm.begin(T_SELECT);
-  if (launch_select(sel, s) != hipSuccess) return set_error(DHR_ERR_HIP, "select launch failed");
-  tm.end();
-  if ((rc = emit_results(ix, w, Q, k, out_scores, out_rows, out_mem_kind, s)) != DHR_OK) return rc;
-  if (hipEventRecord(ev1, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "two-stage search failed on the device");
-  float total = 0.f;
-  hipEventElapsedTime(&total, ev0, ev1);
-  st.total_ms = total;
-  collect_timers(tm, st);
-  ix->stats = st;
-  drain.armed = false;
-  return DHR_OK;
+  return timed_search(ix, Q, k, s, [&](Timer& tm, dhr_search_stats& st) {
+    Workspace& w = ix->ws;
+    // ---- stage 1
+    int rc = search_core(ix, w, qb1, k1, 0, tm, st, s);
+    if (rc != DHR_OK) return rc;
+    // ---- stage 2: exact scores of the stage-1 rows under the full batch, top-k of those
+    DevMem rows_mem;
+    HIP_TRY(dev_alloc(rows_mem, (int64_t)Q * k1 * 4));
+    uint32_t* d_rows32 = (uint32_t*)rows_mem.p;
+    HIP_TRY(launch_keys_to_rows(w.topk_keys, w.kp, Q, k1, d_rows32, s));
+    if (w.keys_ld < k1) return set_error(DHR_ERR_INTERNAL, "key buffer smaller than k1");
+    const bool gate2 = ix->d_dlr > 0 && qb2->index != nullptr && qb2->index_dtype != DHR_IDX_NONE;
+    tm.begin(T_PREP);
+    if ((rc = prep_queries(ix, w, qb2, s)) != DHR_OK) return rc;
+    HIP_TRY(hipMemsetAsync(w.topk_keys, 0, (size_t)w.q_pad * w.kp * 8, s));
+    tm.end();
+    RescoreArgs r = base_rescore_args(ix, w, Q, gate2);
+    r.rows32 = d_rows32; r.ld_rows = k1; r.count_all = (uint32_t)k1; r.max_count = (uint32_t)k1;
+    r.out_keys = w.rs_keys; r.ld_keys = w.keys_ld;
+    tm.begin(T_RESCORE);
+    HIP_TRY(launch_rescore(r, s));
+    tm.end();
+    st.candidates_exact += (int64_t)Q * k1;
+    SelectArgs sel = rescored_select_args(w, Q, k);
+    sel.count_all = (uint32_t)k1;            // every query has exactly its k1 keys (no count array)
+    tm.begin(T_SELECT);
+    HIP_TRY(launch_select(sel, s));
+    tm.end();
+    return emit_results(ix, w, Q, k, out_scores, out_rows, out_mem_kind, s);
+  });
 } DHR_CATCH_STATUS
 
 // ---- staged search for the row-sharded path (dhr_amd/dist.py): the shards agree on ONE threshold per
@@ -225,25 +211,24 @@ extern "C" int32_t dhr_search_mid_ranks(const dhr_index* ix, int32_t k, int32_t*
 // The first slice of the main pass with the thresholds of the first agreement; leaves the shard's r_local best scores seen so far in
 // out_scores_dev [Q, r_local] (r_local: dhr_search_mid_ranks, or what the shards agreed on).  dhr_search_finish then takes the thresholds of the
 // second agreement.
-static int search_mid_impl(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream) {
+static int search_mid_impl(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream, bool sync) {
   if (!ix || ix->pend.state == StagedState::None) return set_error(DHR_ERR_INVALID, "dhr_search_mid without a matching dhr_search_begin");
-  if (ix->pend.state == StagedState::Complete) return DHR_OK;                   // the shard was not sampled: its search is complete already
+  if (ix->pend.state == StagedState::Complete) {                                // the shard was not sampled: its search is complete already
+    if (sync) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));              // (the call still answers for the caller's stream)
+    return DHR_OK;
+  }
   if (ix->pend.state == StagedState::AfterMid) return set_error(DHR_ERR_INVALID, "dhr_search_mid called twice");
   if (!tau_hat_dev || !out_scores_dev) return set_error(DHR_ERR_INVALID, "null pointer");
   if (dhr_search_mid_ranks(ix, ix->pend.k, nullptr, nullptr) <= 0) return set_error(DHR_ERR_INVALID, "this index has no mid step (dhr_search_mid_ranks returned 0)");
   if (r_local <= 0 || r_local > ix->pend.k) return set_error(DHR_ERR_INVALID, "r_local must be in [1, k]");
-  return staged_step(ix, nullptr, ix->pend.k, Stage::Mid, tau_hat_dev, stream, false, false,
+  return staged_step(ix, nullptr, ix->pend.k, Stage::Mid, tau_hat_dev, stream, sync, false,
                      [&](hipStream_t s) { return emit_best_scores(ix, ix->pend.Q, r_local, out_scores_dev, s); });
 }
 extern "C" int dhr_search_mid(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream) try {
-  return staged_call(ix, [&] {
-    int rc = search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream);
-    if (rc == DHR_OK && ix) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return rc;
-  });
+  return staged_call(ix, [&] { return search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream, true); });
 } DHR_CATCH_STATUS
 extern "C" int dhr_internal_search_mid_async(dhr_index* ix, const float* tau_hat_dev, int32_t r_local, float* out_scores_dev, void* stream) try {
-  return staged_call(ix, [&] { return search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream); });
+  return staged_call(ix, [&] { return search_mid_impl(ix, tau_hat_dev, r_local, out_scores_dev, stream, false); });
 } DHR_CATCH_STATUS
 
 // ---- first agreement in TWO rounds (round 5).  The shards of a sharded search each ran their whole sampled run from nothing, chasing their
@@ -350,26 +335,20 @@ extern "C" int dhr_score_rows(dhr_index* ix, const dhr_query_batch* qb, int32_t 
   if ((rc = ensure_ws(ix, w, Q, 1, 0, 1, true, true)) != DHR_OK) return rc;
   if ((rc = prep_queries(ix, w, qb, s)) != DHR_OK) return rc;
   const size_t n = (size_t)Q * m;
-  DevMem tmp_mem;
-  void*& tmp = tmp_mem.p;                  // [rows64 (host input only)] [rows32] [scores]
-  HIP_TRY(hipMalloc(&tmp, n * 16));
-  int64_t* d_rows64 = (int64_t*)tmp;
-  uint32_t* d_rows32 = (uint32_t*)((char*)tmp + n * 8);
-  float* d_sc = (float*)((char*)tmp + n * 12);
-  const int64_t* src_rows = rows;
-  if (mem_kind == DHR_MEM_HOST) {
-    if (hipMemcpyAsync(d_rows64, rows, n * 8, hipMemcpyHostToDevice, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
-    src_rows = d_rows64;
-  }
-  if (launch_rows_to_local(src_rows, (int64_t)n, ix->row_offset, ix->n_rows, d_rows32, s) != hipSuccess)
-    return set_error(DHR_ERR_HIP, "rows_to_local launch failed");
+  DevMem m_rows64, m_rows32, m_scores;
+  const int64_t* d_rows64;
+  float* d_scores;
+  HIP_TRY(operand_in(m_rows64, mem_kind, rows, n * 8, s, d_rows64));
+  HIP_TRY(dev_alloc(m_rows32, (int64_t)n * 4));
+  HIP_TRY(operand_out(m_scores, mem_kind, out_scores, n * 4, d_scores));
+  uint32_t* d_rows32 = (uint32_t*)m_rows32.p;
+  HIP_TRY(launch_rows_to_local(d_rows64, (int64_t)n, ix->row_offset, ix->n_rows, d_rows32, s));
   RescoreArgs r = base_rescore_args(ix, w, Q, gate);
   r.rows32 = d_rows32; r.ld_rows = m; r.count_all = (uint32_t)m; r.max_count = (uint32_t)m;
-  r.out_scores = (mem_kind == DHR_MEM_HOST) ? d_sc : out_scores; r.ld_scores = m;
-  if (launch_rescore(r, s) != hipSuccess) return set_error(DHR_ERR_HIP, "rescore launch failed");
-  if (mem_kind == DHR_MEM_HOST && hipMemcpyAsync(out_scores, d_sc, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-    return set_error(DHR_ERR_HIP, "D2H failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "score_rows failed on the device");
+  r.out_scores = d_scores; r.ld_scores = m;
+  HIP_TRY(launch_rescore(r, s));
+  HIP_TRY(operand_back(m_scores, out_scores, n * 4, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
 } DHR_CATCH_STATUS
 
@@ -399,20 +378,17 @@ extern "C" int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical
   // host arrays: stage blocks of rows through the device (complete on return)
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * ies)));
   DevMem m_in, m_val, m_idx;
-  void *&d_in = m_in.p, *&d_val = m_val.p, *&d_idx = m_idx.p;
-  if (dev_alloc(m_in, block * vocab * ies) != hipSuccess || dev_alloc(m_val, block * dims * oes) != hipSuccess ||
-      dev_alloc(m_idx, block * dims * xes) != hipSuccess)
-    return set_error(DHR_ERR_HIP, "hipMalloc failed");
+  HIP_TRY(dev_alloc(m_in, block * vocab * ies));
+  HIP_TRY(dev_alloc(m_val, block * dims * oes));
+  HIP_TRY(dev_alloc(m_idx, block * dims * xes));
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
-    if (copy_in(d_in, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
-    if (launch_densify(d_in, value_dtype == DHR_VAL_F32, vocab, rows, remove_dims, dims, n_groups, d_val, out_value_dtype == DHR_VAL_F32, dims, d_idx,
-                       index_dtype == DHR_IDX_I16, dims, s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "densify launch failed");
-    if (stage_out((char*)out_value + lo * ld_value * oes, ld_value, d_val, rows, dims, oes, s) != hipSuccess ||
-        stage_out((char*)out_index + lo * ld_index * xes, ld_index, d_idx, rows, dims, xes, s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "D2H failed");
-    if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "densify failed on the device");
+    HIP_TRY(copy_in(m_in.p, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s));
+    HIP_TRY(launch_densify(m_in.p, value_dtype == DHR_VAL_F32, vocab, rows, remove_dims, dims, n_groups, m_val.p, out_value_dtype == DHR_VAL_F32, dims,
+                           m_idx.p, index_dtype == DHR_IDX_I16, dims, s));
+    HIP_TRY(stage_out((char*)out_value + lo * ld_value * oes, ld_value, m_val.p, rows, dims, oes, s));
+    HIP_TRY(stage_out((char*)out_index + lo * ld_index * xes, ld_index, m_idx.p, rows, dims, xes, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -426,23 +402,6 @@ int pq_check(const void* a, const void* b, int64_t n, int d, int M, int64_t ld, 
   if (d / M > 64) return set_error(DHR_ERR_UNSUPPORTED, "sub-vectors wider than 64 columns are not supported");
   return DHR_OK;
 }
-// host arrays are staged whole (PQ inputs are at most the corpus, which has to fit the device anyway)
-struct Staged {
-  void* dev = nullptr; bool owned = false;
-  int in(const void* p, size_t bytes, int mem_kind, hipStream_t s) {
-    if (mem_kind == DHR_MEM_DEVICE) { dev = const_cast<void*>(p); return DHR_OK; }
-    if (hipMalloc(&dev, bytes ? bytes : 16) != hipSuccess) return set_error(DHR_ERR_HIP, "hipMalloc failed");
-    owned = true;
-    if (p && hipMemcpyAsync(dev, p, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
-    return DHR_OK;
-  }
-  int out(void* p, size_t bytes, hipStream_t s) {
-    if (!owned) return DHR_OK;
-    if (hipMemcpyAsync(p, dev, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return set_error(DHR_ERR_HIP, "D2H failed");
-    return DHR_OK;
-  }
-  ~Staged() { if (owned) hipFree(dev); }
-};
 }  // namespace
 
 extern "C" int dhr_pq_train(int32_t device, int32_t mem_kind, const void* values, int64_t ld, int64_t n, int32_t d, int32_t M, int32_t iters,
@@ -459,48 +418,41 @@ extern "C" int dhr_pq_train_nbits(int32_t device, int32_t mem_kind, const void* 
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int dsub = d / M;
-  // training rows: every `stride`-th row (host arrays: only those rows are staged)
+  // training rows: every `stride`-th row (host arrays: only those rows are staged, packed; the codebooks are staged whole, as every PQ operand:
+  // they are at most the corpus, which has to fit the device anyway)
+  const bool host = mem_kind == DHR_MEM_HOST;
   const int64_t stride = std::max<int64_t>(1, n / max_points);
   const int64_t np = (n + stride - 1) / stride;
-  Staged v, cb;
-  int64_t v_ld = ld, v_stride = stride;
-  if (mem_kind == DHR_MEM_HOST) {
-    if (hipMalloc(&v.dev, (size_t)np * d * 2) != hipSuccess) return set_error(DHR_ERR_HIP, "hipMalloc failed");
-    v.owned = true;
-    HIP_TRY(hipMemcpy2DAsync(v.dev, (size_t)d * 2, values, (size_t)ld * stride * 2, (size_t)d * 2, (size_t)np, hipMemcpyHostToDevice, s));
-    v_ld = d; v_stride = 1;
-  } else {
-    v.dev = const_cast<void*>(values);
-  }
-  const size_t cb_bytes = (size_t)M * ksub * dsub * 4;
-  if ((rc = cb.in(nullptr, cb_bytes, mem_kind == DHR_MEM_HOST ? DHR_MEM_HOST : DHR_MEM_DEVICE, s)) != DHR_OK) return rc;
-  if (mem_kind == DHR_MEM_DEVICE) cb.dev = codebooks;
-  float* d_cb = (float*)cb.dev;
-  DevMem m_sums, m_counts, m_err;
-  float*& sums = (float*&)m_sums.p; uint32_t*& counts = (uint32_t*&)m_counts.p; float*& err = (float*&)m_err.p;
-  if (hipMalloc((void**)&sums, cb_bytes) != hipSuccess || hipMalloc((void**)&counts, (size_t)M * ksub * 4) != hipSuccess ||
-      hipMalloc((void**)&err, (size_t)M * 4) != hipSuccess)
-    return set_error(DHR_ERR_HIP, "hipMalloc failed");
-  if (launch_pq_init((const __half*)v.dev, v_ld, np, v_stride, dsub, M, d_cb, ksub, s) != hipSuccess) return set_error(DHR_ERR_HIP, "pq_init launch failed");
+  DevMem m_v, m_cb, m_sums, m_counts, m_err;
+  if (host) HIP_TRY(stage_in(m_v, values, ld * stride, np, d, 2, s));
+  const __half* d_v = (const __half*)(host ? m_v.p : values);
+  const int64_t v_ld = host ? d : ld, v_stride = host ? 1 : stride;
+  const size_t cb_bytes = (size_t)M * ksub * dsub * 4, cnt_bytes = (size_t)M * ksub * 4;
+  float* d_cb;
+  HIP_TRY(operand_out(m_cb, mem_kind, codebooks, cb_bytes, d_cb));
+  HIP_TRY(dev_alloc(m_sums, (int64_t)cb_bytes));
+  HIP_TRY(dev_alloc(m_counts, (int64_t)cnt_bytes));
+  HIP_TRY(dev_alloc(m_err, (int64_t)M * 4));
+  float* sums = (float*)m_sums.p; uint32_t* counts = (uint32_t*)m_counts.p; float* err = (float*)m_err.p;
+  HIP_TRY(launch_pq_init(d_v, v_ld, np, v_stride, dsub, M, d_cb, ksub, s));
   for (int it = 0; it <= iters; ++it) {
-    if (hipMemsetAsync(sums, 0, cb_bytes, s) != hipSuccess || hipMemsetAsync(counts, 0, (size_t)M * ksub * 4, s) != hipSuccess ||
-        hipMemsetAsync(err, 0, (size_t)M * 4, s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "memset failed");
-    if (launch_pq_assign((const __half*)v.dev, v_ld, np, v_stride, dsub, M, d_cb, nullptr, 0, sums, counts, err, ksub, s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "pq_assign launch failed");
+    HIP_TRY(hipMemsetAsync(sums, 0, cb_bytes, s));
+    HIP_TRY(hipMemsetAsync(counts, 0, cnt_bytes, s));
+    HIP_TRY(hipMemsetAsync(err, 0, (size_t)M * 4, s));
+    HIP_TRY(launch_pq_assign(d_v, v_ld, np, v_stride, dsub, M, d_cb, nullptr, 0, sums, counts, err, ksub, s));
     if (it == iters) break;                               // the last pass only measures the error
-    if (launch_pq_update(d_cb, sums, counts, dsub, M, ksub, s) != hipSuccess) return set_error(DHR_ERR_HIP, "pq_update launch failed");
+    HIP_TRY(launch_pq_update(d_cb, sums, counts, dsub, M, ksub, s));
   }
   if (out_error) {
     std::vector<float> e(M);
-    if (hipMemcpyAsync(e.data(), err, (size_t)M * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "D2H failed");
+    HIP_TRY(stage_out(e.data(), err, (size_t)M * 4, s));
+    HIP_TRY(hipStreamSynchronize(s));
     double t = 0;
     for (float x : e) t += x;
     *out_error = t / (double)np;
   }
-  if ((rc = cb.out(codebooks, cb_bytes, s)) != DHR_OK) return rc;
-  if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "PQ training failed on the device");
+  HIP_TRY(operand_back(m_cb, codebooks, cb_bytes, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
 } DHR_CATCH_STATUS
 
@@ -519,26 +471,25 @@ extern "C" int dhr_pq_encode_nbits(int32_t device, int32_t mem_kind, const void*
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int dsub = d / M;
-  Staged cb, cd;
-  if ((rc = cb.in(codebooks, (size_t)M * ksub * dsub * 4, mem_kind, s)) != DHR_OK) return rc;
-  if ((rc = cd.in(nullptr, (size_t)n * M, mem_kind == DHR_MEM_HOST ? DHR_MEM_HOST : DHR_MEM_DEVICE, s)) != DHR_OK) return rc;
-  if (mem_kind == DHR_MEM_DEVICE) cd.dev = codes;
+  DevMem m_cb, m_cd;
+  const float* d_cb;
+  uint8_t* d_cd;
+  HIP_TRY(operand_in(m_cb, mem_kind, codebooks, (size_t)M * ksub * dsub * 4, s, d_cb));
+  HIP_TRY(operand_out(m_cd, mem_kind, codes, (size_t)n * M, d_cd));
   if (mem_kind == DHR_MEM_DEVICE) {
-    HIP_TRY(launch_pq_assign((const __half*)values, ld, n, 1, dsub, M, (const float*)cb.dev, (uint8_t*)cd.dev, M, nullptr, nullptr, nullptr, ksub, s));
+    HIP_TRY(launch_pq_assign((const __half*)values, ld, n, 1, dsub, M, d_cb, d_cd, M, nullptr, nullptr, nullptr, ksub, s));
   } else {
     const int64_t block = 1 << 18;                          // rows per staged block
-    DevMem stage_mem;
-    void*& stage = stage_mem.p;
-    if (hipMalloc(&stage, (size_t)std::min<int64_t>(block, n) * d * 2) != hipSuccess) return set_error(DHR_ERR_HIP, "hipMalloc failed");
+    DevMem stage;
+    HIP_TRY(dev_alloc(stage, std::min<int64_t>(block, n) * d * 2));
     for (int64_t lo = 0; lo < n; lo += block) {
       const int64_t rows = std::min(block, n - lo);
-      if (hipMemcpy2DAsync(stage, (size_t)d * 2, (const char*)values + lo * ld * 2, (size_t)ld * 2, (size_t)d * 2, (size_t)rows, hipMemcpyHostToDevice, s) != hipSuccess ||
-          launch_pq_assign((const __half*)stage, d, rows, 1, dsub, M, (const float*)cb.dev, (uint8_t*)cd.dev + lo * M, M, nullptr, nullptr, nullptr, ksub, s) != hipSuccess ||
-          hipStreamSynchronize(s) != hipSuccess)
-        return set_error(DHR_ERR_HIP, "PQ encoding failed on the device");
+      HIP_TRY(copy_in(stage.p, (const char*)values + lo * ld * 2, ld, rows, d, 2, s));
+      HIP_TRY(launch_pq_assign((const __half*)stage.p, d, rows, 1, dsub, M, d_cb, d_cd + lo * M, M, nullptr, nullptr, nullptr, ksub, s));
+      HIP_TRY(hipStreamSynchronize(s));
     }
   }
-  if ((rc = cd.out(codes, (size_t)n * M, s)) != DHR_OK) return rc;
+  HIP_TRY(operand_back(m_cd, codes, (size_t)n * M, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -558,19 +509,15 @@ extern "C" int dhr_pq_decode_nbits(int32_t device, int32_t mem_kind, const uint8
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int dsub = d / M;
-  Staged cb, cd, ov;
-  if ((rc = cb.in(codebooks, (size_t)M * ksub * dsub * 4, mem_kind, s)) != DHR_OK) return rc;
-  if ((rc = cd.in(codes, (size_t)n * M, mem_kind, s)) != DHR_OK) return rc;
-  int64_t ld_dev = ld_out;
-  if (mem_kind == DHR_MEM_HOST) {
-    if ((rc = ov.in(nullptr, (size_t)n * d * 2, DHR_MEM_HOST, s)) != DHR_OK) return rc;
-    ld_dev = d;
-  } else {
-    ov.dev = out_values;
-  }
-  HIP_TRY(launch_pq_decode((const uint8_t*)cd.dev, M, n, M, dsub, (const float*)cb.dev, (__half*)ov.dev, ld_dev, ksub, s));
-  if (mem_kind == DHR_MEM_HOST)
-    HIP_TRY(hipMemcpy2DAsync(out_values, (size_t)ld_out * 2, ov.dev, (size_t)d * 2, (size_t)d * 2, (size_t)n, hipMemcpyDeviceToHost, s));
+  const bool host = mem_kind == DHR_MEM_HOST;
+  DevMem m_cb, m_cd, m_ov;
+  const float* d_cb;
+  const uint8_t* d_cd;
+  HIP_TRY(operand_in(m_cb, mem_kind, codebooks, (size_t)M * ksub * dsub * 4, s, d_cb));
+  HIP_TRY(operand_in(m_cd, mem_kind, codes, (size_t)n * M, s, d_cd));
+  if (host) HIP_TRY(dev_alloc(m_ov, n * d * 2));             // decoded rows, packed
+  HIP_TRY(launch_pq_decode(d_cd, M, n, M, dsub, d_cb, (__half*)(host ? m_ov.p : out_values), host ? d : ld_out, ksub, s));
+  if (host) HIP_TRY(stage_out(out_values, ld_out, m_ov.p, n, d, 2, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -585,10 +532,9 @@ extern "C" int dhr_debug_bound_scores(dhr_index* ix, const dhr_query_batch* qb, 
   Workspace& w = ix->ws;
   if ((rc = ensure_ws(ix, w, qb->n_queries, 1, 0)) != DHR_OK) return rc;
   if ((rc = prep_queries(ix, w, qb, s)) != DHR_OK) return rc;
-  GemmArgs g{};
-  g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant; g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum; g.seq_lo = row_lo / TILE_ROWS;
-  g.seq_hi = (row_hi + TILE_ROWS - 1) / TILE_ROWS; g.map_mode = 0; g.period = 1; g.head = 0; g.n_tiles = ix->n_tiles; g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows;
-  g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt; g.cap = (uint32_t)w.cap; g.n_queries = qb->n_queries;
+  GemmArgs g = base_gemm_args(ix, w, qb->n_queries);
+  g.seq_lo = row_lo / TILE_ROWS; g.seq_hi = (row_hi + TILE_ROWS - 1) / TILE_ROWS; g.map_mode = 0; g.period = 1; g.head = 0;      // the tiles of the rows, in corpus order
+  g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
   g.dump = out_dev; g.dump_ld = row_hi - row_lo; g.dump_row0 = row_lo;
   HIP_TRY(launch_gemm_filter(g, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -637,10 +583,9 @@ extern "C" int dhr_debug_gemm_time(dhr_index* ix, const dhr_query_batch* qb, int
   }
   const bool opened = open;
   HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)w.q_pad * 4, s));
-  GemmArgs g{};
-  g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant; g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum; g.seq_lo = 0; g.seq_hi = ix->n_tiles; g.map_mode = 0;
-  g.period = 1; g.head = 0; g.n_tiles = ix->n_tiles; g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows;
-  g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt; g.cap = (uint32_t)w.cap; g.n_queries = qb->n_queries;
+  GemmArgs g = base_gemm_args(ix, w, qb->n_queries);
+  g.seq_lo = 0; g.seq_hi = ix->n_tiles; g.map_mode = 0; g.period = 1; g.head = 0;      // the whole shard, in corpus order
+  g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
   HIP_TRY(launch_gemm_filter(g, s));                      // warm-up
   Events evs;
   hipEvent_t e0, e1;
@@ -686,54 +631,50 @@ extern "C" int dhr_merge_topk_lists(int32_t device, int32_t n_queries, int32_t n
   return DHR_OK;
 } DHR_CATCH_STATUS
 
-extern "C" int dhr_merge_topk_lists_host(int32_t n_queries, int32_t n_lists, int32_t list_len, const float* in_scores,
-                                         const int64_t* in_rows, int32_t k_out, float* out_scores, int64_t* out_rows) try {
-  if (n_queries <= 0 || n_lists <= 0 || list_len <= 0 || k_out <= 0 || !in_scores || !out_scores || (in_rows && !out_rows))
-    return set_error(DHR_ERR_INVALID, "bad argument");
+// The two host merges: per query, the candidates at source positions src(q, 0 .. n_per_query) of the input arrays, those with a row >= 0 where
+// there are rows, best first -- score key descending, then row ascending, then (by_position) source position -- and the first k_out of them, padded
+// with (-inf, -1).  (+0 and -0 share a score key: without by_position two such entries of one row tie, and which comes first is the sort's matter.)
+namespace {
+template <typename Src>
+void merge_topk_on_host(int n_queries, int64_t n_per_query, Src&& src, bool by_position, const float* in_scores, const int64_t* in_rows, int k_out,
+                        float* out_scores, int64_t* out_rows) {
   std::vector<int64_t> order;
   for (int q = 0; q < n_queries; ++q) {
     order.clear();
-    for (int l = 0; l < n_lists; ++l)
-      for (int j = 0; j < list_len; ++j) {
-        const int64_t src = ((int64_t)l * n_queries + q) * list_len + j;
-        if (!in_rows || in_rows[src] >= 0) order.push_back(src);
-      }
+    for (int64_t j = 0; j < n_per_query; ++j) {
+      const int64_t at = src(q, j);
+      if (!in_rows || in_rows[at] >= 0) order.push_back(at);
+    }
     const int take = std::min<int>(k_out, (int)order.size());
     std::partial_sort(order.begin(), order.begin() + take, order.end(), [&](int64_t a, int64_t b) {
       const uint32_t ka = f32_ordered(in_scores[a]), kb = f32_ordered(in_scores[b]);
       if (ka != kb) return ka > kb;
       if (in_rows && in_rows[a] != in_rows[b]) return in_rows[a] < in_rows[b];
-      return a < b;                                        // list order, then position
+      return by_position && a < b;
     });
     for (int j = 0; j < k_out; ++j) {
       out_scores[(size_t)q * k_out + j] = j < take ? in_scores[order[j]] : -INFINITY;
       if (in_rows) out_rows[(size_t)q * k_out + j] = j < take ? in_rows[order[j]] : -1;
     }
   }
+}
+}  // namespace
+
+// in_scores / in_rows [n_lists][n_queries][list_len]: source positions ascend by list, then by position in the list
+extern "C" int dhr_merge_topk_lists_host(int32_t n_queries, int32_t n_lists, int32_t list_len, const float* in_scores,
+                                         const int64_t* in_rows, int32_t k_out, float* out_scores, int64_t* out_rows) try {
+  if (n_queries <= 0 || n_lists <= 0 || list_len <= 0 || k_out <= 0 || !in_scores || !out_scores || (in_rows && !out_rows))
+    return set_error(DHR_ERR_INVALID, "bad argument");
+  merge_topk_on_host(n_queries, (int64_t)n_lists * list_len, [&](int q, int64_t j) { return ((j / list_len) * n_queries + q) * list_len + j % list_len; },
+                     true, in_scores, in_rows, k_out, out_scores, out_rows);
   return DHR_OK;
 } DHR_CATCH_STATUS
 
+// in_scores / in_rows [n_queries][n_in]
 extern "C" int dhr_merge_topk_host(int32_t n_queries, int32_t n_in, const float* in_scores, const int64_t* in_rows,
                                    int32_t k_out, float* out_scores, int64_t* out_rows) try {
   if (n_queries <= 0 || n_in <= 0 || k_out <= 0 || !in_scores || !in_rows || !out_scores || !out_rows)
     return set_error(DHR_ERR_INVALID, "bad argument");
-  std::vector<int> order;
-  for (int q = 0; q < n_queries; ++q) {
-    const float* s = in_scores + (size_t)q * n_in;
-    const int64_t* r = in_rows + (size_t)q * n_in;
-    order.clear();
-    for (int j = 0; j < n_in; ++j)
-      if (r[j] >= 0) order.push_back(j);
-    const int take = std::min<int>(k_out, (int)order.size());
-    std::partial_sort(order.begin(), order.begin() + take, order.end(), [&](int a, int b) {
-      const uint32_t ka = f32_ordered(s[a]), kb = f32_ordered(s[b]);
-      if (ka != kb) return ka > kb;
-      return r[a] < r[b];
-    });
-    for (int j = 0; j < k_out; ++j) {
-      out_scores[(size_t)q * k_out + j] = j < take ? s[order[j]] : -INFINITY;
-      out_rows[(size_t)q * k_out + j] = j < take ? r[order[j]] : -1;
-    }
-  }
+  merge_topk_on_host(n_queries, n_in, [&](int q, int64_t j) { return (int64_t)q * n_in + j; }, false, in_scores, in_rows, k_out, out_scores, out_rows);
   return DHR_OK;
 } DHR_CATCH_STATUS

@@ -1,7 +1,10 @@
 // State shared by the host-side translation units of the library (round 6 split of api.hip, 2 583 lines):
 //   index_build.hip   dhr_index_create / destroy / parameters / info, the index file (over index_layout.h: the layout of an index, its column steps and bucket deal; included there alone -- two op files have a function `layout` of their own)
 //   search_core.hip   workspace, query preparation, the phase controller (search_core)
-//   api.hip           the search entry points (dhr_search, dhr_search_rerank, the staged calls), dhr_score_rows, densify, PQ training, debug hooks, shard reduce
+//   api.hip           the search entry points (dhr_search, dhr_search_rerank, the staged calls), dhr_score_rows, densify, PQ training / encoding / decoding, debug hooks, shard reduce
+//   pq_adc.hip        the dhr_pq_* handle (its kernels and its host half; through host_stage.h)
+//   sharded.hip       the sharded control flow
+// host_stage.h (on top of this header) adds the staging of host arrays through the device, for these files and for the op files.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -245,6 +248,8 @@ int check_queries(const dhr_index* ix, const dhr_query_batch* qb);
 int grow(void*& p, size_t& have, size_t need, int64_t& total);
 int prep_queries(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, hipStream_t s);
 dhr::RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_queries, bool gate);
+dhr::GemmArgs base_gemm_args(const dhr_index* ix, const Workspace& w, int n_queries);      // the caller adds the tile range and its mapping, the thresholds and lists, the dump
+dhr::SelectArgs rescored_select_args(const Workspace& w, int n_queries, int k);            // top k of w.rs_keys into w.topk_keys; the caller adds the key counts
 // The plan of a search of this handle for k rows (search_plan.h).  staged: a staged call or a rank query -- the handle chases its share of the
 // union's rank; a whole search (the repair dhr_search inside a sharded step among them) chases the rank itself.
 inline SearchPlan search_plan_of(const dhr_index* ix, int k, int depth, bool staged) {

@@ -17,14 +17,10 @@
 //      every block of rows; blocks double in size (the number of rows that beat a running k-th best is ~k ln(N/N0)), a block
 //      whose candidate lists overflow is re-run in halves.
 // Scores are plain fp32 sums in table order m = 0..M-1: deterministic and independent of the blocking.
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "dhr_internal.h"
+#include <memory>
 #include <mutex>
 
-using namespace dhr;
+#include "host_stage.h"
 
 struct dhr_pq {
   int device = 0;
@@ -52,8 +48,6 @@ constexpr int ADC_CAP = 32768;          // candidate list depth per query
 constexpr int ADC_Q_CHUNK = 1024;       // queries per pass over the codes (bounds the workspace: 0.77 GB)
 constexpr int ADC_THREADS = 1024;        // 16 waves share one pair's tables: with 256 threads the 128 KiB of LDS left ONE wave per SIMD to hide the gather latency (0.27 of the HBM rate)
 constexpr int ADC_ROWS_PER_WG = 32768;
-
-#define PQ_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dhr_set_error_message(DHR_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(e_)).c_str()); } while (0)
 
 // queries (fp16 or fp32, any leading dimension) -> dense fp32 [Q][d]
 __global__ void adc_q32_kernel(const void* __restrict__ src, int is_f32, int64_t ld, int n_queries, int d, float* __restrict__ out) {
@@ -133,57 +127,49 @@ __global__ void adc_init_kernel(float* thr, float* tau, float* margin, uint32_t*
   if (i < n) { thr[i] = -INFINITY; tau[i] = -INFINITY; margin[i] = 0.f; cnt[i] = 0u; }
 }
 
-template <typename T>
-int grow(T*& p, size_t bytes, int64_t& total) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  if (hipMalloc((void**)&p, bytes) != hipSuccess) return dhr_set_error_message(DHR_ERR_HIP, ("hipMalloc of " + std::to_string(bytes) + " bytes failed (ADC workspace)").c_str());
-  total += (int64_t)bytes;
-  return DHR_OK;
-}
-
+// The workspace for nq queries and k results: grow-only in the queries, re-made when kp changes.  The ten buffers are allocated into local
+// guards first; the handle takes them -- with q_cap, kp and bytes -- only when all ten exist, so a failed growth leaves it as it was.
 int ensure_ws(dhr_pq* pq, int nq, int k) {
   int kp = 64;
   while (kp < k) kp <<= 1;
   const int q_cap = (std::min(nq, ADC_Q_CHUNK) + 1) & ~1;
   if (pq->q_cap >= q_cap && pq->kp == kp) return DHR_OK;
-  const int qc = std::max(q_cap, pq->q_cap);
+  const size_t qc = (size_t)std::max(q_cap, pq->q_cap), per_q = (size_t)pq->M * pq->ksub;
+  enum { LUT, Q32, CAND, CNT, KEYS, TOPK, THR, TAU, MARGIN, D_MAX, N_BUFFERS };
+  const size_t bytes[N_BUFFERS] = {qc * per_q * 4, qc * pq->d * 4, qc * ADC_CAP * 8, qc * 4, qc * ADC_CAP * 8, qc * kp * 8, qc * 4, qc * 4, qc * 4, 16};
+  DevMem fresh[N_BUFFERS];
   int64_t tot = 0;
-  int rc;
-  const size_t per_q = (size_t)pq->M * pq->ksub;
-  if ((rc = grow(pq->lut, (size_t)qc * per_q * 4, tot))) return rc;
-  if ((rc = grow(pq->q32, (size_t)qc * pq->d * 4, tot))) return rc;
-  if ((rc = grow(pq->cand, (size_t)qc * ADC_CAP * 8, tot))) return rc;
-  if ((rc = grow(pq->cnt, (size_t)qc * 4, tot))) return rc;
-  if ((rc = grow(pq->keys, (size_t)qc * ADC_CAP * 8, tot))) return rc;
-  if ((rc = grow(pq->topk, (size_t)qc * kp * 8, tot))) return rc;
-  if ((rc = grow(pq->thr, (size_t)qc * 4, tot))) return rc;
-  if ((rc = grow(pq->tau, (size_t)qc * 4, tot))) return rc;
-  if ((rc = grow(pq->margin, (size_t)qc * 4, tot))) return rc;
-  if ((rc = grow(pq->d_max, 16, tot))) return rc;
-  pq->q_cap = qc; pq->kp = kp;
+  for (int i = 0; i < N_BUFFERS; ++i) {
+    HIP_TRY(dev_alloc(fresh[i], (int64_t)bytes[i]));
+    tot += (int64_t)bytes[i];
+  }
+  auto take = [&](auto*& p, int i) {
+    (void)hipFree(p);
+    p = static_cast<std::remove_reference_t<decltype(p)>>(fresh[i].p);
+    fresh[i].p = nullptr;
+  };
+  take(pq->lut, LUT); take(pq->q32, Q32); take(pq->cand, CAND); take(pq->cnt, CNT); take(pq->keys, KEYS); take(pq->topk, TOPK);
+  take(pq->thr, THR); take(pq->tau, TAU); take(pq->margin, MARGIN); take(pq->d_max, D_MAX);
+  pq->q_cap = (int)qc; pq->kp = kp;
   pq->bytes = (int64_t)pq->n * pq->M + (int64_t)pq->M * pq->ksub * pq->dsub * 4 + tot;
   return DHR_OK;
 }
 
 int build_lut(dhr_pq* pq, const dhr_query_batch* qb, int q_lo, int nq, hipStream_t s) {
-  const void* src = qb->value;
   const int vsz = qb->value_dtype == DHR_VAL_F32 ? 4 : 2;
-  const char* base = (const char*)src + (size_t)q_lo * qb->ld_value * vsz;
-  void* staged = nullptr;
+  const char* base = (const char*)qb->value + (size_t)q_lo * qb->ld_value * vsz;
+  DevMem staged;
   if (qb->mem_kind == DHR_MEM_HOST) {                         // stage the chunk's rows
-    const size_t bytes = (size_t)nq * qb->ld_value * vsz;
-    PQ_HIP(hipMalloc(&staged, bytes));
-    PQ_HIP(hipMemcpyAsync(staged, base, bytes, hipMemcpyHostToDevice, s));
-    base = (const char*)staged;
+    HIP_TRY(stage_in(staged, base, (size_t)nq * qb->ld_value * vsz, s));
+    base = (const char*)staged.p;
   }
   const int64_t n1 = (int64_t)nq * pq->d;
   hipLaunchKernelGGL(adc_q32_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, (const void*)base, qb->value_dtype == DHR_VAL_F32 ? 1 : 0,
                      qb->ld_value, nq, pq->d, pq->q32);
   const int64_t n2 = (int64_t)nq * pq->M * pq->ksub;
-  if (nq & 1) PQ_HIP(hipMemsetAsync(pq->lut + (size_t)(nq >> 1) * pq->M * pq->ksub * 2, 0, (size_t)pq->M * pq->ksub * 8, s));   // the odd pair's second table
+  if (nq & 1) HIP_TRY(hipMemsetAsync(pq->lut + (size_t)(nq >> 1) * pq->M * pq->ksub * 2, 0, (size_t)pq->M * pq->ksub * 8, s));   // the odd pair's second table
   hipLaunchKernelGGL(adc_lut_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, pq->q32, nq, pq->d, pq->M, pq->ksub, pq->dsub, pq->cb, pq->lut);
-  if (staged) { PQ_HIP(hipStreamSynchronize(s)); PQ_HIP(hipFree(staged)); }
+  if (staged.p) HIP_TRY(hipStreamSynchronize(s));            // (the staged rows are released on return)
   return DHR_OK;
 }
 
@@ -195,12 +181,12 @@ int scan(dhr_pq* pq, int nq, int64_t lo, int64_t hi, bool filter, float* dump, i
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lock(attr_mu);
-    if (lds > attr_dev[dev & 63]) { PQ_HIP(hipFuncSetAttribute((const void*)adc_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); attr_dev[dev & 63] = lds; }
+    if (lds > attr_dev[dev & 63]) { HIP_TRY(hipFuncSetAttribute((const void*)adc_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); attr_dev[dev & 63] = lds; }
   }
   const unsigned blocks = (unsigned)((hi - lo + ADC_ROWS_PER_WG - 1) / ADC_ROWS_PER_WG);
   hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)((nq + 1) / 2), blocks), dim3(ADC_THREADS), lds, s, pq->codes, pq->M, pq->ksub, lo, hi, pq->lut, nq,
                      filter ? pq->thr : nullptr, pq->cand, pq->cnt, (uint32_t)ADC_CAP, dump, dump_ld);
-  PQ_HIP(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return DHR_OK;
 }
 
@@ -209,22 +195,21 @@ int scan(dhr_pq* pq, int nq, int64_t lo, int64_t hi, bool filter, float* dump, i
 extern "C" int dhr_pq_create(int32_t device, int32_t mem_kind, int64_t n, int32_t d, int32_t M, int32_t nbits, const float* codebooks,
                              const uint8_t* codes, int64_t row_offset, dhr_pq** out) try {
   if (!out || !codebooks || !codes || n <= 0 || d <= 0 || M <= 0 || d % M || nbits < 1 || nbits > 8)
-    return dhr_set_error_message(DHR_ERR_INVALID, "bad argument (1 <= nbits <= 8, d a multiple of M)");
-  if (!DHR_MEM_KIND_OK(mem_kind)) return dhr_set_error_message(DHR_ERR_INVALID, "bad mem_kind");
-  if ((M << nbits) * 8 > 160 * 1024 - 1024) return dhr_set_error_message(DHR_ERR_UNSUPPORTED, "the lookup tables of a query pair (M * 2^nbits * 8 B) do not fit the LDS");
-  PQ_HIP(hipSetDevice(device));
-  dhr_pq* pq = new dhr_pq();
+    return set_error(DHR_ERR_INVALID, "bad argument (1 <= nbits <= 8, d a multiple of M)");
+  if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
+  if ((M << nbits) * 8 > 160 * 1024 - 1024) return set_error(DHR_ERR_UNSUPPORTED, "the lookup tables of a query pair (M * 2^nbits * 8 B) do not fit the LDS");
+  HIP_TRY(hipSetDevice(device));
+  struct Destroy { void operator()(dhr_pq* p) const { dhr_pq_destroy(p); } };
+  std::unique_ptr<dhr_pq, Destroy> pq(new dhr_pq());          // (owns the handle and its arrays until *out takes it)
   pq->device = device; pq->n = n; pq->row_offset = row_offset; pq->d = d; pq->M = M; pq->nbits = nbits; pq->ksub = 1 << nbits; pq->dsub = d / M;
   const size_t cb_bytes = (size_t)M * pq->ksub * pq->dsub * 4, code_bytes = (size_t)n * M;
-  if (hipMalloc((void**)&pq->cb, cb_bytes) != hipSuccess || hipMalloc((void**)&pq->codes, code_bytes) != hipSuccess) {
-    (void)hipFree(pq->cb); delete pq;
-    return dhr_set_error_message(DHR_ERR_HIP, "hipMalloc of the PQ index failed");
-  }
+  HIP_TRY(hipMalloc((void**)&pq->cb, cb_bytes));
+  HIP_TRY(hipMalloc((void**)&pq->codes, code_bytes));
   const hipMemcpyKind kind = mem_kind == DHR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  PQ_HIP(hipMemcpy(pq->cb, codebooks, cb_bytes, kind));
-  PQ_HIP(hipMemcpy(pq->codes, codes, code_bytes, kind));
+  HIP_TRY(hipMemcpy(pq->cb, codebooks, cb_bytes, kind));
+  HIP_TRY(hipMemcpy(pq->codes, codes, code_bytes, kind));
   pq->bytes = (int64_t)(cb_bytes + code_bytes);
-  *out = pq;
+  *out = pq.release();
   return DHR_OK;
 } DHR_CATCH_STATUS
 extern "C" void dhr_pq_destroy(dhr_pq* pq) try {
@@ -236,7 +221,7 @@ extern "C" void dhr_pq_destroy(dhr_pq* pq) try {
 } DHR_CATCH_VOID
 extern "C" int64_t dhr_pq_device_bytes(const dhr_pq* pq) try { return pq ? pq->bytes : 0; } DHR_CATCH_VALUE(0)
 extern "C" int dhr_pq_last_scan(const dhr_pq* pq, double* ms, double* code_bytes) try {
-  if (!pq) return dhr_set_error_message(DHR_ERR_INVALID, "null handle");
+  if (!pq) return set_error(DHR_ERR_INVALID, "null handle");
   if (ms) *ms = pq->last_scan_ms;
   if (code_bytes) *code_bytes = pq->last_code_bytes;
   return DHR_OK;
@@ -244,8 +229,8 @@ extern "C" int dhr_pq_last_scan(const dhr_pq* pq, double* ms, double* code_bytes
 
 // Raw ADC scores of rows [row_lo, row_hi) for every query: out [n_queries][row_hi - row_lo] fp32, device memory (tests).
 extern "C" int dhr_pq_adc_scores(dhr_pq* pq, const dhr_query_batch* qb, int64_t row_lo, int64_t row_hi, float* out_dev, void* stream) try {
-  if (!pq || !qb || !qb->value || !out_dev || row_lo < 0 || row_hi > pq->n || row_lo >= row_hi) return dhr_set_error_message(DHR_ERR_INVALID, "bad argument");
-  PQ_HIP(hipSetDevice(pq->device));
+  if (!pq || !qb || !qb->value || !out_dev || row_lo < 0 || row_hi > pq->n || row_lo >= row_hi) return set_error(DHR_ERR_INVALID, "bad argument");
+  HIP_TRY(hipSetDevice(pq->device));
   hipStream_t s = (hipStream_t)stream;
   int rc;
   for (int q_lo = 0; q_lo < qb->n_queries; q_lo += ADC_Q_CHUNK) {
@@ -254,7 +239,7 @@ extern "C" int dhr_pq_adc_scores(dhr_pq* pq, const dhr_query_batch* qb, int64_t 
     if ((rc = build_lut(pq, qb, q_lo, nq, s))) return rc;
     if ((rc = scan(pq, nq, row_lo, row_hi, false, out_dev + (int64_t)q_lo * (row_hi - row_lo), row_hi - row_lo, s))) return rc;
   }
-  PQ_HIP(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(s));
   return DHR_OK;
 } DHR_CATCH_STATUS
 
@@ -262,26 +247,24 @@ extern "C" int dhr_pq_adc_scores(dhr_pq* pq, const dhr_query_batch* qb, int64_t 
 // out_scores [n_queries][k] fp32, out_rows [n_queries][k] int64 global rows; (-inf, -1) beyond the corpus size.
 extern "C" int dhr_pq_search(dhr_pq* pq, const dhr_query_batch* qb, int32_t k, float* out_scores, int64_t* out_rows, int32_t out_mem_kind,
                              void* stream) try {
-  if (!pq || !qb || !qb->value || !out_scores || !out_rows || qb->n_queries <= 0) return dhr_set_error_message(DHR_ERR_INVALID, "bad argument");
-  if (k <= 0 || k > (1 << 20)) return dhr_set_error_message(DHR_ERR_INVALID, "k must be in [1, 1048576]");      // k > 16384: the global-memory merge (select_global.hip)
-  if (!DHR_MEM_KIND_OK(out_mem_kind) || !DHR_MEM_KIND_OK(qb->mem_kind)) return dhr_set_error_message(DHR_ERR_INVALID, "bad mem_kind");
-  PQ_HIP(hipSetDevice(pq->device));
+  if (!pq || !qb || !qb->value || !out_scores || !out_rows || qb->n_queries <= 0) return set_error(DHR_ERR_INVALID, "bad argument");
+  if (k <= 0 || k > (1 << 20)) return set_error(DHR_ERR_INVALID, "k must be in [1, 1048576]");      // k > 16384: the global-memory merge (select_global.hip)
+  if (!DHR_MEM_KIND_OK(out_mem_kind) || !DHR_MEM_KIND_OK(qb->mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
+  HIP_TRY(hipSetDevice(pq->device));
   hipStream_t s = (hipStream_t)stream;
+  Events evs;
   hipEvent_t e0, e1;
-  PQ_HIP(hipEventCreate(&e0)); PQ_HIP(hipEventCreate(&e1));
+  HIP_TRY(evs.add(&e0)); HIP_TRY(evs.add(&e1));
   double scan_ms = 0, code_bytes = 0;
   int rc = DHR_OK;
-  float* d_scores = nullptr;
-  int64_t* d_rows = nullptr;
-  void* stage = nullptr;
-  auto done = [&](int code) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(stage); return code; };
+  DevMem stage;                                // host outputs: the lists of one chunk on their way out
   for (int q_lo = 0; q_lo < qb->n_queries; q_lo += ADC_Q_CHUNK) {
     const int nq = std::min(ADC_Q_CHUNK, qb->n_queries - q_lo);
-    if ((rc = ensure_ws(pq, nq, k))) return done(rc);
+    if ((rc = ensure_ws(pq, nq, k))) return rc;
     const int kp = pq->kp;
-    if ((rc = build_lut(pq, qb, q_lo, nq, s))) return done(rc);
+    if ((rc = build_lut(pq, qb, q_lo, nq, s))) return rc;
     hipLaunchKernelGGL(adc_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, pq->thr, pq->tau, pq->margin, pq->cnt, nq);
-    if (hipMemsetAsync(pq->topk, 0, (size_t)nq * kp * 8, s) != hipSuccess) return done(dhr_set_error_message(DHR_ERR_HIP, "memset failed"));
+    HIP_TRY(hipMemsetAsync(pq->topk, 0, (size_t)nq * kp * 8, s));
     SelectArgs sel{};
     sel.topk_keys = pq->topk; sel.in_keys = pq->keys; sel.ld_keys = ADC_CAP; sel.cnt = pq->cnt; sel.count_all = 0; sel.cap = ADC_CAP;
     sel.k = k; sel.kp = kp; sel.sort_n = 4 * kp; sel.kps = kp; sel.margin = pq->margin; sel.tau = pq->tau; sel.thr = pq->thr; sel.n_queries = nq;
@@ -292,15 +275,15 @@ extern "C" int dhr_pq_search(dhr_pq* pq, const dhr_query_batch* qb, int32_t k, f
     while (lo < pq->n) {
       int64_t hi = std::min(pq->n, lo + step);
       for (;;) {
-        if (hipMemsetAsync(pq->cnt, 0, (size_t)nq * 4, s) != hipSuccess) return done(dhr_set_error_message(DHR_ERR_HIP, "memset failed"));
+        HIP_TRY(hipMemsetAsync(pq->cnt, 0, (size_t)nq * 4, s));
         (void)hipEventRecord(e0, s);
-        if ((rc = scan(pq, nq, lo, hi, true, nullptr, 0, s))) return done(rc);
+        if ((rc = scan(pq, nq, lo, hi, true, nullptr, 0, s))) return rc;
         (void)hipEventRecord(e1, s);
-        if (hipMemsetAsync(pq->d_max, 0, 16, s) != hipSuccess || launch_max_u32(pq->cnt, nq, pq->d_max, (unsigned long long*)(pq->d_max + 2), s) != hipSuccess)
-          return done(dhr_set_error_message(DHR_ERR_HIP, "max launch failed"));
+        HIP_TRY(hipMemsetAsync(pq->d_max, 0, 16, s));
+        HIP_TRY(launch_max_u32(pq->cnt, nq, pq->d_max, (unsigned long long*)(pq->d_max + 2), s));
         uint32_t mx = 0;
-        if (hipMemcpyAsync(&mx, pq->d_max, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-          return done(dhr_set_error_message(DHR_ERR_HIP, "count read-back failed"));
+        HIP_TRY(stage_out(&mx, pq->d_max, 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
         float ms = 0;
         (void)hipEventElapsedTime(&ms, e0, e1);
         scan_ms += ms; code_bytes += (double)(hi - lo) * pq->M * ((nq + 1) / 2);
@@ -308,25 +291,16 @@ extern "C" int dhr_pq_search(dhr_pq* pq, const dhr_query_batch* qb, int32_t k, f
         hi = lo + std::max<int64_t>((hi - lo) / 2, 1);            // a list overflowed: the block again, half as long (<= ADC_CAP rows cannot overflow)
       }
       hipLaunchKernelGGL(adc_keys_kernel, dim3(8, (unsigned)nq), dim3(256), 0, s, pq->cand, pq->cnt, (uint32_t)ADC_CAP, nq, pq->keys);
-      if (launch_select(sel, s) != hipSuccess) return done(dhr_set_error_message(DHR_ERR_HIP, "select launch failed"));
+      HIP_TRY(launch_select(sel, s));
       step = std::max<int64_t>(hi, step);
       lo = hi;
     }
-    // deliver this chunk's lists
-    float* os = out_scores + (int64_t)q_lo * k;
-    int64_t* orow = out_rows + (int64_t)q_lo * k;
-    if (out_mem_kind == DHR_MEM_HOST) {
-      if (!stage && hipMalloc(&stage, (size_t)ADC_Q_CHUNK * k * 12) != hipSuccess) return done(dhr_set_error_message(DHR_ERR_HIP, "hipMalloc failed"));
-      d_rows = (int64_t*)stage; d_scores = (float*)((char*)stage + (size_t)ADC_Q_CHUNK * k * 8);
-    } else { d_scores = os; d_rows = orow; }
-    if (launch_emit(pq->topk, kp, nq, k, pq->row_offset, d_scores, d_rows, s) != hipSuccess) return done(dhr_set_error_message(DHR_ERR_HIP, "emit launch failed"));
-    if (out_mem_kind == DHR_MEM_HOST) {
-      if (hipMemcpyAsync(os, d_scores, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-          hipMemcpyAsync(orow, d_rows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return done(dhr_set_error_message(DHR_ERR_HIP, "result copy failed"));
-    }
+    // deliver this chunk's lists (host arrays: complete before the next chunk re-uses the staging buffer)
+    if (out_mem_kind == DHR_MEM_HOST && !stage.p) HIP_TRY(dev_alloc(stage, (int64_t)ADC_Q_CHUNK * k * 12));
+    if ((rc = emit_topk(pq->topk, kp, nq, k, pq->row_offset, out_scores + (int64_t)q_lo * k, out_rows + (int64_t)q_lo * k, out_mem_kind, stage.p, s))) return rc;
+    if (out_mem_kind == DHR_MEM_HOST) HIP_TRY(hipStreamSynchronize(s));
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return done(dhr_set_error_message(DHR_ERR_HIP, "stream synchronize failed"));
+  HIP_TRY(hipStreamSynchronize(s));
   pq->last_scan_ms = scan_ms; pq->last_code_bytes = code_bytes;
-  return done(DHR_OK);
+  return DHR_OK;
 } DHR_CATCH_STATUS

@@ -245,12 +245,22 @@ RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_que
 }
 // What every bound-GEMM launch of a search shares -- the operands of both sides, the geometry, the depth of the uniform lists; the caller adds the
 // tile range and its mapping, the thresholds and the list set
-static GemmArgs base_gemm_args(const dhr_index* ix, const Workspace& w, int Q) {
+GemmArgs base_gemm_args(const dhr_index* ix, const Workspace& w, int Q) {
   GemmArgs g{};
   g.a_tiles = ix->tiles; g.b_tiles = w.q_tiles; g.ksteps = ix->ksteps; g.k_split = ix->d_dlr / TILE_K; g.ts = ix->ts; g.td = ix->td; g.ts_q = w.ts_q; g.variant = ix->gemm_variant;
   g.i8_mul = (ix->dense_i8 || ix->gated_i8) ? w.i8_mul : nullptr; g.g8_shift = ix->gated_i8 ? w.g8_shift : nullptr; g.g8_rsum = ix->g8_rsum;
   g.n_tiles = ix->n_tiles; g.n_qtiles = w.q_pad / TILE_ROWS; g.n_rows = ix->n_rows; g.cap = (uint32_t)w.cap; g.n_queries = Q;
   return g;
+}
+// The top k of the rescored keys in the workspace (w.rs_keys), merged into the running lists w.topk_keys; the caller adds where the key counts
+// come from (cnt / count_all) and, where the threshold rank differs from the rows kept, k_keep
+SelectArgs rescored_select_args(const Workspace& w, int Q, int k) {
+  SelectArgs sel{};
+  sel.topk_keys = w.topk_keys; sel.in_keys = w.rs_keys; sel.ld_keys = w.keys_ld; sel.cap = (uint32_t)w.cap;
+  sel.k = k; sel.kp = w.kp; sel.sort_n = select_sort_n(w.kp);
+  sel.kps = 64; while (sel.kps < k) sel.kps <<= 1;
+  sel.margin = w.margin; sel.tau = w.tau; sel.thr = w.thr; sel.n_queries = Q;
+  return sel;
 }
 // ... and every refine launch: bound lists of depth w.cap filtered at thr into the survivor lists; the caller adds the list set and the launch geometry
 static RefineArgs base_refine_args(const dhr_index* ix, const Workspace& w, int Q, bool gate, const float* thr) {
@@ -879,12 +889,8 @@ int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, i
   // first attempt of a sampled search: the controller only enqueues (no host read-backs); DHR_PARAM_ASYNC_CONTROLLER 0 keeps the
   // host-driven controller (and the fallback depths always use it: it is the one that is exact for any input)
   c.async_ctl = depth == 0 && p.S >= 2 && ix->async_ctl != 0 && !getenv("DHR_DEBUG_PLAN");
-  SelectArgs& sel = c.sel;
-  sel.topk_keys = w.topk_keys; sel.in_keys = w.rs_keys; sel.ld_keys = w.keys_ld; sel.cap = (uint32_t)w.cap;
-  sel.k = p.r_eff; sel.kp = w.kp; sel.sort_n = select_sort_n(w.kp);
-  sel.k_keep = k;                          // the threshold is the r-th best seen, the list keeps the k best (ties with the final k-th score survive the sampled run)
-  sel.kps = 64; while (sel.kps < k) sel.kps <<= 1; sel.margin = w.margin; sel.tau = w.tau; sel.thr = w.thr;
-  sel.n_queries = c.Q;
+  c.sel = rescored_select_args(w, c.Q, k);
+  c.sel.k = p.r_eff; c.sel.k_keep = k;     // the threshold is the r-th best seen, the list keeps the k best (ties with the final k-th score survive the sampled run)
 
   if (fresh && (rc = prepare_and_phase0(c, qb)) != DHR_OK) return rc;
   if (!fresh && ix->pend.state == StagedState::Complete) return DHR_OK;              // the begin call already finished the search

@@ -1,6 +1,6 @@
-// Host code shared by the translation units that take arrays from host or device memory (the op files gip_train, maxsim, train_loss, lexical*,
-// aggretriever_train; the entry points of api.hip; the PQ handle of pq_adc.hip): the dtype checks of the C ABI and the ONE vocabulary for staging
-// host arrays through the device.  A staged call owns its device copies in DevMem objects, enqueues every copy on the caller's stream and
+// Host code shared by the translation units that take arrays from host or device memory (the op files gip_train, maxsim, train_loss and
+// aggretriever_train; the lexical heads, through lexical_common.h -- dhr_lexical_head and dhr_aggregate stage host arrays with it; the entry points
+// of api.hip; the PQ handle of pq_adc.hip): the dtype checks of the C ABI and the ONE vocabulary for staging host arrays through the device.  A staged call owns its device copies in DevMem objects, enqueues every copy on the caller's stream and
 // synchronises that stream itself before it returns.  Matrices with a row stride go through the 2-D forms, contiguous arrays through the flat
 // ones; operand_in / operand_out give "the device view of an operand" (the pointer itself for device memory, else a staged copy), emit_topk hands
 // a sorted top-k out.  The step from a code that passed these checks to a C++ type is op_dispatch.h (with_value_type, with_index_type, ...),

@@ -13,7 +13,6 @@
 // Semantics kept literally: every contribution is (p * w) * mask in fp32 (a masked token folds in a zero with the sign of w), ties keep the
 // first token and the first group (torch.max on the device), aggregate(full) is pos * (pos > neg) - neg * (pos <= neg) with its signs of zero.
 // NaN and +inf logits are out of scope (an unmasked row must hold a finite value).
-#include "host_stage.h"
 #include "op_dispatch.h"
 #include "lexical_common.h"
 
@@ -188,16 +187,8 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
       ld_weights < n_tokens || ld_mask < n_tokens || cls_dim < 0 || (int64_t)batch * n_tokens > ((int64_t)1 << 31) - 1)
     return set_error(DHR_ERR_INVALID, "bad sizes / strides");
   Geometry geo;
-  int rc = geometry(mode, vocab, dims, remove_dims, geo);
+  int rc = check_record(mode, vocab, dims, remove_dims, ld_value, out_index, index_dtype, ld_index, cls, cls_dtype, ld_cls, cls_dim, geo);
   if (rc) return rc;
-  if (ld_value < (int64_t)geo.out_cols + cls_dim) return set_error(DHR_ERR_INVALID, "ld_value is smaller than the record's columns");
-  if (cls_dim > 0 && (!cls || !val_ok(cls_dtype) || ld_cls < cls_dim)) return set_error(DHR_ERR_INVALID, "bad cls reps");
-  if (mode == MODE_DENSIFY) {
-    if (!out_index) return set_error(DHR_ERR_INVALID, "null index pointer");
-    if (index_dtype != DHR_IDX_U8 && index_dtype != DHR_IDX_I16) return set_error(DHR_ERR_INVALID, "index dtype must be uint8 or int16");
-    if (index_dtype == DHR_IDX_U8 && geo.n_groups > 256) return set_error(DHR_ERR_UNSUPPORTED, "more than 256 groups need the int16 index dtype");
-    if (ld_index < geo.out_cols) return set_error(DHR_ERR_INVALID, "ld_index < dims");
-  }
   if (batch == 0) return DHR_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
@@ -207,33 +198,32 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   a.T = T; a.V = vocab; a.remove = geo.remove; a.W = geo.W; a.n_groups = geo.n_groups;
   a.val_f32 = out_value_dtype == DHR_VAL_F32; a.idx_i16 = index_dtype == DHR_IDX_I16;
   auto run = [&](const void* lg, int64_t ldb, int64_t ldt, const float* w, int64_t ldw, const float* m, int64_t ldm, int64_t rows, float4* stats,
-                 void* val, int64_t ldv, void* idx, int64_t ldi, const void* c, int64_t ldc) -> hipError_t {
+                 void* val, int64_t ldv, void* idx, int64_t ldi, const void* c, int64_t ldc) -> int {
     with_value_type_bf16(logits_dtype, [&](auto t) {
       using TIN = typename decltype(t)::type;
       hipLaunchKernelGGL(lexical_stats_kernel<TIN>, dim3((unsigned)(rows * T)), dim3(256), 0, s, (const TIN*)lg, ldb, ldt, T, vocab, w, ldw, m, ldm,
                          stats);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    HIP_TRY(hipGetLastError());
     FoldArgs f = a;
     f.ld_batch = ldb; f.ld_token = ldt; f.stats = stats; f.batch = rows;
     f.out_val = val; f.ld_val = ldv; f.out_idx = idx; f.ld_idx = ldi;
-    if ((e = launch_fold(lg, logits_dtype, mode, f, s)) != hipSuccess) return e;
+    HIP_TRY(launch_fold(lg, logits_dtype, mode, f, s));
     if (cls_dim > 0) {
       const unsigned blocks = (unsigned)std::min<int64_t>((rows * cls_dim + 255) / 256, 4096);
       hipLaunchKernelGGL(lexical_cls_kernel, dim3(blocks), dim3(256), 0, s, c, cls_dtype == DHR_VAL_F32, ldc, cls_dim, rows, val,
                          out_value_dtype == DHR_VAL_F32, ldv, geo.out_cols);
-      e = hipGetLastError();
+      HIP_TRY(hipGetLastError());
     }
-    return e;
+    return DHR_OK;
   };
   if (mem_kind == DHR_MEM_DEVICE) {
     DevMem ws_mem;
     void* ws = workspace;
     if (!ws) HIP_TRY(dev_alloc(ws_mem, batch * T * (int64_t)sizeof(float4)));
     if (!ws) ws = ws_mem.p;
-    HIP_TRY(run(logits, ld_batch, ld_token, term_weights, ld_weights, mask, ld_mask, batch, (float4*)ws, out_value, ld_value, out_index, ld_index, cls,
-                ld_cls));
+    rc = run(logits, ld_batch, ld_token, term_weights, ld_weights, mask, ld_mask, batch, (float4*)ws, out_value, ld_value, out_index, ld_index, cls, ld_cls);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return DHR_OK;
   }
@@ -242,27 +232,26 @@ extern "C" int dhr_lexical_head(int32_t device, int32_t mem_kind, int32_t mode, 
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / per_row));
   const int64_t ldv = geo.out_cols + cls_dim;
   DevMem m_in, m_w, m_m, m_st, m_val, m_idx, m_cls;
-  if (dev_alloc(m_in, block * per_row) != hipSuccess || dev_alloc(m_w, block * T * 4) != hipSuccess || dev_alloc(m_m, block * T * 4) != hipSuccess ||
-      dev_alloc(m_st, block * T * (int64_t)sizeof(float4)) != hipSuccess || dev_alloc(m_val, block * ldv * oes) != hipSuccess ||
-      (mode == MODE_DENSIFY && dev_alloc(m_idx, block * geo.out_cols * xes) != hipSuccess) ||
-      (cls_dim > 0 && dev_alloc(m_cls, block * cls_dim * ces) != hipSuccess))
-    return set_error(DHR_ERR_HIP, "hipMalloc failed");
+  HIP_TRY(dev_alloc(m_in, block * per_row));
+  HIP_TRY(dev_alloc(m_w, block * T * 4));
+  HIP_TRY(dev_alloc(m_m, block * T * 4));
+  HIP_TRY(dev_alloc(m_st, block * T * (int64_t)sizeof(float4)));
+  HIP_TRY(dev_alloc(m_val, block * ldv * oes));
+  if (mode == MODE_DENSIFY) HIP_TRY(dev_alloc(m_idx, block * geo.out_cols * xes));
+  if (cls_dim > 0) HIP_TRY(dev_alloc(m_cls, block * cls_dim * ces));
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
     for (int64_t r = 0; r < rows; ++r)
-      if (copy_in((char*)m_in.p + r * per_row, (const char*)logits + (lo + r) * ld_batch * ies, ld_token, T, vocab, ies, s) != hipSuccess)
-        return set_error(DHR_ERR_HIP, "H2D failed");
-    if (copy_in(m_w.p, term_weights + lo * ld_weights, ld_weights, rows, T, 4, s) != hipSuccess ||
-        copy_in(m_m.p, mask + lo * ld_mask, ld_mask, rows, T, 4, s) != hipSuccess ||
-        (cls_dim > 0 && copy_in(m_cls.p, (const char*)cls + lo * ld_cls * ces, ld_cls, rows, cls_dim, ces, s) != hipSuccess))
-      return set_error(DHR_ERR_HIP, "H2D failed");
-    if (run(m_in.p, (int64_t)T * vocab, vocab, (const float*)m_w.p, T, (const float*)m_m.p, T, rows, (float4*)m_st.p, m_val.p, ldv, m_idx.p,
-            geo.out_cols, m_cls.p, cls_dim) != hipSuccess)
-      return set_error(DHR_ERR_HIP, "lexical head launch failed");
-    if (stage_out((char*)out_value + lo * ld_value * oes, ld_value, m_val.p, rows, ldv, oes, s) != hipSuccess ||
-        (mode == MODE_DENSIFY && stage_out((char*)out_index + lo * ld_index * xes, ld_index, m_idx.p, rows, geo.out_cols, xes, s) != hipSuccess))
-      return set_error(DHR_ERR_HIP, "D2H failed");
-    if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "lexical head failed on the device");
+      HIP_TRY(copy_in((char*)m_in.p + r * per_row, (const char*)logits + (lo + r) * ld_batch * ies, ld_token, T, vocab, ies, s));
+    HIP_TRY(copy_in(m_w.p, term_weights + lo * ld_weights, ld_weights, rows, T, 4, s));
+    HIP_TRY(copy_in(m_m.p, mask + lo * ld_mask, ld_mask, rows, T, 4, s));
+    if (cls_dim > 0) HIP_TRY(copy_in(m_cls.p, (const char*)cls + lo * ld_cls * ces, ld_cls, rows, cls_dim, ces, s));
+    rc = run(m_in.p, (int64_t)T * vocab, vocab, (const float*)m_w.p, T, (const float*)m_m.p, T, rows, (float4*)m_st.p, m_val.p, ldv, m_idx.p, geo.out_cols,
+             m_cls.p, cls_dim);
+    if (rc) return rc;
+    HIP_TRY(stage_out((char*)out_value + lo * ld_value * oes, ld_value, m_val.p, rows, ldv, oes, s));
+    if (mode == MODE_DENSIFY) HIP_TRY(stage_out((char*)out_index + lo * ld_index * xes, ld_index, m_idx.p, rows, geo.out_cols, xes, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return DHR_OK;
 } DHR_CATCH_STATUS
@@ -276,8 +265,7 @@ extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexic
   if (batch < 0 || vocab <= 0 || ld < vocab || ld_out < dims) return set_error(DHR_ERR_INVALID, "bad sizes / strides");
   const int mode = full ? MODE_AGG_FULL : MODE_AGG_SEMI;
   Geometry geo;
-  int rc = geometry(mode, vocab, dims, remove_dims, geo);
-  if (rc) return rc;
+  if (int rc = geometry(mode, vocab, dims, remove_dims, geo)) return rc;
   if (batch == 0) return DHR_OK;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
@@ -293,16 +281,16 @@ extern "C" int dhr_aggregate(int32_t device, int32_t mem_kind, const void* lexic
   }
   const int64_t block = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)256 << 20) / ((int64_t)vocab * ies)));
   DevMem m_in, m_out;
-  if (dev_alloc(m_in, block * vocab * ies) != hipSuccess || dev_alloc(m_out, block * dims * oes) != hipSuccess)
-    return set_error(DHR_ERR_HIP, "hipMalloc failed");
+  HIP_TRY(dev_alloc(m_in, block * vocab * ies));
+  HIP_TRY(dev_alloc(m_out, block * dims * oes));
   a.ld_batch = vocab; a.out_val = m_out.p; a.ld_val = dims;
   for (int64_t lo = 0; lo < batch; lo += block) {
     const int64_t rows = std::min(block, batch - lo);
     a.batch = rows;
-    if (copy_in(m_in.p, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s) != hipSuccess) return set_error(DHR_ERR_HIP, "H2D failed");
-    if (launch_fold(m_in.p, value_dtype, mode, a, s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate launch failed");
-    if (stage_out((char*)out + lo * ld_out * oes, ld_out, m_out.p, rows, dims, oes, s) != hipSuccess) return set_error(DHR_ERR_HIP, "D2H failed");
-    if (hipStreamSynchronize(s) != hipSuccess) return set_error(DHR_ERR_HIP, "aggregate failed on the device");
+    HIP_TRY(copy_in(m_in.p, (const char*)lexical + lo * ld * ies, ld, rows, vocab, ies, s));
+    HIP_TRY(launch_fold(m_in.p, value_dtype, mode, a, s));
+    HIP_TRY(stage_out((char*)out + lo * ld_out * oes, ld_out, m_out.p, rows, dims, oes, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return DHR_OK;
 } DHR_CATCH_STATUS

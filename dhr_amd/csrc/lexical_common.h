@@ -1,9 +1,9 @@
 // What the translation units of the lexical head share (lexical.hip: encoding, lexical_train.hip: training, aggretriever_train.hip: the
 // Aggretriever training ops): the 16-byte row walk and lexical_stats_kernel, the per-token softmax statistics; the geometry of the grouped
-// views and the signed fold of aggregate(full); the 4-byte-aligned column vectors of the streaming passes.  One definition each, so the
-// training forwards are bit-identical to the encoding ones.
+// views and the signed fold of aggregate(full); the 4-byte-aligned column vectors of the streaming passes; check_record, the record rules of
+// the two encoding heads (lexical.hip, lexical_proj.hip).  One definition each, so the training forwards are bit-identical to the encoding ones.
 #pragma once
-#include "dhr_state.h"
+#include "host_stage.h"
 
 namespace dhr {
 // lexical.hip: its record epilogues (lexical_fold_kernel without statistics, lexical_cls_kernel) on fp32 reps [batch, vocab] (row stride
@@ -118,6 +118,21 @@ inline int geometry(int mode, int vocab, int dims, int remove, Geometry& g) {
   }
   if (cols / W > 32767) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 groups");
   g = {dims, (int)W, (int)(cols / W), remove};
+  return DHR_OK;
+}
+
+// The record rules of the encoding heads (dhr_lexical_head, dhr_lexical_proj_head): geometry() first, then the value rows with their [CLS]
+// columns, then -- densify alone -- the index rows.  Fills g.
+inline int check_record(int mode, int vocab, int dims, int remove, int64_t ld_value, const void* out_index, int index_dtype, int64_t ld_index,
+                        const void* cls, int cls_dtype, int64_t ld_cls, int cls_dim, Geometry& g) {
+  if (int rc = geometry(mode, vocab, dims, remove, g)) return rc;
+  if (ld_value < (int64_t)g.out_cols + cls_dim) return set_error(DHR_ERR_INVALID, "ld_value is smaller than the record's columns");
+  if (cls_dim > 0 && (!cls || !val_ok(cls_dtype) || ld_cls < cls_dim)) return set_error(DHR_ERR_INVALID, "bad cls reps");
+  if (mode != MODE_DENSIFY) return DHR_OK;
+  if (!out_index) return set_error(DHR_ERR_INVALID, "null index pointer");
+  if (index_dtype != DHR_IDX_U8 && index_dtype != DHR_IDX_I16) return set_error(DHR_ERR_INVALID, "index dtype must be uint8 or int16");
+  if (index_dtype == DHR_IDX_U8 && g.n_groups > 256) return set_error(DHR_ERR_UNSUPPORTED, "more than 256 groups need the int16 index dtype");
+  if (ld_index < g.out_cols) return set_error(DHR_ERR_INVALID, "ld_index < dims");
   return DHR_OK;
 }
 

@@ -1,22 +1,23 @@
 // What lexical_proj.hip (encoding) and lexical_proj_train.hip (training) share: the arguments, the compaction of the unmasked token rows, the
-// staged MFMA tile product, the softmax statistics pass with its combine, and the fold.  One definition each, so the training forward is
+// staged MFMA tile product, the softmax statistics pass with its combine, and the fold; on the host the operand rules, the workspace rule and
+// the one place that fills ProjArgs (the workspace layout itself: lexical_proj_layout.h).  One definition each, so the training forward is
 // bit-identical to the encoding one.  The kernels that touch hidden / weight are templates on their 16-bit element type E (_Float16 or __bf16):
 // the staging moves bytes, the fragment layouts of v_mfma_f32_32x32x16_f16 and _bf16 are the same, so tiling, walk and reduction order are common.
 #pragma once
 #include "lexical_common.h"
+#include "lexical_proj_layout.h"
 #include "op_dispatch.h"
 
 // Internal linkage on purpose: each translation unit that includes this header compiles its own copy of the kernels below, the non-template
 // ones (count, scan, fill, statistics, combine) included.  The duplication costs code size only and keeps the launches free of cross-unit symbols.
 namespace {
 
-constexpr int TM = 64;                 // token rows of a tile
-constexpr int TN = 256;                // vocabulary columns of a tile: 64 per wave
+// (TM, TN and the split constants: lexical_proj_layout.h)
 constexpr int BK = 64;                 // columns of H staged per step (128 bytes of a row)
 constexpr int PITCH = 2 * BK + 16;     // LDS pitch of a staged row: the 16-byte reads of 16 consecutive rows fall on 16 different slots
-constexpr int MAX_SPLIT = 16;          // shares of the vocabulary in the statistics pass
-constexpr int FILL_WGS = 1024;         // workgroups the statistics pass wants
 constexpr int GROUP_ROWS = 1024;       // token rows (before masking) a fold workgroup owns at least
+constexpr int MAX_TOKENS = 32767;      // training: tok is int16
+constexpr int MAX_H = 1024;            // training: the widest hidden size whose gradient kernels are built
 
 typedef float float16v __attribute__((ext_vector_type(16)));
 
@@ -420,12 +421,70 @@ __global__ void __launch_bounds__(256) proj_fold_kernel(ProjArgs a) {
   }
 }
 
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+// The operands of a projection head as its entry point received them (n_tokens counts the tokens after the skipped ones; encoding skips none).
+struct ProjOperands {
+  int32_t mem_kind; const void* hidden; int32_t value_dtype; int64_t batch; int32_t n_tokens, skip_tokens, hidden_dim; int64_t ld_batch, ld_token;
+  const void* weight; int32_t vocab; int64_t ld_weight; const void* bias; int32_t bias_dtype;
+  const float* term_weights; int64_t ld_weights; const float* mask; int64_t ld_mask;
+  void* workspace; int64_t workspace_bytes;
+};
 
-// shares of the vocabulary in the statistics pass: enough workgroups to fill the chip when there are few token rows
-inline int proj_stats_split(int64_t BT, int n_ntiles) {
-  const int64_t m_tiles = std::max<int64_t>(1, (BT + TM - 1) / TM);
-  return (int)std::min<int64_t>(std::min<int64_t>(MAX_SPLIT, n_ntiles), std::max<int64_t>(1, (FILL_WGS + m_tiles - 1) / m_tiles));
+// The operand rules of the three entry points, before anything is dereferenced.  `what` prefixes the messages.  The training calls
+// (train = true) add the limits of their kernels and answer the operand types and host memory last; the encoding call refuses everything but
+// device memory at once and answers the operand types before the sizes.  more_dtypes_ok / more_sizes_ok: the caller's own arguments that
+// answer with the same two messages (the record's value dtype and cls_dim of the encoding call).
+inline int check_operands(const char* what, bool train, const ProjOperands& o, bool more_dtypes_ok = true, bool more_sizes_ok = true) {
+  auto operand_types = [&]() -> int {
+    if (o.value_dtype == DHR_VAL_F32) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden states and weight must be fp16 or bf16");
+    if (o.bias && o.bias_dtype == DHR_VAL_BF16 && o.value_dtype == DHR_VAL_F16)
+      return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": a bf16 bias needs bf16 hidden states and weight (the fp16 kernels read fp32 or fp16)");
+    return DHR_OK;
+  };
+  if (!o.hidden || !o.weight || !o.term_weights || !o.mask) return set_error(DHR_ERR_INVALID, "null pointer");
+  if (train && !DHR_MEM_KIND_OK(o.mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
+  if (!train && o.mem_kind != DHR_MEM_DEVICE) return set_error(DHR_ERR_INVALID, std::string(what) + ": device memory only");
+  if (!val_ok_bf16(o.value_dtype) || (o.bias && !val_ok_bf16(o.bias_dtype)) || !more_dtypes_ok) return set_error(DHR_ERR_INVALID, "bad value dtype");
+  if (!train)
+    if (int rc = operand_types()) return rc;
+  const int64_t L = (int64_t)o.n_tokens + o.skip_tokens;
+  if (o.batch < 0 || o.n_tokens <= 0 || o.vocab <= 0 || o.hidden_dim <= 0 || o.skip_tokens < 0 || o.skip_tokens > MAX_TOKENS ||
+      o.ld_token < o.hidden_dim || o.ld_batch < (L - 1) * o.ld_token + o.hidden_dim || o.ld_weight < o.hidden_dim || o.ld_weights < o.n_tokens ||
+      o.ld_mask < o.n_tokens || !more_sizes_ok || o.workspace_bytes < 0 || o.batch * L > ((int64_t)1 << 31) - 1)
+    return set_error(DHR_ERR_INVALID, "bad sizes / strides");
+  if (o.hidden_dim % 8) return set_error(DHR_ERR_INVALID, "the hidden size must be a multiple of 8");
+  if (!train) return DHR_OK;
+  if (o.n_tokens > MAX_TOKENS) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 tokens (the token index is int16)");
+  if (o.hidden_dim > MAX_H) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden sizes above 1024 are not built");
+  if (int rc = operand_types()) return rc;
+  if (o.mem_kind != DHR_MEM_DEVICE)
+    return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": host arrays are not staged, training tensors live on the device (DHR_MEM_DEVICE)");
+  return DHR_OK;
+}
+
+// the workspace rule of the three entry points; size_fn names the function that returns `total`
+inline int check_workspace(const char* size_fn, int64_t total, const ProjOperands& o) {
+  if (!o.workspace || o.workspace_bytes < total)
+    return set_error(DHR_ERR_INVALID, std::string("workspace is smaller than ") + size_fn + " (" + std::to_string(total) + " bytes)");
+  if ((uintptr_t)o.workspace % 16) return set_error(DHR_ERR_INVALID, "workspace must be aligned to 16 bytes");
+  return DHR_OK;
+}
+
+// ProjArgs of the operands and the shared sections of the workspace; the caller adds its outputs (reps, and tok / pwin when training)
+inline ProjArgs proj_args(const ProjLayout& l, const ProjOperands& o) {
+  char* ws = (char*)o.workspace;
+  ProjArgs a{};
+  a.hid = (const _Float16*)o.hidden + (int64_t)o.skip_tokens * o.ld_token; a.ld_hb = o.ld_batch; a.ld_ht = o.ld_token;
+  a.wgt = (const _Float16*)o.weight; a.ld_w = o.ld_weight;
+  a.bias = o.bias; dtype_flags(o.bias_dtype, a.bias_f32, a.bias_f16);
+  a.tw = o.term_weights; a.ld_tw = o.ld_weights; a.mask = o.mask; a.ld_mask = o.ld_mask;
+  a.B = o.batch; a.T = o.n_tokens; a.H = o.hidden_dim; a.V = o.vocab;
+  a.vec_h = (uintptr_t)a.hid % 16 == 0 && o.ld_batch % 8 == 0 && o.ld_token % 8 == 0;
+  a.vec_w = (uintptr_t)o.weight % 16 == 0 && o.ld_weight % 8 == 0;
+  a.n_split = l.n_split; a.n_ntiles = l.n_ntiles;
+  a.group = (int)std::max<int64_t>((GROUP_ROWS + o.n_tokens - 1) / o.n_tokens, (o.batch + 65534) / 65535);
+  a.hdr = (int*)(ws + l.hdr); a.cnt = (int*)(ws + l.cnt); a.start = (int*)(ws + l.start); a.tmask = (int*)(ws + l.tmask);
+  a.rows = (int*)(ws + l.rows); a.stats = (float4*)(ws + l.stats); a.part = (float2*)(ws + l.part);
+  return a;
 }
 
 // the forward of both heads on a filled ProjArgs: compaction of the unmasked rows, statistics, combine, fold (TRAIN: with tok and pwin).

@@ -24,7 +24,6 @@
 // (16 per 64 columns of H: 192 at H = 768; a wider H is cut into two slabs, each of which computes x again).  One workgroup owns its rows of the output: no atomics, no float atomics
 // anywhere, every sum in a fixed order -- two runs are bit-identical.  dbias is the fp32 sum of the unrounded dx.
 // Everything is enqueued on the caller's stream; nothing is allocated.  NaN / inf inputs are out of scope.
-#include "host_stage.h"
 #include "op_dispatch.h"
 #include "lexical_proj_common.h"
 
@@ -33,10 +32,7 @@ namespace {
 constexpr int RT_BIG = 16;             // tokens per workgroup of the route sums ...
 constexpr int RT_SMALL = 4;            // ... and where 16 would leave most of the chip without a workgroup
 constexpr int DXP = 2 * TN + 16;       // LDS pitch of a row of the dx image [resident 64][walked 256] of E
-constexpr int MAX_TOKENS = 32767;      // tok is int16
-constexpr int MAX_H = 1024;
 constexpr int MAX_CHUNKS = 12;         // 64-column chunks of H whose output accumulators fit the registers: 16 registers per chunk
-constexpr int SPLIT_WGS = 256;         // pass 2 splits the vocabulary into shares where the worst-case list has fewer 64-row tiles than half of this
 
 struct GradArgs {
   const float* g;                      // dL/dreps [B, V]
@@ -340,81 +336,6 @@ __global__ void __launch_bounds__(256) proj_grad_combine_kernel(ProjArgs a, Grad
   store_out<E>(q.out, q.out_f32, q.out_f16, (int64_t)b * q.ld_ob + (int64_t)t * q.ld_ot + col, (float)s);
 }
 
-struct Layout {
-  int64_t hdr, cnt, start, tmask, rows, stats, part, D, partial, total;
-  int n_split, n_ntiles, grad_split;
-};
-
-Layout layout(int64_t B, int T, int V, int H) {
-  Layout l{};
-  const int64_t BT = B * T;
-  l.n_ntiles = (V + TN - 1) / TN;
-  l.n_split = proj_stats_split(BT, l.n_ntiles);
-  const int64_t m_tiles = std::max<int64_t>(1, (BT + TM - 1) / TM);
-  l.grad_split = (int)std::min<int64_t>(std::min<int64_t>(MAX_SPLIT, l.n_ntiles), std::max<int64_t>(1, SPLIT_WGS / m_tiles));
-  int64_t at = 0;
-  l.hdr = at; at += 256;
-  l.cnt = at; at = align256(at + 4 * B);
-  l.start = at; at = align256(at + 4 * (B + 1));
-  l.tmask = at; at = align256(at + 4 * B);
-  l.rows = at; at = align256(at + 4 * BT);
-  l.stats = at; at = align256(at + 16 * BT);
-  l.part = at; at = align256(at + 8 * BT * l.n_split);
-  l.D = at; at = align256(at + 4 * BT);
-  l.partial = at;
-  if (l.grad_split > 1) at = align256(at + 4 * BT * H * l.grad_split);
-  l.total = at;
-  return l;
-}
-
-// the checks the forward and the backward share, before anything is dereferenced.  n_tokens counts the tokens after the skipped ones.
-int check_common(const char* what, int32_t mem_kind, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens, int32_t skip_tokens,
-                 int32_t hidden_dim, int64_t ld_batch, int64_t ld_token, const void* weight, int32_t vocab, int64_t ld_weight, const void* bias,
-                 int32_t bias_dtype, const float* term_weights, int64_t ld_weights, const float* mask, int64_t ld_mask, int64_t workspace_bytes) {
-  if (!hidden || !weight || !term_weights || !mask) return set_error(DHR_ERR_INVALID, "null pointer");
-  if (!DHR_MEM_KIND_OK(mem_kind)) return set_error(DHR_ERR_INVALID, "bad mem_kind");
-  if (!val_ok_bf16(value_dtype) || (bias && !val_ok_bf16(bias_dtype))) return set_error(DHR_ERR_INVALID, "bad value dtype");
-  if (batch < 0 || n_tokens <= 0 || vocab <= 0 || hidden_dim <= 0 || skip_tokens < 0 || skip_tokens > MAX_TOKENS || ld_token < hidden_dim ||
-      ld_batch < (int64_t)(n_tokens + skip_tokens - 1) * ld_token + hidden_dim || ld_weight < hidden_dim || ld_weights < n_tokens ||
-      ld_mask < n_tokens || workspace_bytes < 0 || batch * ((int64_t)n_tokens + skip_tokens) > ((int64_t)1 << 31) - 1)
-    return set_error(DHR_ERR_INVALID, "bad sizes / strides");
-  if (hidden_dim % 8) return set_error(DHR_ERR_INVALID, "the hidden size must be a multiple of 8");
-  if (n_tokens > MAX_TOKENS) return set_error(DHR_ERR_UNSUPPORTED, "more than 32767 tokens (the token index is int16)");
-  if (hidden_dim > MAX_H) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden sizes above 1024 are not built");
-  if (value_dtype == DHR_VAL_F32) return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": hidden states and weight must be fp16 or bf16");
-  if (bias && bias_dtype == DHR_VAL_BF16 && value_dtype == DHR_VAL_F16)
-    return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": a bf16 bias needs bf16 hidden states and weight (the fp16 kernels read fp32 or fp16)");
-  if (mem_kind != DHR_MEM_DEVICE)
-    return set_error(DHR_ERR_UNSUPPORTED, std::string(what) + ": host arrays are not staged, training tensors live on the device (DHR_MEM_DEVICE)");
-  return DHR_OK;
-}
-
-int check_workspace(const Layout& l, const void* workspace, int64_t workspace_bytes) {
-  if (!workspace || workspace_bytes < l.total)
-    return set_error(DHR_ERR_INVALID, "workspace is smaller than dhr_lexical_proj_train_workspace (" + std::to_string(l.total) + " bytes)");
-  if ((uintptr_t)workspace % 16) return set_error(DHR_ERR_INVALID, "workspace must be aligned to 16 bytes");
-  return DHR_OK;
-}
-
-ProjArgs proj_args(const Layout& l, const void* hidden, int64_t batch, int32_t n_tokens, int32_t skip_tokens, int32_t hidden_dim, int64_t ld_batch,
-                   int64_t ld_token, const void* weight, int32_t vocab, int64_t ld_weight, const void* bias, int32_t bias_dtype,
-                   const float* term_weights, int64_t ld_weights, const float* mask, int64_t ld_mask, void* workspace) {
-  char* ws = (char*)workspace;
-  ProjArgs a{};
-  a.hid = (const _Float16*)hidden + (int64_t)skip_tokens * ld_token; a.ld_hb = ld_batch; a.ld_ht = ld_token;
-  a.wgt = (const _Float16*)weight; a.ld_w = ld_weight;
-  a.bias = bias; dtype_flags(bias_dtype, a.bias_f32, a.bias_f16);
-  a.tw = term_weights; a.ld_tw = ld_weights; a.mask = mask; a.ld_mask = ld_mask;
-  a.B = batch; a.T = n_tokens; a.H = hidden_dim; a.V = vocab;
-  a.vec_h = (uintptr_t)a.hid % 16 == 0 && ld_batch % 8 == 0 && ld_token % 8 == 0;
-  a.vec_w = (uintptr_t)weight % 16 == 0 && ld_weight % 8 == 0;
-  a.n_split = l.n_split; a.n_ntiles = l.n_ntiles;
-  a.group = (int)std::max<int64_t>((GROUP_ROWS + n_tokens - 1) / n_tokens, (batch + 65534) / 65535);
-  a.hdr = (int*)(ws + l.hdr); a.cnt = (int*)(ws + l.cnt); a.start = (int*)(ws + l.start); a.tmask = (int*)(ws + l.tmask);
-  a.rows = (int*)(ws + l.rows); a.stats = (float4*)(ws + l.stats); a.part = (float2*)(ws + l.part);
-  return a;
-}
-
 // One launch per slab of H: up to MAX_CHUNKS 64-column chunks fit the registers; a wider H (above 768) is cut into equal slabs, each of
 // which computes x again.  dbias belongs to the first slab; where it is all that is wanted (no out), the later slabs have nothing to write.
 template <int PASS>
@@ -437,7 +358,7 @@ extern "C" int64_t dhr_lexical_proj_train_workspace(int64_t batch, int32_t n_tok
   if (batch < 0 || n_tokens <= 0 || n_tokens > MAX_TOKENS || vocab <= 0 || hidden_dim <= 0 || hidden_dim > MAX_H || hidden_dim % 8 ||
       batch * n_tokens > ((int64_t)1 << 31) - 1)
     return 0;
-  return layout(batch, n_tokens, vocab, hidden_dim).total;
+  return proj_train_layout(batch, n_tokens, vocab, hidden_dim).total;
 } DHR_CATCH_VALUE(0)
 
 extern "C" int dhr_lexical_proj_train(int32_t device, int32_t mem_kind, const void* hidden, int32_t value_dtype, int64_t batch, int32_t n_tokens,
@@ -447,18 +368,18 @@ extern "C" int dhr_lexical_proj_train(int32_t device, int32_t mem_kind, const vo
                                       float* out_pwin, int64_t ld_pwin, void* workspace, int64_t workspace_bytes, void* stream) try {
   dhr::alloc_checkpoint();
   if (!out_reps || !out_tokens || !out_pwin) return set_error(DHR_ERR_INVALID, "null pointer");
-  int rc = check_common("dhr_lexical_proj_train", mem_kind, hidden, value_dtype, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token, weight,
-                        vocab, ld_weight, bias, bias_dtype, term_weights, ld_weights, mask, ld_mask, workspace_bytes);
+  const ProjOperands o{mem_kind, hidden, value_dtype, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token, weight, vocab, ld_weight, bias,
+                       bias_dtype, term_weights, ld_weights, mask, ld_mask, workspace, workspace_bytes};
+  int rc = check_operands("dhr_lexical_proj_train", true, o);
   if (rc) return rc;
   if (ld_reps < vocab || ld_tokens < vocab || ld_pwin < vocab) return set_error(DHR_ERR_INVALID, "bad sizes / strides");
   if (batch == 0) return DHR_OK;
-  const Layout l = layout(batch, n_tokens, vocab, hidden_dim);
-  rc = check_workspace(l, workspace, workspace_bytes);
+  const ProjTrainLayout l = proj_train_layout(batch, n_tokens, vocab, hidden_dim);
+  rc = check_workspace("dhr_lexical_proj_train_workspace", l.total, o);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  ProjArgs a = proj_args(l, hidden, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token, weight, vocab, ld_weight, bias, bias_dtype,
-                         term_weights, ld_weights, mask, ld_mask, workspace);
+  ProjArgs a = proj_args(l, o);
   a.reps = out_reps; a.ld_reps = ld_reps;
   a.tok = out_tokens; a.ld_tok = ld_tokens;
   a.pwin = out_pwin; a.ld_pwin = ld_pwin;
@@ -477,8 +398,9 @@ extern "C" int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const
                                          int32_t grad_bias_dtype, float* grad_term_weights, int64_t ld_grad_term_weights, void* stream) try {
   dhr::alloc_checkpoint();
   if (!grad_reps || !tokens || !pwin) return set_error(DHR_ERR_INVALID, "null pointer");
-  int rc = check_common("dhr_lexical_proj_backward", mem_kind, hidden, value_dtype, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token,
-                        weight, vocab, ld_weight, bias, bias_dtype, term_weights, ld_weights, mask, ld_mask, workspace_bytes);
+  const ProjOperands o{mem_kind, hidden, value_dtype, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token, weight, vocab, ld_weight, bias,
+                       bias_dtype, term_weights, ld_weights, mask, ld_mask, workspace, workspace_bytes};
+  int rc = check_operands("dhr_lexical_proj_backward", true, o);
   if (rc) return rc;
   if ((grad_hidden && !val_ok_bf16(grad_hidden_dtype)) || (grad_weight && !val_ok_bf16(grad_weight_dtype)) ||
       (grad_bias && !val_ok_bf16(grad_bias_dtype)))
@@ -491,13 +413,12 @@ extern "C" int dhr_lexical_proj_backward(int32_t device, int32_t mem_kind, const
       (grad_hidden && (ld_grad_token < hidden_dim || ld_grad_batch < (int64_t)(n_tokens + skip_tokens - 1) * ld_grad_token + hidden_dim)))
     return set_error(DHR_ERR_INVALID, "bad sizes / strides");
   if (batch == 0 || (!grad_hidden && !grad_weight && !grad_bias && !grad_term_weights)) return DHR_OK;
-  const Layout l = layout(batch, n_tokens, vocab, hidden_dim);
-  rc = check_workspace(l, workspace, workspace_bytes);
+  const ProjTrainLayout l = proj_train_layout(batch, n_tokens, vocab, hidden_dim);
+  rc = check_workspace("dhr_lexical_proj_train_workspace", l.total, o);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  const ProjArgs a = proj_args(l, hidden, batch, n_tokens, skip_tokens, hidden_dim, ld_batch, ld_token, weight, vocab, ld_weight, bias, bias_dtype,
-                               term_weights, ld_weights, mask, ld_mask, workspace);
+  const ProjArgs a = proj_args(l, o);
   const int T = n_tokens;
   const int64_t BT = batch * T;
   float* D = (float*)((char*)workspace + l.D);

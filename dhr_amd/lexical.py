@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lexical_args as A
 from . import _lib
 from . import _marshal as M
 
@@ -74,46 +75,28 @@ def _inputs(logits, term_weights, attention_mask):
         raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / bfloat16 / float32)")
     if M.dtype_name(logits) == "bfloat16" and (M.is_np(logits) or not logits.is_cuda):
         raise _lib.DhrError("lexical head: bfloat16 logits must live on a GPU (the staged host path serves numpy arrays, which have no bfloat16)")
-    if M.is_np(logits):
-        w = np.ascontiguousarray(np.asarray(term_weights).reshape(B, T), dtype=np.float32)
-        m = np.ascontiguousarray(np.asarray(attention_mask).reshape(B, T), dtype=np.float32)
-    else:
-        import torch
+    w, m = A.tokens_f32(term_weights, B, T, logits), A.tokens_f32(attention_mask, B, T, logits)
+    if not M.is_np(logits):
         logits = logits.detach()
-        w = term_weights.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
-        m = attention_mask.detach().reshape(B, T).to(device=logits.device, dtype=torch.float32).contiguous()
     logits, (ldb, ldt) = M.as_read(logits)
     return logits, ldb, ldt, w, m, B, T, V
+
+
+def _wrong_kind(name):
+    return _lib.DhrError("lexical head: semantic reps must live in the same memory kind as the logits" if name == "semantic_reps" else
+                         "lexical head: inputs and outputs must live in the same memory kind")
 
 
 def _run(mode, logits, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps):
     lg, ldb, ldt, w, m, B, T, V = _inputs(logits, term_weights, attention_mask)     # (its dtype checks come before the library is touched)
     lib = _lib.load()
     kind = M.mem_kind(lg)
-    p_v, ld_v, kind_v = _lib._ptr_ld(value_out)
-    if kind_v != kind:
-        raise _lib.DhrError("lexical head: inputs and outputs must live in the same memory kind")
-    p_i, ld_i, idx_dt = None, 0, _lib.IDX_NONE
-    if index_out is not None:
-        p_i, ld_i, kind_i = _lib._ptr_ld(index_out)
-        if kind_i != kind:
-            raise _lib.DhrError("lexical head: inputs and outputs must live in the same memory kind")
-        idx_dt = _lib.idx_code(index_out.dtype)
-    p_c, ld_c, c_dt, c_dim, keep = None, 0, _lib.VAL_F16, 0, None
-    if semantic_reps is not None:
-        c = M.values(semantic_reps if M.is_np(semantic_reps) else semantic_reps.detach())
-        p_c, ld_c, kind_c = _lib._ptr_ld(c)
-        if kind_c != kind:
-            raise _lib.DhrError("lexical head: semantic reps must live in the same memory kind as the logits")
-        if int(c.shape[0]) != B:
-            raise ValueError("semantic reps do not match the batch")
-        c_dt, c_dim, keep = _lib._val_code(c), int(c.shape[1]), c
+    (p_v, ld_v), record, _keep = A.record_outputs(value_out, index_out, semantic_reps, B, kind, _wrong_kind)     # (_keep: converted semantic reps)
     if B:
         ws = M.empty(lg, B * T * 16, "uint8") if kind == _lib.MEM_DEVICE else None
         _lib.check(lib.dhr_lexical_head(M.device(lg), kind, mode, M.data_ptr(lg), _lib._val_code(lg, bf16=True), B, T, V, ldb, ldt, M.data_ptr(w), T,
-                                        M.data_ptr(m), T, dims, remove_dims, p_v, _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt,
-                                        ld_c, c_dim, M.data_ptr(ws), M.stream(lg)), "dhr_lexical_head")
-    del keep
+                                        M.data_ptr(m), T, dims, remove_dims, p_v, _lib._val_code(value_out), ld_v, *record, M.data_ptr(ws), M.stream(lg)),
+                   "dhr_lexical_head")
     return B, V
 
 

@@ -19,14 +19,19 @@ Torch CUDA tensors only: the op runs on their device, enqueues on the current st
 DhrError: there is no staged host path and no CPU implementation."""
 from __future__ import annotations
 
+from . import _lexical_args as A
 from . import _lib
 from . import _marshal as M
 from .lexical import _agg_geometry, _check_out, _densify_check
 
 
+def _not_on_gpu(name):
+    return _lib.DhrError(f"lexical projection head: {name} must be a torch tensor on the GPU (there is no host path)")
+
+
 def _on_gpu(name, a):
-    if not hasattr(a, "is_cuda") or not a.is_cuda:
-        raise _lib.DhrError(f"lexical projection head: {name} must be a torch tensor on the GPU (there is no host path)")
+    if not getattr(a, "is_cuda", False):
+        raise _not_on_gpu(name)
 
 
 def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, index_out, dims, remove_dims, semantic_reps):
@@ -51,40 +56,22 @@ def _run(mode, hidden, weight, bias, term_weights, attention_mask, value_out, in
     if weight.device != dev:
         raise _lib.DhrError("lexical projection head: hidden and weight must live on the same GPU")
     weight, (ld_weight,) = M.as_read(weight.detach())
-    p_b, b_dt = None, _lib.VAL_F32
     if bias is not None:
         _on_gpu("bias", bias)
         if bias.dtype not in (torch.float16, torch.bfloat16, torch.float32):
             raise _lib.DhrError(f"unsupported bias dtype {bias.dtype} (float16 / bfloat16 / float32)")
         if bias.dim() != 1 or int(bias.shape[0]) != V:
             raise ValueError("bias does not match the vocabulary")
-        bias = bias.detach().to(dev).contiguous()
-        if bias.dtype == torch.bfloat16 and hidden.dtype == torch.float16:       # the fp16 kernels read fp32 or fp16: [V] values, widened exactly
-            bias = bias.float()
-        p_b, b_dt = bias.data_ptr(), _lib._val_code(bias, bf16=True)
-    w = term_weights.detach().reshape(B, T).to(device=dev, dtype=torch.float32).contiguous()
-    m = attention_mask.detach().reshape(B, T).to(device=dev, dtype=torch.float32).contiguous()
-    p_v, ld_v, _ = _lib._ptr_ld(value_out)
-    p_i, ld_i, idx_dt = None, 0, _lib.IDX_NONE
-    if index_out is not None:
-        _on_gpu("index_out", index_out)
-        p_i, ld_i, _ = _lib._ptr_ld(index_out)
-        idx_dt = _lib.idx_code(index_out.dtype)
-    p_c, ld_c, c_dt, c_dim, c = None, 0, _lib.VAL_F16, 0, None
-    if semantic_reps is not None:
-        _on_gpu("semantic_reps", semantic_reps)
-        c = M.values(semantic_reps.detach())
-        p_c, ld_c, _ = _lib._ptr_ld(c)
-        if int(c.shape[0]) != B:
-            raise ValueError("semantic reps do not match the batch")
-        c_dt, c_dim = _lib._val_code(c), int(c.shape[1])
+    bias = A.bias_as_read(bias, hidden.dtype, dev)
+    b_dt = _lib.VAL_F32 if bias is None else _lib._val_code(bias, bf16=True)
+    w, m = A.tokens_f32(term_weights, B, T, hidden), A.tokens_f32(attention_mask, B, T, hidden)
+    (p_v, ld_v), record, _keep = A.record_outputs(value_out, index_out, semantic_reps, B, _lib.MEM_DEVICE, _not_on_gpu)  # (_keep: converted semantic reps)
     if B:
         n_ws = int(lib.dhr_lexical_proj_workspace(B, T, V, mode))
         ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
         _lib.check(lib.dhr_lexical_proj_head(M.device(hidden), _lib.MEM_DEVICE, mode, hidden.data_ptr(), _lib._val_code(hidden, bf16=True), B, T, H, ld_batch, ld_token,
-                                             weight.data_ptr(), V, ld_weight, p_b, b_dt, w.data_ptr(), T, m.data_ptr(), T, dims, remove_dims, p_v,
-                                             _lib._val_code(value_out), ld_v, p_i, idx_dt, ld_i, p_c, c_dt, ld_c, c_dim, ws.data_ptr(), n_ws,
-                                             M.stream(hidden)), "dhr_lexical_proj_head")
+                                             weight.data_ptr(), V, ld_weight, M.data_ptr(bias), b_dt, w.data_ptr(), T, m.data_ptr(), T, dims, remove_dims, p_v,
+                                             _lib._val_code(value_out), ld_v, *record, ws.data_ptr(), n_ws, M.stream(hidden)), "dhr_lexical_proj_head")
         # (the call is asynchronous; the temporaries were allocated on the stream it runs on, so the allocator reuses them only behind it)
     return B, V
 

@@ -29,6 +29,7 @@ stream of `hidden`'s device, without a host synchronisation; buffers come from t
 tensors that autograd hands back, so saved-tensor hooks (`save_on_cpu`, non-reentrant checkpointing) work.  There is no CPU implementation."""
 from __future__ import annotations
 
+from . import _lexical_args as A
 from . import _lib
 from . import _marshal as M
 
@@ -48,20 +49,11 @@ def _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens):
     if weight.dim() != 2 or int(weight.shape[1]) != H:
         raise ValueError('weight must be [vocab, hidden size {}], got {}'.format(H, tuple(weight.shape)))
     V = int(weight.shape[0])
-    if skip_tokens < 0:
-        raise ValueError('skip_tokens must be >= 0, got {}'.format(skip_tokens))
-    T = L - skip_tokens
-    if T <= 0:
-        raise ValueError('no tokens: the maximum over tokens of an empty sequence is undefined ({} tokens, {} skipped)'.format(L, skip_tokens))
     if V == 0 or H == 0:
         raise ValueError('weight has no rows or no columns')
     if bias is not None and (bias.dim() != 1 or int(bias.shape[0]) != V):
         raise ValueError("bias does not match the vocabulary")
-    for a, what in ((term_weights, "term_weights"), (attention_mask, "attention_mask")):
-        if tuple(a.shape) not in ((B, T), (B, T, 1)):
-            raise ValueError('{} must be [{}, {}] or [{}, {}, 1] (batch, tokens - skip_tokens), got {}'.format(what, B, T, B, T, tuple(a.shape)))
-    if T > MAX_TOKENS:
-        raise ValueError('more than {} tokens'.format(MAX_TOKENS))
+    T = A.check_token_side(term_weights, attention_mask, B, L, skip_tokens, MAX_TOKENS)
     ok = (torch.float16, torch.bfloat16, torch.float32)
     if hidden.dtype not in ok or weight.dtype not in ok:
         raise _lib.DhrError(f"unsupported hidden / weight dtype {hidden.dtype} / {weight.dtype} (float16 / bfloat16 / float32)")
@@ -69,8 +61,6 @@ def _check(hidden, weight, bias, term_weights, attention_mask, skip_tokens):
         raise _lib.DhrError(f"hidden / weight dtype {hidden.dtype} / {weight.dtype}: one float16 and one bfloat16 operand have no common 16-bit type")
     if bias is not None and bias.dtype not in ok:
         raise _lib.DhrError(f"unsupported bias dtype {bias.dtype} (float16 / bfloat16 / float32)")
-    if not term_weights.dtype.is_floating_point:
-        raise _lib.DhrError(f"unsupported term_weights dtype {term_weights.dtype} (a floating-point dtype)")
     if H % 8 or H > MAX_HIDDEN:
         raise _lib.DhrError(f"lexical_proj_train.lexical_reps: the hidden size {H} is not a multiple of 8 up to {MAX_HIDDEN}")
     if not hidden.is_cuda:
@@ -113,11 +103,8 @@ def _function():
             dev = hidden.device
             op = _operand_dtype(hidden, weight)
             h, W = _rows16(hidden, op), _rows16(weight, op)
-            b = None if bias is None else bias.detach().contiguous()
-            if b is not None and M.dtype_name(b) == "bfloat16" and op == "float16":  # the fp16 kernels read fp32 or fp16: [V] values, widened exactly
-                b = b.float()
-            w = term_weights.detach().reshape(B, T).to(torch.float32).contiguous()
-            m = attention_mask.detach().reshape(B, T).to(torch.float32).contiguous()
+            b = A.bias_as_read(bias, op, dev)
+            w, m = A.tokens_f32(term_weights, B, T), A.tokens_f32(attention_mask, B, T)
             reps = torch.empty((B, V), dtype=torch.float32, device=dev)
             tok = torch.empty((B, V), dtype=torch.int16, device=dev)
             pwin = torch.empty((B, V), dtype=torch.float32, device=dev)

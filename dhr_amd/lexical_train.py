@@ -27,6 +27,7 @@ run in a fixed order: two runs on the same inputs are bit-identical.  Everything
 device, without a host synchronisation; buffers come from torch's allocator.  There is no CPU implementation: without a GPU the call raises."""
 from __future__ import annotations
 
+from . import _lexical_args as A
 from . import _lib
 from . import _marshal as M
 
@@ -41,22 +42,11 @@ def _check(logits, term_weights, attention_mask, skip_tokens):
     if logits.dim() != 3:
         raise ValueError('logits must be [batch, tokens, vocab], got {} dimensions'.format(logits.dim()))
     B, L, V = (int(d) for d in logits.shape)
-    if skip_tokens < 0:
-        raise ValueError('skip_tokens must be >= 0, got {}'.format(skip_tokens))
-    T = L - skip_tokens
-    if T <= 0:
-        raise ValueError('no tokens: the maximum over tokens of an empty sequence is undefined ({} tokens, {} skipped)'.format(L, skip_tokens))
     if V == 0:
         raise ValueError('logits have no vocabulary columns')
-    for a, what in ((term_weights, "term_weights"), (attention_mask, "attention_mask")):
-        if tuple(a.shape) not in ((B, T), (B, T, 1)):
-            raise ValueError('{} must be [{}, {}] or [{}, {}, 1] (batch, tokens - skip_tokens), got {}'.format(what, B, T, B, T, tuple(a.shape)))
-    if T > MAX_TOKENS:
-        raise ValueError('more than {} tokens'.format(MAX_TOKENS))
+    T = A.check_token_side(term_weights, attention_mask, B, L, skip_tokens, MAX_TOKENS)
     if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
         raise _lib.DhrError(f"unsupported logits dtype {logits.dtype} (float16 / bfloat16 / float32)")
-    if not term_weights.dtype.is_floating_point:
-        raise _lib.DhrError(f"unsupported term_weights dtype {term_weights.dtype} (a floating-point dtype)")
     if not logits.is_cuda:
         raise _lib.DhrError("lexical_train.lexical_reps: the logits must live on a GPU (there is no CPU implementation)")
     if term_weights.device != logits.device or attention_mask.device != logits.device:
@@ -77,8 +67,7 @@ def _function():
             B, L, T, V = _check(logits, term_weights, attention_mask, skip_tokens)
             lib = _lib.load()
             x, (ld_batch, ld_token) = M.as_read(logits.detach())
-            w = term_weights.detach().reshape(B, T).to(torch.float32).contiguous()
-            m = attention_mask.detach().reshape(B, T).to(torch.float32).contiguous()
+            w, m = A.tokens_f32(term_weights, B, T), A.tokens_f32(attention_mask, B, T)
             reps = torch.empty((B, V), dtype=torch.float32, device=x.device)
             tok = torch.empty((B, V), dtype=torch.int16, device=x.device)
             ws = torch.empty((int(lib.dhr_lexical_head_train_workspace(B, T)) if B else 0,), dtype=torch.uint8, device=x.device)

@@ -304,6 +304,26 @@ int dhr_merge_topk_lists_host(int32_t n_queries, int32_t n_lists, int32_t list_l
 int dhr_densify(int32_t device, int32_t mem_kind, const void* lexical, int32_t value_dtype, int64_t ld, int64_t batch, int32_t vocab,
                 int32_t remove_dims, int32_t dims, void* out_value, int32_t out_value_dtype, int64_t ld_value, void* out_index,
                 int32_t index_dtype, int64_t ld_index, void* stream);
+/* Densify of SPARSE term-weight vectors, the producer of the BM25 / DeepImpact / uniCOIL / SPLADE indexes (densify/densify_corpus.py:29-52,
+ * densify/densify_query.py:96).  The vectors come as CSR: the entries of vector b are [row_ptr[b], row_ptr[b + 1]) of term_ids (id_bytes 4: int32,
+ * 8: int64) and weights (weight_dtype DHR_VAL_F16 or DHR_VAL_F32), nnz entries in all.  Per vector the entries (t, w) are folded IN THE ORDER
+ * GIVEN, with r = fp16(w) rounded once to nearest even, s = (t - omission) % dims, g = (t - omission) / dims:
+ *   value[s] == 0 (+0.0 or -0.0):  value[s] = r, index[s] = g          (so an entry that rounds to zero sets the index and leaves the slice empty)
+ *   otherwise:                      a collision; value[s] = r, index[s] = g if value[s] < r, compared in fp16
+ * bit for bit what the reference leaves with NumPy >= 2.  Entries with t < omission, t < 0 or t >= vocab are skipped and not counted; no term id
+ * is used as an address.  Row ranges are clamped to [0, nnz]; a row whose end lies before its start is empty.  NaN weights are not covered.
+ *   out_value [batch, dims]   DHR_VAL_F16, or DHR_VAL_F32 holding the fp16-rounded value; row stride ld_value >= dims
+ *   out_index [batch, dims]   DHR_IDX_I8 (the reference's dtype without whole-word matching), DHR_IDX_U8 or DHR_IDX_I16 (with it); ld_index >= dims
+ *   collisions [batch]        int32, may be NULL
+ * Every output row is written whole, zeros included, straight into the caller's record arrays.  DHR_ERR_INVALID for a null pointer (term_ids and
+ * weights may be NULL when nnz is 0), a bad mem_kind or dtype code, negative sizes, omission outside [0, vocab), dims <= 0, strides below dims,
+ * and when the largest group (vocab - 1 - omission) / dims does not fit index_dtype (the reference raises OverflowError when it meets such a
+ * term); DHR_ERR_UNSUPPORTED for dims > 8192.  batch == 0 returns DHR_OK without touching a device.  All arrays live in mem_kind memory.  Device
+ * arrays: the call ENQUEUES on `stream` and returns without waiting; host arrays are staged through the device and are complete on return. */
+int dhr_densify_sparse(int32_t device, int32_t mem_kind, const int64_t* row_ptr, const void* term_ids, int32_t id_bytes, const void* weights,
+                       int32_t weight_dtype, int64_t nnz, int64_t batch, int64_t vocab, int32_t omission, int32_t dims, void* out_value,
+                       int32_t out_value_dtype, int64_t ld_value, void* out_index, int32_t index_dtype, int64_t ld_index, int32_t* collisions,
+                       void* stream);
 
 /* The lexical head of the encoders fused with the step after it (tevatron/DHR/modeling.py:297-300,328-331,
  * tevatron/Aggretriever/modeling.py:274-278,306-310; then densify or aggregate and the fp16 casts of tevatron/driver/encode.py:149-194).

@@ -555,6 +555,26 @@ extern "C" int dhr_debug_query_margins(dhr_index* ix, const dhr_query_batch* qb,
   return DHR_OK;
 } DHR_CATCH_STATUS
 
+// Test hook: how the main pass of the latest dhr_search on this handle seated its batch (seating.h).  Returns 1 and fills the host arrays ([n_slots] each,
+// n_slots = the batch's query count rounded up to 256; any may be null) when that pass ran seated: slot -> query, query -> slot, the bound-list
+// lengths of the sampled run the order was taken from, the slot-ordered threshold mirror and the thresholds themselves as the pass left them.
+// Returns 0, and copies nothing, when every query sat where the caller put it.
+extern "C" int dhr_debug_query_seating(dhr_index* ix, int32_t n_slots, int32_t* slot_q, int32_t* q_slot, uint32_t* lengths, float* thr_seat, float* thr_hat) try {
+  if (!ix) return set_error(DHR_ERR_INVALID, "null index");
+  HIP_TRY(hipSetDevice(ix->device));
+  const Workspace& w = ix->ws;
+  if (!w.seated || !w.seat_rec) return 0;
+  if (n_slots != w.q_pad) return set_error(DHR_ERR_INVALID, "n_slots must be the padded query count of the latest search");
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t b = (size_t)n_slots * 4;
+  if (slot_q) HIP_TRY(hipMemcpy(slot_q, w.slot_q(), b, hipMemcpyDeviceToHost));
+  if (q_slot) HIP_TRY(hipMemcpy(q_slot, w.q_slot(), b, hipMemcpyDeviceToHost));
+  if (lengths) HIP_TRY(hipMemcpy(lengths, w.seat_len, b, hipMemcpyDeviceToHost));
+  if (thr_seat) HIP_TRY(hipMemcpy(thr_seat, w.thr_seat(), b, hipMemcpyDeviceToHost));
+  if (thr_hat) HIP_TRY(hipMemcpy(thr_hat, w.thr_hat, b, hipMemcpyDeviceToHost));
+  return 1;
+} DHR_CATCH_STATUS
+
 // Kernel-tuning hook: the bound GEMM alone over the whole shard with the filter closed (thr = +inf),
 // `iters` launches, average milliseconds per launch (hipEvents on the stream).
 extern "C" void dhr_debug_seq_to_tile(int64_t seq, int32_t map_mode, int32_t period, int64_t head, int64_t perm_mul, int64_t perm_n, int64_t out[2]) try {

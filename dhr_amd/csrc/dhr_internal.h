@@ -162,6 +162,9 @@ struct GemmArgs {
   const int32_t* g8_rsum;     // gated_i8: [n_tiles * 256] 128 x (sum of the row's gated int8 values): the accumulators START there, which pays for the
                               // query operand being stored as level - 128 (8 bits of query resolution instead of 7)
   int partial_wn;             // gemm_g8.hip: > 0 = the batch's last query tile holds real queries in its first partial_wn (1 or 2) 64-query wave columns only (set by launch_gemm_g8)
+  int seat;                   // gemm_g8.hip: > 0 = a SEATED launch (search_core.hip main pass): b_tiles, i8_mul, g8_shift and thr are in slot order, and the
+                              // slot -> query words of the batch lie `seat` words behind thr[0] (one record, no further pointer: see `tier`); the kernel
+                              // takes the query number of a list from there.  0: slot = query
   uint32_t* p_ctr;            // gemm_g8p.hip (persistent workgroups): this launch's 8 per-XCD tile counters, zeroed on the stream before the launch (set by launch_gemm_g8p)
   int64_t p_groups;           //   corpus tile groups of the launch, ceil((seq_hi - seq_lo) / DOC_GROUP)
   const float* i8_mul;        // [Q_pad] or null.  Non-null: the td dense stages hold int8 columns (64 per stage); the kernel runs them
@@ -386,7 +389,7 @@ hipError_t launch_plan_overflow(const uint32_t* cnt_prev, double rows_ratio, uin
 hipError_t launch_max_u32(const uint32_t* v, int n, uint32_t* out_max, unsigned long long* out_sum, hipStream_t s);
 hipError_t launch_lists_ready(const uint32_t* cnt, uint32_t cap, int n_queries, uint32_t per, uint32_t* offs, uint32_t* out_max, uint32_t* out_max2,
                               unsigned long long* out_sum, unsigned long long* out_sum2, uint32_t* fail_flags, uint32_t* zero, int n_zero,
-                              hipStream_t s, const uint32_t* ovf_cap = nullptr);
+                              hipStream_t s, const uint32_t* ovf_cap = nullptr, uint32_t* seat_len = nullptr /* [n_queries] += cnt: seating.h */);
 hipError_t launch_rows_to_local(const int64_t* rows, int64_t n, int64_t row_offset, int64_t n_rows, uint32_t* out,
                                 hipStream_t s);
 hipError_t launch_mark_overflow(const uint32_t* cnt, uint32_t cap, int n_queries, uint32_t* fail_flags, hipStream_t s);
@@ -400,6 +403,15 @@ hipError_t launch_make_thr(const float* tau, const float* margin, int n_queries,
 hipError_t launch_raise_thr(float* thr_hat, const float* thr_run, int n_queries, hipStream_t s);
 hipError_t launch_flag_tau_above(const float* tau_own, const float* tau_ext, int n_queries, uint32_t* fail_flags, hipStream_t s);
 hipError_t launch_raise_thr_rank(float* thr_hat, float* tau_hat, const uint64_t* topk_keys, int kp, int r, const float* margin, int n_queries, hipStream_t s);
+// the two raises above in one launch (thr_run null / r == 0: that one is skipped) + the slot-ordered threshold mirror of a seated main pass (thr_seat null: none)
+hipError_t launch_raise_thr_main(float* thr_hat, const float* thr_run, float* tau_hat, const uint64_t* topk_keys, int kp, int r, const float* margin,
+                                 int n_queries, float* thr_seat, const int32_t* q_slot, hipStream_t s);
+// Seating of a batch for the main pass (seating.h): slot_q / q_slot [q_pad] from the per-query list lengths len [n_queries], the slot-ordered copies of
+// thr, i8_mul and (non-null) g8_shift, and the query operand tiles in slot order (two launches on s; q_pad <= seat::MAX_QUERIES)
+hipError_t launch_seat_queries(const uint32_t* len, int n_queries, int q_pad, const float* thr, const float* i8_mul, const int32_t* g8_shift, const void* q_tiles,
+                               int ts_q, int td, int32_t* slot_q, int32_t* q_slot, float* thr_seat, float* mul_seat, int32_t* shift_seat, void* tiles_seat,
+                               hipStream_t s);
+bool gemm_filter_takes_g8(const GemmArgs& a);      // launch_gemm_filter would run gemm_filter_g8_kernel
 hipError_t launch_count_ge(const uint64_t* topk_keys, int kp, int k, const float* tau, const uint32_t* fail_flags, int n_queries,
                            int32_t* out, hipStream_t s);
 hipError_t launch_merge_topk(int n_queries, int n_in, const float* in_scores, const int64_t* in_rows, int k_out,

@@ -102,7 +102,19 @@ struct Workspace {
   uint32_t* blk_off = nullptr;           // 2 x (q_pad + 1): block offsets of the flat refine / rescoring launches
   uint2* cand2 = nullptr;                // second candidate list set: chunk i+1's GEMM overlaps chunk i's rescoring
   uint32_t* cnt2 = nullptr;
-  void* h_pinned = nullptr;              // 16 bytes pinned mirror
+  // Seating of the main pass (seating.h; allocated with the second list set).  seat_rec: ONE record of 5 x q_alloc words, thr_seat | slot_q | q_slot |
+  // mul_seat | shift_seat -- the bound GEMM gets thr_seat as its thresholds and finds slot_q q_alloc words behind them (GemmArgs::seat);
+  // q_tiles_seat: the operand tiles in slot order; seat_len: [q_alloc] bound-list totals of the sampled run (lists_ready_kernel)
+  float* seat_rec = nullptr;
+  __half* q_tiles_seat = nullptr;
+  uint32_t* seat_len = nullptr;
+  bool seated = false;                   // the latest main pass on this workspace ran seated
+  float* thr_seat() const { return seat_rec; }
+  int32_t* slot_q() const { return (int32_t*)seat_rec + q_alloc; }
+  int32_t* q_slot() const { return (int32_t*)seat_rec + 2 * (size_t)q_alloc; }
+  float* mul_seat() const { return seat_rec + 3 * (size_t)q_alloc; }
+  int32_t* shift_seat() const { return (int32_t*)seat_rec + 4 * (size_t)q_alloc; }
+  void* h_pinned = nullptr;             // 16 bytes pinned mirror
   char* h_pinned2 = nullptr;             // 2 x 16 bytes pinned (main-pass chunk statistics)
   uint32_t* d_max2 = nullptr;            // 2 x 16 bytes device
   unsigned long long* d_stats = nullptr; // 4 x u64 device: {bound candidates, exact rescorings, -, -} of a search whose controller runs without host read-backs
@@ -175,7 +187,8 @@ struct dhr_index {
   int gemm_variant = 0;                    // 2:4 layout kernel of THIS handle (0 = library default)
   int last_gemm_kernel = 0;                // DHR_INFO_GEMM_KERNEL: what the latest search's bound-GEMM launches ran (kernels.hip g_last_gemm_kernel)
   int overlap_aux = -1;                    // 0: refine / rescoring / select run on the GEMM's stream (every kernel gets the whole chip); 1: beside the next chunk's GEMM on the aux stream; -1 (default) = 1 (round 4; until then gated unsharded searches ran serially)
-  int aux_cus = -1, gemm_exclusive = 0;    // CU-masked streams of the main pass (0 = no mask; -1 = default: 128 CUs for dense-only indexes, no mask for gated ones)
+  int seat_queries = -1;                   // DHR_PARAM_SEAT_QUERIES: -1 = the main pass of a whole search seats the batch where it can (search_core.hip seat_plan), 0 = never
+  int aux_cus = -1, gemm_exclusive = 0;   // CU-masked streams of the main pass (0 = no mask; -1 = default: 128 CUs for dense-only indexes, no mask for gated ones)
   int aux_cus_made = -1, gemm_excl_made = -1;
   hipStream_t s_gemm = nullptr;         // main-pass GEMM stream when CU masks are in use
   hipStream_t s_aux = nullptr;          // non-blocking stream for rescoring/select overlapped with the main-pass GEMM
@@ -196,6 +209,7 @@ struct dhr_index {
 inline void free_ws(Workspace& w) {
   hipFree(w.q_tiles); hipFree(w.q32); hipFree(w.q_idx); hipFree(w.q16); hipFree(w.q_idx8); hipFree(w.q_inexact); hipFree(w.margin); hipFree(w.i8_mul); hipFree(w.g8_q8); hipFree(w.g8_shift); hipFree(w.g8_unit); hipFree(w.tau); hipFree(w.thr);
   hipFree(w.cnt); hipFree(w.cand); if (!w.keys_alias) hipFree(w.rs_keys); hipFree(w.topk_keys); hipFree(w.d_max); hipFree(w.tau_hat); hipFree(w.fail_flags); hipFree(w.thr_hat); hipFree(w.cand2); hipFree(w.cnt2); hipFree(w.q_pack); hipFree(w.cand_r); hipFree(w.cnt_r); hipFree(w.thr_raise); hipFree(w.blk_off); hipFree(w.ovf); hipFree(w.ovf2); hipFree(w.ovf_off); hipFree(w.ovf_cap); hipFree(w.cnt_plan); hipFree(w.tier_dev); hipFree(w.boot_rows); hipFree(w.boot_bound);
+  hipFree(w.seat_rec); hipFree(w.q_tiles_seat); hipFree(w.seat_len);
   if (w.h_pinned) hipHostFree(w.h_pinned);
   if (w.h_pinned2) hipHostFree(w.h_pinned2);
   hipFree(w.d_max2); hipFree(w.d_ref); hipFree(w.d_stats);

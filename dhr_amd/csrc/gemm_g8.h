@@ -12,7 +12,9 @@ typedef int intx8 __attribute__((ext_vector_type(8)));
 constexpr int G8_QOFF = 16384;                 // query part of a ring slot (the corpus part is 10 KiB gated / 16 KiB ungated)
 constexpr int G8_SLOT = 32768;
 constexpr int G8_META = 4 * G8_SLOT;           // behind the ring: 4 x 1 KiB = the tile's 256 row sums, and unit / threshold / shift of its 256 queries
-constexpr int G8_RING_LDS = 4 * G8_SLOT + 4096 + 64;
+constexpr int G8_MAP = G8_META + 4096;         // seated launches (GemmArgs::seat): 1 KiB = slot -> query words of the tile's 256 queries.  BEHIND the 4 KiB above,
+                                               // which the epilogue reuses as slot EPI_STACK of the hit stacks: the map is read after the scan
+constexpr int G8_RING_LDS = 4 * G8_SLOT + 4096 + 1024 + 64;
 constexpr int G8_NT = 512;
 
 

@@ -64,10 +64,10 @@ __device__ __forceinline__ void g8_dump_tile(const GemmArgs& p, floatx16 (&acc)[
 // only cost its 15 maxima.)
 template <bool SURPLUS, int NI_, bool CHECK_ROWS = true>
 __device__ __forceinline__ void g8_scan_half(const GemmArgs& p, floatx16 (&acc)[4][2], int qt, int wm, int wn, int lane, int rows_valid, int64_t row0,
-                                             uint2* stack, const int t, const float mul, uint32_t& j) {
+                                             uint2* stack, const int t, const float mul, uint32_t& j, const int* qmap = nullptr) {
   const int fhalf = lane >> 5;
   const int rbase = wm * 128 + 4 * fhalf;
-  const int q = qt * TILE_ROWS + wn * 64 + NI_ * 32 + (lane & 31);
+  const int ql = wn * 64 + NI_ * 32 + (lane & 31);      // the lane's query slot inside the tile (SURPLUS: its query number is looked up behind the hit test)
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
     const floatx16& a = acc[mi][NI_];
@@ -98,6 +98,7 @@ __device__ __forceinline__ void g8_scan_half(const GemmArgs& p, floatx16 (&acc)[
             asm volatile("");
             if constexpr (SURPLUS) {
               if (j >= EPI_STACK) {
+                const int q = qmap ? qmap[ql] : qt * TILE_ROWS + ql;
                 const uint32_t slot = atomicAdd(p.cnt + q, 1u);
                 cand_store(p, q, slot, make_uint2((uint32_t)(row0 + rl), __float_as_uint(g8_score(v, mul))));
               }
@@ -110,10 +111,10 @@ __device__ __forceinline__ void g8_scan_half(const GemmArgs& p, floatx16 (&acc)[
   }
 }
 __device__ __forceinline__ void g8_epilogue_surplus(const GemmArgs& p, floatx16 (&acc)[4][2], int qt, int wm, int wn, int lane, int rows_valid, int64_t row0,
-                                                 const int (&thr_r)[2], const float (&mul_r)[2]) {
+                                                 const int (&thr_r)[2], const float (&mul_r)[2], const int* qmap) {
   uint32_t j = 0;
-  g8_scan_half<true, 0>(p, acc, qt, wm, wn, lane, rows_valid, row0, nullptr, thr_r[0], mul_r[0], j);
-  g8_scan_half<true, 1>(p, acc, qt, wm, wn, lane, rows_valid, row0, nullptr, thr_r[1], mul_r[1], j);
+  g8_scan_half<true, 0>(p, acc, qt, wm, wn, lane, rows_valid, row0, nullptr, thr_r[0], mul_r[0], j, qmap);
+  g8_scan_half<true, 1>(p, acc, qt, wm, wn, lane, rows_valid, row0, nullptr, thr_r[1], mul_r[1], j, qmap);
 }
 // Filter epilogue.  Scheme of gemm_epilogue_w (private hit stacks in the idle ring, one global atomic per lane and query), on
 // integers, with a SMALL hot path: a hit pushes (row, raw integer sum) and nothing else; conversion happens in the flush loop, and
@@ -127,7 +128,11 @@ __device__ __forceinline__ void g8_epilogue(const GemmArgs& p, floatx16 (&acc)[4
   const int64_t row0 = dt * TILE_ROWS;
   const int rows_valid = (int)(p.n_rows - row0 < TILE_ROWS ? p.n_rows - row0 : TILE_ROWS);
   uint2* stack = (uint2*)smem + tid;                       // slot j at stack[j * G8_NT]
-  const int q0 = qt * TILE_ROWS + wn * 64 + (lane & 31);
+  // A seated launch (GemmArgs::seat) computes in SLOT space: the lists and their counters belong to the query the slot -> query words of the
+  // tile name (G8_MAP, landed with the tile constants).  They are read on the cold side of the hit tests only.
+  const int ql0 = wn * 64 + (lane & 31);
+  const int* qmap = p.seat ? (const int*)(smem + G8_MAP) : nullptr;
+  int q0 = qt * TILE_ROWS + ql0, q1 = q0 + 32;
   // every tile but a shard's last one is full: its copy of the scan has no per-element row test (one compare and one scalar AND less in
   // each of the ~90 serial test chains of a tile)
   const bool full = rows_valid == TILE_ROWS;
@@ -137,7 +142,10 @@ __device__ __forceinline__ void g8_epilogue(const GemmArgs& p, floatx16 (&acc)[4
   const uint32_t s0 = j < (uint32_t)EPI_STACK ? j : (uint32_t)EPI_STACK;
 #if G8_ABL != 16
   uint32_t base0 = 0u, base1 = 0u;
-  if (s0 > 0) base0 = atomicAdd(p.cnt + q0, s0);
+  if (s0 > 0) {
+    if (qmap) q0 = qmap[ql0];
+    base0 = atomicAdd(p.cnt + q0, s0);
+  }
 #endif
   if (full) g8_scan_half<false, 1, false>(p, acc, qt, wm, wn, lane, rows_valid, row0, stack, thr_r[1], mul_r[1], j);
   else g8_scan_half<false, 1, true>(p, acc, qt, wm, wn, lane, rows_valid, row0, stack, thr_r[1], mul_r[1], j);
@@ -145,8 +153,11 @@ __device__ __forceinline__ void g8_epilogue(const GemmArgs& p, floatx16 (&acc)[4
 #if G8_ABL == 16       // timing only: hits are found and stacked, never flushed to the lists
   return;
 #else
-  if (s1 > s0) base1 = atomicAdd(p.cnt + q0 + 32, s1 - s0);
-  if (__builtin_amdgcn_ballot_w64(j > (uint32_t)EPI_STACK) != 0) g8_epilogue_surplus(p, acc, qt, wm, wn, lane, rows_valid, row0, thr_r, mul_r);
+  if (s1 > s0) {
+    if (qmap) q1 = qmap[ql0 + 32];
+    base1 = atomicAdd(p.cnt + q1, s1 - s0);
+  }
+  if (__builtin_amdgcn_ballot_w64(j > (uint32_t)EPI_STACK) != 0) g8_epilogue_surplus(p, acc, qt, wm, wn, lane, rows_valid, row0, thr_r, mul_r, qmap);
   for (uint32_t i = 0; i < s0; ++i) {
     const uint2 en = stack[i * G8_NT];
     const uint32_t slot = base0 + i;
@@ -155,7 +166,7 @@ __device__ __forceinline__ void g8_epilogue(const GemmArgs& p, floatx16 (&acc)[4
   for (uint32_t i = s0; i < s1; ++i) {
     const uint2 en = stack[i * G8_NT];
     const uint32_t slot = base1 + (i - s0);
-    cand_store(p, q0 + 32, slot, make_uint2((uint32_t)row0 + en.x, __float_as_uint(g8_score((int)en.y, mul_r[1]))));
+    cand_store(p, q1, slot, make_uint2((uint32_t)row0 + en.x, __float_as_uint(g8_score((int)en.y, mul_r[1]))));
   }
 #endif
 }
@@ -293,8 +304,8 @@ __device__ __forceinline__ void g8_tile(const GemmArgs& p, char* smem, const int
   };
 
   // ---- prologue.  ONE memory round trip before the first matrix instruction, and nothing the compiler's wait-count model has to
-  // guess about: the tile's per-row and per-query constants (accumulator start values; unit, threshold and shift of the queries) travel
-  // as four 1 KiB LDS-DMA pieces ahead of the first stage pair and are read from the LDS behind the first barrier.  (Until round 3
+  // guess about: the tile's per-row and per-query constants (accumulator start values; unit, threshold and shift of the queries; in a seated launch
+  // the slot -> query words) travel as four or five 1 KiB LDS-DMA pieces ahead of the first stage pair and are read from the LDS behind the first barrier.  (Until round 3
   // they were per-lane global loads, each pinned by an empty asm -- four serialised L2 round trips before the first DMA piece was
   // even issued, behind ~400 scalar instructions of 64-bit division: together most of the 2.5 us "per-tile constant" that neither a
   // persistent workgroup nor a skipped first-pair wait had removed in rounds 1-2.)
@@ -303,6 +314,9 @@ __device__ __forceinline__ void g8_tile(const GemmArgs& p, char* smem, const int
                     : wave == 2 ? (const char*)(p.thr + qt * TILE_ROWS) : (const char*)(p.g8_shift + qt * TILE_ROWS);
     __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src + lane_off), LDS_PTR(smem + G8_META + wave * 1024), 16, 0, 0);
   }
+  // seated launch: the tile's slot -> query words as a fifth piece, outside the 4 KiB the epilogue's hit stacks reuse (G8_MAP)
+  if (wave == 4 && p.seat != 0 && !DUMP)
+    __builtin_amdgcn_global_load_lds(GLOBAL_PTR((const char*)(p.thr + p.seat + qt * TILE_ROWS) + lane_off), LDS_PTR(smem + G8_MAP), 16, 0, 0);
   issue_pair(0);
   if (npairs > 1) {            // the constants and pair 0 must have landed; pair 1 (this wave's 5 or 8 pieces, loads return in order) may stay in flight
     issue_pair(1);

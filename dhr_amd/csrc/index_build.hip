@@ -76,6 +76,7 @@ extern "C" int dhr_index_set_param(dhr_index* ix, int32_t param, int64_t value) 
       ix->aux_cus = (int)value; return DHR_OK;
     case DHR_PARAM_GEMM_EXCLUSIVE: ix->gemm_exclusive = value != 0; return DHR_OK;
     case DHR_PARAM_OVERLAP_AUX: ix->overlap_aux = value < 0 ? -1 : value != 0; return DHR_OK;
+    case DHR_PARAM_SEAT_QUERIES: ix->seat_queries = value < 0 ? -1 : 0; return DHR_OK;      // (-1 = on where it applies, 0 = off: there is no "forced on")
     case DHR_PARAM_GEMM_VARIANT:
 #ifdef DHR_AB_VARIANTS
       if (value == 6) { ix->gemm_variant = 6; return DHR_OK; }      // A/B builds: persistent workgroups on gated_i8 indexes (tools/ab/gemm_g8p.hip)

@@ -16,6 +16,7 @@
 
 #include "dhr_internal.h"
 #include "gemm_common.h"
+#include "seating.h"
 #include <type_traits>
 
 namespace dhr {
@@ -701,15 +702,22 @@ hipError_t launch_gemm_filter(const GemmArgs& a_in, hipStream_t s) {
   }
   return hipSuccess;
 }
+// Will these launch arguments run gemm_filter_g8_kernel?  (The main pass asks before it seats a batch: search_core.hip.)
+bool gemm_filter_takes_g8(const GemmArgs& a) {
+  if (a.ts + a.td <= 0 || (a.ts & 1) || (a.td & 1) || (a.ts_q & 1)) return false;
+  if (a.g8_shift) return a.ts > 0 && a.ts_q == a.ts;
+  // a dense-only int8 index (no gated stage on either side): the integer kernel of the gated_i8 indexes with ts = 0 -- the same operand
+  // images, integer filter epilogue; config 2: 2.78 -> 2.70 ms per launch alone, 76.4 -> 75.1 ms per step (DHR_DENSE_G8=0: gemm_filter_wx_kernel)
+  static const int dense_g8 = getenv("DHR_DENSE_G8") ? atoi(getenv("DHR_DENSE_G8")) : 1;
+  return a.i8_mul && dense_g8 && a.ts == 0 && a.ts_q == 0 && a.td > 0;
+}
 static hipError_t launch_gemm_filter_grid(const GemmArgs& a, dim3 grid, hipStream_t s) {
   const int variant = a.variant == 4 ? 4 : a.variant ? 5 : g_gemm_variant;        // per handle (dhr_index_set_param), else the library default
   // every index is a stage image with an even number of stages of either kind (dhr_index_create pads with all-zero stages)
   if (a.ts + a.td <= 0 || (a.ts & 1) || (a.td & 1) || (a.ts_q & 1)) return hipErrorInvalidValue;
   if (a.g8_shift) { g_last_gemm_kernel = 5; return (a.ts > 0 && a.ts_q == a.ts) ? launch_gemm_g8(a, grid, s) : hipErrorInvalidValue; }
-  // a dense-only int8 index (no gated stage on either side): the integer kernel of the gated_i8 indexes with ts = 0 -- the same operand
-  // images, integer filter epilogue; config 2: 2.78 -> 2.70 ms per launch alone, 76.4 -> 75.1 ms per step (DHR_DENSE_G8=0: gemm_filter_wx_kernel)
-  static const int dense_g8 = getenv("DHR_DENSE_G8") ? atoi(getenv("DHR_DENSE_G8")) : 1;
-  if (a.i8_mul && dense_g8 && a.ts == 0 && a.ts_q == 0 && a.td > 0) { g_last_gemm_kernel = 5; return launch_gemm_g8(a, grid, s); }
+  if (gemm_filter_takes_g8(a)) { g_last_gemm_kernel = 5; return launch_gemm_g8(a, grid, s); }
+  if (a.seat) return hipErrorInvalidValue;          // only gemm_filter_g8_kernel knows the slot -> query map
   g_last_gemm_kernel = variant == 4 ? 4 : 3;
   return launch_gemm_wx(a, grid, variant, s);      // fp16 gated stages; ungated stages fp16 or (i8_mul) int8
 }
@@ -751,7 +759,7 @@ __global__ void __launch_bounds__(1024) lists_ready_kernel(const uint32_t* __res
                                                            uint32_t* __restrict__ offs, uint32_t* __restrict__ out_max, uint32_t* __restrict__ out_max2,
                                                            unsigned long long* __restrict__ out_sum, unsigned long long* __restrict__ out_sum2,
                                                            uint32_t* __restrict__ fail_flags, uint32_t* __restrict__ zero, int n_zero,
-                                                           const uint32_t* __restrict__ ovf_cap) {
+                                                           const uint32_t* __restrict__ ovf_cap, uint32_t* __restrict__ seat_len) {
   __shared__ uint32_t part[1024];
   __shared__ uint32_t wmax[16];
   __shared__ unsigned long long wsum[16];
@@ -764,6 +772,7 @@ __global__ void __launch_bounds__(1024) lists_ready_kernel(const uint32_t* __res
     uint32_t c = cnt[q];
     m = c > m ? c : m;
     tot += c;
+    if (seat_len) seat_len[q] += c;                                // sampled run: the per-query totals the main pass seats the batch by (seat_rank_kernel)
     const uint32_t cq = ovf_cap ? cap + ovf_cap[q] : cap;          // two-tier lists: the query's own capacity
     if (c > cq) { c = cq; if (fail_flags) fail_flags[q] = 1u; }
     s += (c + per - 1) / per;
@@ -797,9 +806,9 @@ __global__ void __launch_bounds__(1024) lists_ready_kernel(const uint32_t* __res
 }
 hipError_t launch_lists_ready(const uint32_t* cnt, uint32_t cap, int n_queries, uint32_t per, uint32_t* offs, uint32_t* out_max, uint32_t* out_max2,
                               unsigned long long* out_sum, unsigned long long* out_sum2, uint32_t* fail_flags, uint32_t* zero, int n_zero,
-                              hipStream_t s, const uint32_t* ovf_cap) {
+                              hipStream_t s, const uint32_t* ovf_cap, uint32_t* seat_len) {
   hipLaunchKernelGGL(lists_ready_kernel, dim3(1), dim3(1024), 0, s, cnt, cap, n_queries, per, offs, out_max, out_max2, out_sum, out_sum2, fail_flags,
-                     zero, n_zero, ovf_cap);
+                     zero, n_zero, ovf_cap, seat_len);
   return hipGetLastError();
 }
 // Second tier of the bound lists (GemmArgs::ovf): one workgroup; thread t plans a contiguous range of queries, an exclusive scan of the
@@ -2491,6 +2500,87 @@ __global__ void raise_thr_rank_kernel(float* __restrict__ thr_hat, float* __rest
 }
 hipError_t launch_raise_thr_rank(float* thr_hat, float* tau_hat, const uint64_t* topk_keys, int kp, int r, const float* margin, int n_queries, hipStream_t s) {
   hipLaunchKernelGGL(raise_thr_rank_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, s, thr_hat, tau_hat, topk_keys, kp, r, margin, n_queries);
+  return hipGetLastError();
+}
+// What a chunk boundary of the main pass does to the filter thresholds, in ONE launch: raise_thr_kernel (thr_run, or null), then
+// raise_thr_rank_kernel (r > 0) -- the same maxima in the same order -- and, for a seated pass, the slot-ordered mirror the bound GEMM reads
+// (thr_seat[q_slot[q]], or null): every writer of thr_hat in the pass keeps it current in the launch that writes thr_hat.
+__global__ void raise_thr_main_kernel(float* __restrict__ thr_hat, const float* __restrict__ thr_run, float* __restrict__ tau_hat,
+                                      const uint64_t* __restrict__ topk_keys, int kp, int r, const float* __restrict__ margin, int n_queries,
+                                      float* __restrict__ thr_seat, const int32_t* __restrict__ q_slot) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_queries) return;
+  float t = thr_hat[q];
+  if (thr_run) t = fmaxf(t, thr_run[q]);
+  if (r > 0) {
+    const uint64_t key = topk_keys[(int64_t)q * kp + (r - 1)];
+    if (key != 0ull) {
+      const float te = ordered_f32((uint32_t)(key >> 32));
+      if (te > tau_hat[q]) {
+        tau_hat[q] = te;
+        t = fmaxf(t, te - margin[q]);
+      }
+    }
+  }
+  thr_hat[q] = t;
+  if (thr_seat) thr_seat[q_slot[q]] = t;
+}
+hipError_t launch_raise_thr_main(float* thr_hat, const float* thr_run, float* tau_hat, const uint64_t* topk_keys, int kp, int r, const float* margin,
+                                 int n_queries, float* thr_seat, const int32_t* q_slot, hipStream_t s) {
+  hipLaunchKernelGGL(raise_thr_main_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, s, thr_hat, thr_run, tau_hat, topk_keys, kp, r, margin, n_queries,
+                     thr_seat, q_slot);
+  return hipGetLastError();
+}
+// ---- seating of the main pass (seating.h).  Workgroup b ranks queries [256 b, 256 b + 256) against ALL keys of the batch
+// (every workgroup holds them in its LDS: at most seat::MAX_QUERIES words, a broadcast read per comparison) and writes both directions of the
+// permutation and the slot-ordered copies of what the bound GEMM reads per query: unit, shift, threshold.
+__global__ void __launch_bounds__(256) seat_rank_kernel(const uint32_t* __restrict__ len, int n_queries, int q_pad, const float* __restrict__ thr,
+                                                        const float* __restrict__ i8_mul, const int32_t* __restrict__ g8_shift,
+                                                        int32_t* __restrict__ slot_q, int32_t* __restrict__ q_slot, float* __restrict__ thr_seat,
+                                                        float* __restrict__ mul_seat, int32_t* __restrict__ shift_seat) {
+  __shared__ int32_t keys[seat::MAX_QUERIES];
+  for (int j = threadIdx.x; j < q_pad; j += 256) {
+    const uint32_t l = j < n_queries ? len[j] : 0u;
+    keys[j] = (int32_t)seat::key_of(l < 0x7fffffffu ? l : 0x7fffffffu, j, n_queries);      // (a list length never gets near 2^31: the sample is 1 / 32 of < 2^32 rows)
+  }
+  __syncthreads();
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= q_pad) return;
+  const int64_t kq = keys[q];
+  int slot = 0;
+  for (int j = 0; j < q_pad; ++j) slot += seat::before((int64_t)keys[j], j, kq, q) ? 1 : 0;
+  slot_q[slot] = q;
+  q_slot[q] = slot;
+  thr_seat[slot] = thr[q];
+  mul_seat[slot] = i8_mul[q];
+  if (g8_shift) shift_seat[slot] = g8_shift[q];
+}
+// The query operand tiles in slot order: a pure permutation of 16-byte chunks.  Chunk cc of row r of a stage lies at r * 64 + ((cc ^ ((r >> 2) & 3)) * 16)
+// (the tile writer of query_prep_kernel), so a row that changes its place in the tile changes the order of its four chunks.
+__global__ void __launch_bounds__(256) seat_tiles_kernel(const char* __restrict__ src, char* __restrict__ dst, const int32_t* __restrict__ slot_q, int q_pad,
+                                                         int ts_q, int td) {
+  const int cpq = (ts_q + td) * 4;                     // 16-byte chunks of a query
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)q_pad * cpq) return;
+  const int sl = (int)(i / cpq), c = (int)(i - (int64_t)sl * cpq);
+  const int st = c >> 2, cc = c & 3;
+  const int q = slot_q[sl];
+  const int64_t tile_bytes = (int64_t)ts_q * SP_STAGE_B + (int64_t)td * SP_DENSE;
+  const int64_t st_off = st < ts_q ? (int64_t)st * SP_STAGE_B : (int64_t)ts_q * SP_STAGE_B + (int64_t)(st - ts_q) * SP_DENSE;
+  const int rq = q & 255, rs = sl & 255;
+  const uint4 v = *(const uint4*)(src + (int64_t)(q >> 8) * tile_bytes + st_off + rq * 64 + ((cc ^ ((rq >> 2) & 3)) * 16));
+  *(uint4*)(dst + (int64_t)(sl >> 8) * tile_bytes + st_off + rs * 64 + ((cc ^ ((rs >> 2) & 3)) * 16)) = v;
+}
+hipError_t launch_seat_queries(const uint32_t* len, int n_queries, int q_pad, const float* thr, const float* i8_mul, const int32_t* g8_shift, const void* q_tiles,
+                               int ts_q, int td, int32_t* slot_q, int32_t* q_slot, float* thr_seat, float* mul_seat, int32_t* shift_seat, void* tiles_seat,
+                               hipStream_t s) {
+  if (q_pad <= 0 || q_pad > seat::MAX_QUERIES || (q_pad & 255)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seat_rank_kernel, dim3(q_pad / 256), dim3(256), 0, s, len, n_queries, q_pad, thr, i8_mul, g8_shift, slot_q, q_slot, thr_seat, mul_seat,
+                     shift_seat);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int64_t chunks = (int64_t)q_pad * (ts_q + td) * 4;
+  hipLaunchKernelGGL(seat_tiles_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const char*)q_tiles, (char*)tiles_seat, slot_q, q_pad, ts_q, td);
   return hipGetLastError();
 }
 // Rows of the final list that reach tau (all valid rows when tau is null); -1 when the shard's lists overflowed.

@@ -11,6 +11,7 @@
 // search_core(..., Stage) runs the whole search or one staged entry point's part of it (what a later call resumes from: dhr_index::pend), as a
 // driver over prepare_and_phase0 -> sampled_run | adopt_thresholds -> main_pass -> verify_and_redo; one phase: stream_phases -> gemm_phase -> rescore_select[_async].
 #include "dhr_state.h"
+#include "seating.h"
 
 // ------------------------------------------------------------------------------------------ workspace
 template <typename T>
@@ -282,6 +283,8 @@ struct Search {
   bool gate = false;
   bool after_mid = false;          // Finish behind a dhr_search_mid: chunk 0 of the main pass is done, the thresholds are those of the second agreement
   bool async_ctl = false;          // the controller only enqueues (no host read-backs between the phases)
+  bool seat = false;               // the main pass runs seated (seat_plan): its bound GEMM computes in slot space (seating.h)
+  uint32_t* seat_acc = nullptr;    // sampled run of such a search: where lists_ready_kernel accumulates the per-query bound-list lengths
   SearchPlan p;
   SelectArgs sel{};
   double rate = 0.0, rate_r = 0.0; // fullest bound / survivor list per corpus row at the thresholds of the last sampled phase (0: not known)
@@ -345,7 +348,7 @@ static int rescore_select_async(Search& c, const uint2* cand, const uint32_t* cn
   // the bound lists: statistics, overflow marks, block offsets of the kernel that walks them and (refine) the survivor counters cleared
   HIP_TRY(launch_lists_ready(cnt, (uint32_t)w.cap, Q, refine ? (uint32_t)REFINE_PER_WG : (uint32_t)RESCORE_CANDS_PER_WG, refine ? w.blk_off : w.blk_off + w.q_pad + 1,
                              d_fullest_bound, refine ? nullptr : d_fullest, w.d_stats + 0, refine ? nullptr : w.d_stats + 1, w.fail_flags,
-                             refine ? w.cnt_r : nullptr, refine ? (int)w.q_pad : 0, s, ovf_cap));
+                             refine ? w.cnt_r : nullptr, refine ? (int)w.q_pad : 0, s, ovf_cap, c.seat_acc));
   if (refine) {
     RefineArgs f = base_refine_args(ix, w, Q, c.gate, thr);
     f.ovf = ovf; f.ovf_off = ovf ? w.ovf_off : nullptr; f.ovf_cap = ovf_cap;
@@ -520,7 +523,31 @@ static int prepare_and_phase0(Search& c, const dhr_query_batch* qb) {
   return DHR_OK;
 }
 
-// Step 2: the sampled run -- top-r_eff of {head rows} + {every S-th tile} -> tau_hat.  Pre runs its first part and stops; BeginRest resumes
+// Does the main pass of this search seat its batch (seating.h; DHR_PARAM_SEAT_QUERIES)?  Only the first attempt of a whole sampled search whose
+// controller enqueues (its lists_ready launches collect the list lengths), on gemm_filter_g8_kernel, with more than one query tile: staged and
+// sharded calls, the fp16-gated kernels, the fallback depths and the host-driven controller keep every query where the caller put it.
+// Gated indexes only: a dense-only int8 index runs the same kernel (ts = 0), but its step gains nothing -- config 2 measured 74.7 against 73.7 ms
+// serial and 72.4 against 71.6 ms overlapped with the seating on (profiles/query_seating.txt) -- so it keeps the identity too.
+// The buffers are allocated once per workspace; a call only clears the length totals.
+static int seat_plan(Search& c) {
+  dhr_index* ix = c.ix; Workspace& w = c.w;
+  c.seat = false;
+  if (!c.whole() || c.depth != 0 || !c.async_ctl || !c.p.sampled || ix->seat_queries == 0 || ix->gemm_variant == 6 || !ix->gated_i8) return DHR_OK;
+  if (w.q_pad <= TILE_ROWS || w.q_pad > seat::MAX_QUERIES) return DHR_OK;
+  if (!gemm_filter_takes_g8(base_gemm_args(ix, w, c.Q))) return DHR_OK;
+  if (!w.seat_rec) {
+    int64_t tot = 0;
+    HIP_TRY(re_malloc(w.seat_rec, (size_t)w.q_alloc * 5 * 4, tot));
+    HIP_TRY(re_malloc(w.q_tiles_seat, (size_t)w.q_alloc * ix->kt * 2, tot));
+    HIP_TRY(re_malloc(w.seat_len, (size_t)w.q_alloc * 4, tot));
+    w.bytes += tot;
+  }
+  HIP_TRY(hipMemsetAsync(w.seat_len, 0, (size_t)w.q_pad * 4, c.s));
+  c.seat = true;
+  return DHR_OK;
+}
+
+// Step 2: the sampled run -- top-r_eff of {head rows} + {every S-th tile} -> tau_hat. Pre runs its first part and stops; BeginRest resumes
 // behind that part from the threshold the shards agreed on; Begin and BeginRest leave the handle ready for the main pass of a later call.
 static int sampled_run(Search& c) {
   dhr_index* ix = c.ix; Workspace& w = c.w; hipStream_t s = c.s; const SearchPlan& p = c.p; const int Q = c.Q;
@@ -548,7 +575,9 @@ static int sampled_run(Search& c) {
     // the union sample -- 8 x the rows this shard has seen -- and a phase of a shard's sampled run is bound by its launches, not by its rows
     chunk0 = round_up(p.n_sample - o.pos0, DOC_GROUP);
   }
+  c.seat_acc = c.seat ? w.seat_len : nullptr;
   int rc = stream_phases(c, n_hi, p.S, chunk0, seen0, o);
+  c.seat_acc = nullptr;
   if (rc != DHR_OK) return rc;
   if (pre) {
     staged_open(ix, StagedState::AfterPre, c.gate, Q, c.k);
@@ -702,6 +731,10 @@ static int main_gemm(Search& c, MainPass& mp, int i) {
   g.seq_lo = mp.bound[i]; g.seq_hi = mp.bound[i + 1]; g.map_mode = mp.scatter ? 3 : 2; g.period = c.p.S; g.head = c.p.head;
   g.perm_mul = mp.scatter ? c.p.perm_mul : 1; g.perm_n = c.p.n_main;
   g.thr = w.thr_hat; g.cand = (i & 1) ? w.cand2 : w.cand; g.cnt = cnt;
+  if (c.seat) {          // slot space: operand tiles, units, shifts and thresholds in slot order, slot_q one q_alloc behind the thresholds (Workspace::seat_rec)
+    g.b_tiles = w.q_tiles_seat; g.i8_mul = w.mul_seat(); g.thr = w.thr_seat(); g.seat = w.q_alloc;
+    if (g.g8_shift) g.g8_shift = w.shift_seat();
+  }
   if (mp.two_tier) g.tier = w.tier_dev + (i & 1);
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)w.q_pad * 4, sg));
   if (!c.async_ctl) HIP_TRY(hipMemsetAsync(w.d_max2 + 4 * (i & 1), 0, 16, sg));
@@ -738,11 +771,17 @@ static int main_chunks(Search& c, MainPass& mp) {
       HIP_TRY(launch_mark_overflow(cnt, (uint32_t)w.cap, Q, w.fail_flags, sb));
       if ((rc = rescore_select(c, cand, cnt, w.thr_hat, maxc, sb, (int64_t)sumc, w.fail_flags)) != DHR_OK) return rc;
     }
-    if (ix->progressive_thr) HIP_TRY(launch_raise_thr(w.thr_hat, c.sel.thr, Q, sb));   // later chunks filter with the running exact thresholds
+    // later chunks filter with the running exact thresholds and, where they are extrapolated, with the rank of the scattered fraction seen: one
+    // launch, which also keeps the slot-ordered mirror of a seated pass current
+    const float* thr_run = ix->progressive_thr ? c.sel.thr : nullptr;
+    int r = 0;
     if (mp.extrapolate && i + 1 < mp.M) {
-      const int r = plan::extrapolated_rank(c.k, (double)(p.head + p.n_sample + mp.bound[i + 1]) / (double)ix->n_tiles);
-      if (r < c.k) HIP_TRY(launch_raise_thr_rank(w.thr_hat, w.tau_hat, w.topk_keys, w.kp, r, w.margin, Q, sb));
+      r = plan::extrapolated_rank(c.k, (double)(p.head + p.n_sample + mp.bound[i + 1]) / (double)ix->n_tiles);
+      if (r >= c.k) r = 0;
     }
+    if (thr_run || r > 0)
+      HIP_TRY(launch_raise_thr_main(w.thr_hat, thr_run, w.tau_hat, w.topk_keys, w.kp, r, w.margin, Q, c.seat ? w.thr_seat() : nullptr,
+                                    c.seat ? w.q_slot() : nullptr, sb));
     HIP_TRY(hipEventRecord(mp.ev_done[i], sb));
   }
   return DHR_OK;
@@ -759,6 +798,12 @@ static int main_pass(Search& c) {
   const bool mid_proto = mid || c.after_mid;      // the shards agree a second time after a first slice: it must be a scattered one
   mp.scatter = mp.extrapolate || (mid_proto && p.n_main >= 64);
   if (!c.after_mid) HIP_TRY(hipMemcpyAsync(w.thr_hat, w.thr, (size_t)w.q_pad * 4, hipMemcpyDeviceToDevice, s));
+  // seated pass: the permutation from the sampled run's list lengths, and everything the bound GEMM reads per query in slot order -- the
+  // thresholds just copied among them (thr == thr_hat here; from now on raise_thr_main_kernel keeps the mirror current)
+  w.seated = c.seat;
+  if (c.seat)
+    HIP_TRY(launch_seat_queries(w.seat_len, c.Q, w.q_pad, w.thr, w.i8_mul, ix->gated_i8 ? w.g8_shift : nullptr, w.q_tiles, w.ts_q, ix->td, w.slot_q(), w.q_slot(),
+                                w.thr_seat(), w.mul_seat(), w.shift_seat(), w.q_tiles_seat, s));
   if (!w.cand2) {          // the second list set
     int64_t tot = 0;
     HIP_TRY(re_malloc(w.cand2, (size_t)w.q_alloc * w.cap * 8, tot));
@@ -902,7 +947,7 @@ int search_core(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, int k, i
   }
   switch (stage) {
     case Stage::Whole:
-      if ((rc = sampled_run(c)) != DHR_OK || (rc = main_pass(c)) != DHR_OK) return rc;
+      if ((rc = seat_plan(c)) != DHR_OK || (rc = sampled_run(c)) != DHR_OK || (rc = main_pass(c)) != DHR_OK) return rc;
       return verify_and_redo(c);
     case Stage::Begin: case Stage::Pre: case Stage::BeginRest:
       return sampled_run(c);                               // the staged search goes on in another call

@@ -128,6 +128,12 @@ typedef enum dhr_param {
                                  beyond that comes from a shared arena planned on the device (two-tier lists: the workspace of an 8.8 M-row index is
                                  ~7 GB instead of 34).  Takes effect for indexes with a refine level whose planned list depth exceeds it; tests
                                  force a small stride to exercise the second tier on small inputs.  0 or a multiple of 256 in [1024, 4194304] */
+  DHR_PARAM_SEAT_QUERIES = 15, /* main pass of a whole search of a gated int8 index (gemm_filter_g8_kernel with gated stages), batches of 257 .. 8 192 padded queries:
+                                  -1 (default) = the queries are seated in the kernel's query tiles by descending length of their bound lists over the
+                                  sampled run, so that the few queries that pass 10-100 x the average through the filter share wave columns instead of
+                                  slowing their neighbours' scan; 0 = every query sits where the caller put it.  Results, candidate
+                                  sets and launch plan do not depend on it.  Staged and sharded calls, the fp16-gated kernels, dense-only indexes (measured:
+                                  no gain) and the fallback controllers never seat */
   DHR_PARAM_SAMPLE_PERIOD = 5 /* every S-th corpus tile seeds the thresholds (default 32; 0 = plain streaming) */
 } dhr_param;
 
@@ -626,6 +632,12 @@ int dhr_debug_bound_scores(dhr_index* index, const dhr_query_batch* queries, int
 /* Debug/test hook: the filter margins of a query batch (HOST buffer [n_queries] fp32): the bound GEMM guarantees
  * U[q][row] >= exact score - margin[q] for every row, which is what lets the filter drop rows without losing a top-k row. */
 int dhr_debug_query_margins(dhr_index* index, const dhr_query_batch* queries, float* out_host, void* stream);
+
+/* Debug/test hook: how the main pass of the latest dhr_search on this handle seated its batch (DHR_PARAM_SEAT_QUERIES).  Returns 1 and fills the
+ * HOST arrays ([n_slots] each, n_slots = that batch's query count rounded up to 256; any may be null) when the pass ran seated: slot -> query,
+ * query -> slot, the per-query bound-list lengths of the sampled run the order was taken from, the slot-ordered threshold mirror and the
+ * thresholds as the pass left them.  Returns 0 and copies nothing when every query sat where the caller put it; negative: a dhr_status. */
+int dhr_debug_query_seating(dhr_index* index, int32_t n_slots, int32_t* slot_q, int32_t* q_slot, uint32_t* lengths, float* thr_seat, float* thr_hat);
 
 /* Test hook (host code only, no device needed): the corpus tile that position `seq` of a bound-GEMM launch maps to, computed with
  * the kernels' division-free arithmetic (out[0]) and with plain integer division (out[1]); the two must agree for every input. */

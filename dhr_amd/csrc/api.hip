@@ -555,6 +555,76 @@ extern "C" int dhr_debug_query_margins(dhr_index* ix, const dhr_query_batch* qb,
   return DHR_OK;
 } DHR_CATCH_STATUS
 
+// Test hook: what ONE phase of a search does with rows [row_lo, row_hi) up to the exact rescoring -- the bound GEMM into the candidate LISTS (not its
+// dump path: the entries the filter epilogue appends are what the refine level reads), then launch_refine on those lists with the arguments of
+// search_core.hip (base_refine_args) -- and both lists scattered into dense [Q][row_hi - row_lo] arrays: U of the rows the filter listed, U2 of the
+// rows the refine level kept, NaN elsewhere.  Uniform lists only (no second tier): the tiles of the range must fit both list depths.
+namespace {
+// entry i of query q's list (row, float bits) -> out[q][row - row_lo] where the row lies in the range (the tiles of a range may hold rows beside it)
+__global__ void __launch_bounds__(256) scatter_list_kernel(const uint2* __restrict__ list, const uint32_t* __restrict__ cnt, uint32_t cap, int64_t row_lo,
+                                                           int64_t row_hi, float* __restrict__ out) {
+  const int q = blockIdx.y;
+  const uint32_t count = cnt[q] < cap ? cnt[q] : cap;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+    const uint2 e = list[(int64_t)q * cap + i];
+    if ((int64_t)e.x >= row_lo && (int64_t)e.x < row_hi) out[(int64_t)q * (row_hi - row_lo) + ((int64_t)e.x - row_lo)] = __uint_as_float(e.y);
+  }
+}
+hipError_t scatter_list(const uint2* list, const uint32_t* cnt, uint32_t cap, int Q, int64_t row_lo, int64_t row_hi, float* out, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(out, 0xFF, (size_t)Q * (size_t)(row_hi - row_lo) * 4, s);      // 0xFFFFFFFF: a NaN
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(scatter_list_kernel, dim3(64, (unsigned)Q), dim3(256), 0, s, list, cnt, cap, row_lo, row_hi, out);
+  return hipGetLastError();
+}
+}  // namespace
+// tau_host: [Q] exact-score thresholds (the levels compare with thr = tau - margin, make_thr_kernel), or null: -inf, every row passes both levels.
+// flat: 0 = one workgroup per (block of the longest list, query); 1 = flat launch over the block offsets with the grid of the controller that
+// only enqueues; n > 1 = a flat launch of n workgroups (fewer than there are blocks: the rest by grid stride).  out_thr_host: [Q] thr, may be null;
+// out_unit_host: [Q] score units of one gated operand product (RefineArgs::g8_unit; zeros where the gated half has no int8 image), may be null.
+extern "C" int dhr_debug_refine_bounds(dhr_index* ix, const dhr_query_batch* qb, int64_t row_lo, int64_t row_hi, const float* tau_host, int32_t flat,
+                                       float* out_u_dev, float* out_u2_dev, float* out_thr_host, float* out_unit_host, void* stream) try {
+  int rc = check_queries(ix, qb);
+  if (rc) return rc;
+  if (row_lo < 0 || row_hi > ix->n_rows || row_lo >= row_hi) return set_error(DHR_ERR_INVALID, "bad row range");
+  if (!out_u_dev || !out_u2_dev) return set_error(DHR_ERR_INVALID, "null output pointer");
+  if (flat < 0) return set_error(DHR_ERR_INVALID, "flat must be >= 0");
+  const int Q = qb->n_queries;
+  const bool gate = ix->d_dlr > 0 && qb->index != nullptr && qb->index_dtype != DHR_IDX_NONE;
+  if (!uses_refine(ix, gate)) return set_error(DHR_ERR_UNSUPPORTED, "this batch has no refine level on this index");
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t s = (hipStream_t)stream;
+  staged_set(ix, StagedState::None);          // the call overwrites the workspace of any staged search left open on this handle
+  Workspace& w = ix->ws;
+  if ((rc = ensure_ws(ix, w, Q, 1, 0)) != DHR_OK) return rc;
+  const int64_t t_lo = row_lo / TILE_ROWS, t_hi = (row_hi + TILE_ROWS - 1) / TILE_ROWS;      // the tiles of the rows, in corpus order
+  const int64_t listed = std::min<int64_t>(t_hi * TILE_ROWS, ix->n_rows) - t_lo * TILE_ROWS;  // rows a list can receive
+  if (!w.cand_r || listed > std::min(w.cap, w.cap_r)) return set_error(DHR_ERR_INVALID, "row range deeper than the candidate lists");
+  if ((rc = prep_queries(ix, w, qb, s)) != DHR_OK) return rc;
+  if (tau_host) HIP_TRY(hipMemcpyAsync(w.tau, tau_host, (size_t)Q * 4, hipMemcpyHostToDevice, s));      // (else -inf: query_prep_kernel)
+  HIP_TRY(launch_make_thr(w.tau, w.margin, Q, w.q_pad, w.thr, s));
+  GemmArgs g = base_gemm_args(ix, w, Q);
+  g.seq_lo = t_lo; g.seq_hi = t_hi; g.map_mode = 0; g.period = 1; g.head = 0;
+  g.thr = w.thr; g.cand = w.cand; g.cnt = w.cnt;
+  HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)w.q_pad * 4, s));
+  HIP_TRY(launch_gemm_filter(g, s));
+  HIP_TRY(scatter_list(w.cand, w.cnt, (uint32_t)w.cap, Q, row_lo, row_hi, out_u_dev, s));
+  RefineArgs f = base_refine_args(ix, w, Q, gate, w.thr);
+  f.cand = w.cand; f.cnt = w.cnt;
+  if (flat == 0) f.max_count = (uint32_t)listed;
+  else {
+    HIP_TRY(launch_block_offsets(w.cnt, (uint32_t)w.cap, Q, REFINE_PER_WG, w.blk_off, s));
+    f.max_count = 1; f.blk_off = w.blk_off; f.flat_blocks = flat == 1 ? FLAT_GRID_ASYNC : (uint32_t)flat;
+  }
+  HIP_TRY(hipMemsetAsync(w.cnt_r, 0, (size_t)w.q_pad * 4, s));
+  HIP_TRY(launch_refine(f, s));
+  HIP_TRY(scatter_list(w.cand_r, w.cnt_r, (uint32_t)w.cap_r, Q, row_lo, row_hi, out_u2_dev, s));
+  if (out_thr_host) HIP_TRY(hipMemcpyAsync(out_thr_host, w.thr, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+  if (out_unit_host && f.g8_unit) HIP_TRY(hipMemcpyAsync(out_unit_host, f.g8_unit, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_unit_host && !f.g8_unit) std::fill(out_unit_host, out_unit_host + Q, 0.f);
+  return DHR_OK;
+} DHR_CATCH_STATUS
+
 // Test hook: how the main pass of the latest dhr_search on this handle seated its batch (seating.h).  Returns 1 and fills the host arrays ([n_slots] each,
 // n_slots = the batch's query count rounded up to 256; any may be null) when that pass ran seated: slot -> query, query -> slot, the bound-list
 // lengths of the sampled run the order was taken from, the slot-ordered threshold mirror and the thresholds themselves as the pass left them.

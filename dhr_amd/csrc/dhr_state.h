@@ -264,6 +264,8 @@ int prep_queries(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, hipStre
 dhr::RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_queries, bool gate);
 dhr::GemmArgs base_gemm_args(const dhr_index* ix, const Workspace& w, int n_queries);      // the caller adds the tile range and its mapping, the thresholds and lists, the dump
 dhr::SelectArgs rescored_select_args(const Workspace& w, int n_queries, int k);            // top k of w.rs_keys into w.topk_keys; the caller adds the key counts
+bool uses_refine(const dhr_index* ix, bool gate);                                          // does a batch (gated or plain IP) on this index go through a refine level?
+dhr::RefineArgs base_refine_args(const dhr_index* ix, const Workspace& w, int n_queries, bool gate, const float* thr);      // the caller adds the list set and the launch geometry
 // The plan of a search of this handle for k rows (search_plan.h).  staged: a staged call or a rank query -- the handle chases its share of the
 // union's rank; a whole search (the repair dhr_search inside a sharded step among them) chases the rank itself.
 inline SearchPlan search_plan_of(const dhr_index* ix, int k, int depth, bool staged) {

@@ -235,7 +235,7 @@ int prep_queries(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, hipStre
 // ------------------------------------------------------------------------------------------ argument structs
 // The refine step serves gated batches, and -- on gated_i8 indexes -- ungated ones too (--IP stage 1): there it takes the int8
 // products of a row's listed entries off the bound and puts their real products back, whatever the index values (RefineArgs::ungated).
-static inline bool uses_refine(const dhr_index* ix, bool gate) { return (ix->heavy_key != nullptr && (gate || ix->gated_i8)) || ix->resid8 != nullptr; }
+bool uses_refine(const dhr_index* ix, bool gate) { return (ix->heavy_key != nullptr && (gate || ix->gated_i8)) || ix->resid8 != nullptr; }
 RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_queries, bool gate) {
   RescoreArgs r{};
   r.vals_rm = ix->vals_rm; r.c_idx = ix->c_idx; r.c_idx_dtype = ix->idx_dtype;
@@ -264,7 +264,7 @@ SelectArgs rescored_select_args(const Workspace& w, int Q, int k) {
   return sel;
 }
 // ... and every refine launch: bound lists of depth w.cap filtered at thr into the survivor lists; the caller adds the list set and the launch geometry
-static RefineArgs base_refine_args(const dhr_index* ix, const Workspace& w, int Q, bool gate, const float* thr) {
+RefineArgs base_refine_args(const dhr_index* ix, const Workspace& w, int Q, bool gate, const float* thr) {
   RefineArgs f{};
   f.cap = (uint32_t)w.cap; f.heavy_key = ix->heavy_key; f.heavy_val = ix->heavy_val;
   f.q_pack = w.q_pack; f.d_dlr = ix->d_dlr; f.thr = thr; f.out = w.cand_r; f.out_cnt = w.cnt_r; f.out_cap = (uint32_t)w.cap_r;

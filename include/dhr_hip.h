@@ -633,6 +633,19 @@ int dhr_debug_bound_scores(dhr_index* index, const dhr_query_batch* queries, int
  * U[q][row] >= exact score - margin[q] for every row, which is what lets the filter drop rows without losing a top-k row. */
 int dhr_debug_query_margins(dhr_index* index, const dhr_query_batch* queries, float* out_host, void* stream);
 
+/* Debug/test hook: the bounds of the filter levels behind the bound GEMM, pair by pair.  Runs for rows [row_lo,row_hi) what one phase of a
+ * search runs -- the bound GEMM into the candidate lists, then the refine level on those lists -- and scatters both lists into DEVICE buffers
+ * [n_queries, row_hi-row_lo] fp32: out_u_dev the bound U of every row the filter listed, out_u2_dev the refined bound U2 of every row the
+ * refine level kept, NaN where a row is not in that list.  tau_host: HOST [n_queries] exact-score thresholds -- both levels compare with
+ * thr = tau - margin, as a search does -- or null: -inf, every row passes both levels.  flat: 0 = the refine kernel on a (block, query) grid,
+ * 1 = on the flat grid of the controller that only enqueues, n > 1 = on a flat grid of n workgroups.  out_thr_host: HOST [n_queries], the thr
+ * the levels compared with (may be null); out_unit_host: HOST [n_queries], the score units of one gated operand product of an int8 gated image
+ * (U and U2 of such an index differ by integer multiples of it plus real-valued products), zeros otherwise (may be null).  DHR_ERR_UNSUPPORTED where the batch has no refine level on this index (no gated columns and no
+ * residual image; a plain inner-product batch on an fp16 gated image), DHR_ERR_INVALID where the tiles of the row range hold more rows
+ * than a candidate list (32 768 by default, DHR_PARAM_CAND_CAP).  Overwrites the workspace of a staged search left open on the handle. */
+int dhr_debug_refine_bounds(dhr_index* index, const dhr_query_batch* queries, int64_t row_lo, int64_t row_hi, const float* tau_host,
+                            int32_t flat, float* out_u_dev, float* out_u2_dev, float* out_thr_host, float* out_unit_host, void* stream);
+
 /* Debug/test hook: how the main pass of the latest dhr_search on this handle seated its batch (DHR_PARAM_SEAT_QUERIES).  Returns 1 and fills the
  * HOST arrays ([n_slots] each, n_slots = that batch's query count rounded up to 256; any may be null) when the pass ran seated: slot -> query,
  * query -> slot, the per-query bound-list lengths of the sampled run the order was taken from, the slot-ordered threshold mirror and the

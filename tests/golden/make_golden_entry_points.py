@@ -13,6 +13,9 @@ Run at the commit whose behaviour is to be pinned:   python tests/golden/make_go
 The GPU recording is made twice: a run that finds entry_points_gpu.json keeps only the fields that come out equal to the file's and lists what it
 dropped under "_dropped" (ALLOWED_TO_DIFFER says what may stand there: pq_assign_kernel sums the training error with float atomics).
 
+The bad-argument exits of dhr_debug_refine_bounds came with that hook: its null-handle exit in the first file, the exits behind the handle check (bad
+range, null output, a range deeper than the candidate lists, a batch or an index without a refine level) as (status, error text) in the second.
+
 The index holds gated values that are integer multiples of 2^-6 (make_golden_index_build.py: the two-bucket deal of the default image is then the
 same in every build), so the bound scores and the filter margins are pinned too."""
 import contextlib
@@ -233,6 +236,7 @@ def _check_cases(lib, _lib):
         "score_rows_null_handle": lambda: lib.dhr_score_rows(None, qbp, 1, pout, pout, HOST, None),
         "debug_bound_scores_null_handle": lambda: lib.dhr_debug_bound_scores(None, qbp, 0, 1, pout, None),
         "debug_query_margins_null_handle": lambda: lib.dhr_debug_query_margins(None, qbp, pout, None),
+        "debug_refine_bounds_null_handle": lambda: lib.dhr_debug_refine_bounds(None, qbp, 0, 1, None, 0, pout, pout, None, None, None),
         "debug_gemm_time_null_handle": lambda: lib.dhr_debug_gemm_time(None, qbp, 1, C.byref(err), None, None),
         "sample_rank_null_handle": lambda: [lib.dhr_search_sample_rank(None, 10)],
         "union_rank_null_handle": lambda: [lib.dhr_search_union_rank(None, 10)],
@@ -386,6 +390,35 @@ def collect_search(G, _lib, torch):
             margin = np.full(NQ, 9.0, np.float32)
             _lib.check(lib.dhr_debug_query_margins(ix._h, C.byref(qb), margin.ctypes.data, None), "dhr_debug_query_margins")
             rec["margins_sha256"] = _digest(margin)
+            # dhr_debug_refine_bounds: the exits behind the handle check (what it computes: tests/test_refine_bounds.py)
+            u, u2 = torch.full((NQ, N), 9.0, dtype=torch.float32, device="cuda"), torch.full((NQ, N), 9.0, dtype=torch.float32, device="cuda")
+
+            def refine_exit(tag, h, batch, lo, hi, pu=u.data_ptr(), flat=0):
+                lib.dhr_merge_topk_host(0, 0, None, None, 0, None, None)          # a known error record in front of the call (collect_checks)
+                rec["refine_bounds_" + tag] = [int(lib.dhr_debug_refine_bounds(h, C.byref(batch), lo, hi, None, flat, pu, u2.data_ptr(), None, None, None)),
+                                               lib.dhr_last_error().decode()]
+
+            refine_exit("row_lo_negative", ix._h, qb, -1, 10)
+            refine_exit("row_hi_beyond_the_shard", ix._h, qb, 0, N + 1)
+            refine_exit("empty_range", ix._h, qb, 10, 10)
+            refine_exit("null_output", ix._h, qb, 0, N, pu=None)
+            refine_exit("flat_negative", ix._h, qb, 0, N, flat=-1)
+            refine_exit("plain_ip_batch", ix._h, qb_plain, 0, N)                 # refined on the int8 image of the gated half only
+            with _gated_i8(on):                                                  # 1536 rows against lists of 1024 entries
+                deep = G.GipIndex(np.concatenate([cv, cv[:536]]), np.concatenate([ci, ci[:536]]))
+            try:
+                deep.set_param(_lib.PARAM_CAND_CAP, 1024)
+                refine_exit("range_deeper_than_the_lists", deep._h, qb, 0, 1536)
+                refine_exit("range_that_fits_the_lists", deep._h, qb, 512, 1536)
+            finally:
+                deep.close()
+            dense = G.GipIndex(np.ascontiguousarray(cv[:, D_DLR:]), None)        # no gated columns, no residual image: no refine level
+            try:
+                qd = np.ascontiguousarray(qv[:, D_DLR:])
+                qb_dense, keep_dense = _lib.make_query_batch(qd, None)
+                refine_exit("index_without_a_refine_level", dense._h, qb_dense, 0, N)
+            finally:
+                dense.close()
             ms, flops = C.c_double(-1.0), C.c_double(-1.0)
             rec["gemm_time_status"] = int(lib.dhr_debug_gemm_time(ix._h, C.byref(qb), 1, C.byref(ms), C.byref(flops), None))
             rec["gemm_time_flops"] = float(flops.value).hex()

@@ -26,7 +26,7 @@ EXPORTS = ["dhr_version", "dhr_abi_sizes", "dhr_abi_size", "dhr_debug_fail_alloc
            "dhr_get_stats", "dhr_debug_bound_scores", "dhr_debug_query_margins", "dhr_debug_refine_bounds", "dhr_debug_query_seating", "dhr_debug_gemm_time", "dhr_debug_seq_to_tile", "dhr_debug_sharded_repairs", "dhr_search_sample_rank", "dhr_search_union_rank", "dhr_search_begin",
            "dhr_search_finish", "dhr_search_mid_ranks", "dhr_search_mid", "dhr_search_pre_ranks", "dhr_search_pre", "dhr_search_begin_rest", "dhr_search_rerank", "dhr_comm_unique_id", "dhr_comm_create", "dhr_comm_wrap", "dhr_comm_create_callback", "dhr_comm_destroy", "dhr_comm_info", "dhr_comm_abort", "dhr_search_sharded", "dhr_search_sharded_local", "dhr_search_sharded_host", "dhr_pq_create", "dhr_pq_destroy", "dhr_pq_device_bytes", "dhr_pq_search", "dhr_pq_adc_scores", "dhr_pq_last_scan", "dhr_index_save", "dhr_index_file_info", "dhr_index_load", "dhr_densify", "dhr_pq_train", "dhr_pq_encode", "dhr_pq_decode", "dhr_pq_train_nbits", "dhr_pq_encode_nbits", "dhr_pq_decode_nbits", "dhr_write_trec", "dhr_format_float", "dhr_lexical_head", "dhr_aggregate", "dhr_gip_scores_workspace", "dhr_gip_scores", "dhr_gip_scores_backward", "dhr_densify_backward", "dhr_lexical_head_train_workspace", "dhr_lexical_head_train", "dhr_lexical_head_backward", "dhr_maxsim_scores", "dhr_maxsim_scores_backward", "dhr_aggregate_train", "dhr_aggregate_backward", "dhr_term_weight_head",
            "dhr_term_weight_head_backward", "dhr_lexical_proj_workspace", "dhr_lexical_proj_head", "dhr_lexical_proj_train_workspace",
-           "dhr_lexical_proj_train", "dhr_lexical_proj_backward", "dhr_train_loss_workspace", "dhr_train_loss", "dhr_densify_sparse"]
+           "dhr_lexical_proj_train", "dhr_lexical_proj_backward", "dhr_train_loss_workspace", "dhr_train_loss", "dhr_densify_sparse", "dhr_exclude_rows", "dhr_search_excluding", "dhr_debug_exclude_chunk"]
 
 
 class DhrError(RuntimeError):
@@ -135,6 +135,15 @@ def load():
     lib.dhr_index_device_bytes.argtypes = [C.c_void_p]
     lib.dhr_index_device_bytes.restype = C.c_int64
     lib.dhr_search.argtypes = [C.c_void_p, C.POINTER(QueryBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    # device, mem_kind, n_queries, n_in, in_scores, in_rows, excl_ptr_host, excl_rows, k_out, out_scores, out_rows, out_valid, stream
+    if hasattr(lib, "dhr_exclude_rows"):           # (A/B libraries built from older sources lack the three)
+        lib.dhr_exclude_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        # index, queries, k, excl_ptr_host, excl_rows, excl_mem_kind, out_scores, out_rows, out_mem_kind, stream
+        lib.dhr_search_excluding.argtypes = [C.c_void_p, C.POINTER(QueryBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_void_p]
+        lib.dhr_debug_exclude_chunk.argtypes = []
+        lib.dhr_debug_exclude_chunk.restype = C.c_int32
     lib.dhr_search_rerank.argtypes = [C.c_void_p, C.POINTER(QueryBatch), C.POINTER(QueryBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_void_p]
     lib.dhr_index_save.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
@@ -334,3 +343,35 @@ def make_query_batch(value, index):
     else:
         qb.index, qb.ld_index, qb.index_dtype = None, 0, IDX_NONE
     return qb, (value, index)
+
+
+def make_exclusions(lists_or_csr):
+    """Per-query exclusion lists for dhr_exclude_rows / dhr_search_excluding -> (ptr, rows, mem_kind, keepalive): ptr a contiguous int64 HOST
+    array [Q + 1], rows the int64 global rows (a numpy array, or the torch cuda tensor that was handed in), mem_kind where rows live.
+    A TUPLE (ptr, rows) is a CSR -- rows a numpy array or a torch tensor (a cuda tensor stays on the device); anything else is a sequence of
+    per-query row sequences."""
+    if isinstance(lists_or_csr, tuple):
+        if len(lists_or_csr) != 2:
+            raise DhrError("an exclusion CSR is a (ptr, rows) pair")
+        ptr, rows = lists_or_csr
+        ptr = np.ascontiguousarray(ptr if isinstance(ptr, (np.ndarray, list)) else ptr.detach().cpu().numpy(), np.int64)
+        if isinstance(rows, (np.ndarray, list)):
+            rows, kind = np.ascontiguousarray(rows, np.int64), MEM_HOST
+        else:
+            if str(rows.dtype) != "torch.int64":
+                raise DhrError(f"exclusion rows must be int64, got {rows.dtype}")
+            rows = rows.contiguous()
+            kind = MEM_DEVICE if rows.is_cuda else MEM_HOST
+    else:
+        lists = [np.asarray(x, np.int64).reshape(-1) for x in lists_or_csr]
+        ptr = np.zeros(len(lists) + 1, np.int64)
+        if lists:
+            ptr[1:] = np.cumsum([len(x) for x in lists])
+        rows, kind = (np.concatenate(lists) if lists else np.zeros(0, np.int64)), MEM_HOST
+    if ptr.ndim != 1 or len(ptr) < 1 or len(rows.shape) != 1 or int(ptr[-1]) != int(rows.shape[0]):
+        raise DhrError(f"exclusion CSR: ptr ends at {int(ptr[-1]) if ptr.ndim == 1 and len(ptr) else None} but there are {tuple(rows.shape)} rows")
+    return ptr, rows, kind, (ptr, rows)
+
+
+def _data_ptr(a):
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()

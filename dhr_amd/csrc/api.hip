@@ -132,6 +132,61 @@ extern "C" int dhr_search(dhr_index* ix, const dhr_query_batch* qb, int32_t k, f
   });
 } DHR_CATCH_STATUS
 
+// dhr_search with per-query exclusion lists: the ordinary search at depth k + Emax (Emax: the longest list of the batch), its lists emitted into
+// the handle's grow-only staging buffer, the filter of exclude.hip behind it -- no kernel and no plan of the search itself is touched.  The
+// buffer holds [rows k' | scores k' | offsets | the caller's host rows | out rows k | out scores k] (the last three only where they are staged).
+extern "C" int dhr_search_excluding(dhr_index* ix, const dhr_query_batch* qb, int32_t k, const int64_t* excl_ptr_host, const int64_t* excl_rows,
+                                    int32_t excl_mem_kind, float* out_scores, int64_t* out_rows, int32_t out_mem_kind, void* stream) try {
+  dhr::alloc_checkpoint();
+  int rc = check_queries(ix, qb);
+  if (rc) return rc;
+  if (k <= 0) return set_error(DHR_ERR_INVALID, "k must be > 0");
+  if (!out_scores || !out_rows) return set_error(DHR_ERR_INVALID, "null output pointer");
+  if (!DHR_MEM_KIND_OK(out_mem_kind)) return set_error(DHR_ERR_INVALID, "bad out_mem_kind");
+  if (!DHR_MEM_KIND_OK(excl_mem_kind)) return set_error(DHR_ERR_INVALID, "bad excl_mem_kind");
+  const int Q = qb->n_queries;
+  int64_t e_max = 0, e_total = 0;
+  if ((rc = check_exclusions(Q, excl_ptr_host, excl_rows, &e_max, &e_total)) != DHR_OK) return rc;
+  if (e_max == 0) return dhr_search(ix, qb, k, out_scores, out_rows, out_mem_kind, stream);      // nothing to exclude: the plain search, bit for bit
+  if ((int64_t)k + e_max > (1 << 20))
+    return set_error(DHR_ERR_UNSUPPORTED, "k + the longest exclusion list = " + std::to_string(k) + " + " + std::to_string(e_max) +
+                                              " > 1048576 is not supported (split the batch: one long list deepens every query's search)");
+  const int kd = (int)(k + e_max);              // k' > 16384: global-memory merge (select_global.hip), as for any deep dhr_search
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t s = (hipStream_t)stream;
+  staged_set(ix, StagedState::None);
+  return timed_search(ix, Q, kd, s, [&](Timer& tm, dhr_search_stats& st) {
+    Workspace& w = ix->ws;
+    int rc = search_core(ix, w, qb, kd, 0, tm, st, s);
+    if (rc != DHR_OK) return rc;
+    const bool host_out = out_mem_kind == DHR_MEM_HOST, host_ex = excl_mem_kind == DHR_MEM_HOST;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_rows = 0, o_scores = o_rows + up16((size_t)Q * kd * 8), o_ptr = o_scores + up16((size_t)Q * kd * 4);
+    const size_t o_ex = o_ptr + up16((size_t)(Q + 1) * 8), o_orows = o_ex + (host_ex ? up16((size_t)e_total * 8) : 0);
+    const size_t o_oscores = o_orows + (host_out ? up16((size_t)Q * k * 8) : 0), need = o_oscores + (host_out ? up16((size_t)Q * k * 4) : 0);
+    if ((rc = grow(w.out_stage, w.out_stage_bytes, need, w.bytes)) != DHR_OK) return rc;
+    char* base = (char*)w.out_stage;
+    int64_t* d_rows = (int64_t*)(base + o_rows);
+    float* d_scores = (float*)(base + o_scores);
+    int64_t* d_ptr = (int64_t*)(base + o_ptr);
+    HIP_TRY(launch_emit(w.topk_keys, w.kp, Q, kd, ix->row_offset, d_scores, d_rows, s));
+    HIP_TRY(copy_in(d_ptr, excl_ptr_host, (size_t)(Q + 1) * 8, s));
+    const int64_t* d_ex = excl_rows;
+    if (host_ex) {
+      HIP_TRY(copy_in(base + o_ex, excl_rows, (size_t)e_total * 8, s));
+      d_ex = (const int64_t*)(base + o_ex);
+    }
+    int64_t* f_rows = host_out ? (int64_t*)(base + o_orows) : out_rows;
+    float* f_scores = host_out ? (float*)(base + o_oscores) : out_scores;
+    HIP_TRY(launch_exclude_rows(Q, kd, d_scores, d_rows, d_ptr, d_ex, e_max, k, f_scores, f_rows, nullptr, s));
+    if (host_out) {
+      HIP_TRY(stage_out(out_rows, f_rows, (size_t)Q * k * 8, s));
+      HIP_TRY(stage_out(out_scores, f_scores, (size_t)Q * k * 4, s));
+    }
+    return (int)DHR_OK;
+  });
+} DHR_CATCH_STATUS
+
 // Two-stage approximate GIP on the device (gip_retrieval.py:128-156): stage 1 is an ordinary search of the
 // restricted batch for k1 rows, stage 2 the exact gated inner product of the full batch on exactly those rows
 // and the top-k of that; the k1 rows never leave the device.

@@ -420,6 +420,10 @@ hipError_t launch_merge_topk(int n_queries, int n_in, const float* in_scores, co
 // the sharded search gathers [counts | scores | rows | status] blocks, so a rank's sections lie a whole block apart
 hipError_t launch_merge_lists(int n_queries, int n_lists, int list_len, const float* in_scores, const int64_t* in_rows, int k_out,
                               float* out_scores, int64_t* out_rows, hipStream_t s, int64_t stride_s = 0, int64_t stride_r = 0);
+// exclude.hip: per query, the first k_out pairs of its list [n_in] whose row is >= 0 and not in excl_rows[excl_ptr[q] .. excl_ptr[q+1]), in input order,
+// then (-inf, -1); out_valid [n_queries] (may be null): the pairs kept.  excl_ptr: DEVICE copy of the offsets; max_list: the longest list of the batch
+hipError_t launch_exclude_rows(int n_queries, int n_in, const float* in_scores, const int64_t* in_rows, const int64_t* excl_ptr, const int64_t* excl_rows,
+                               int64_t max_list, int k_out, float* out_scores, int64_t* out_rows, int32_t* out_valid, hipStream_t s);
 
 extern int g_gemm_variant;
 extern thread_local int g_last_gemm_kernel;      // kernels.hip: the bound-GEMM kernel of the calling thread's latest launch_gemm_filter

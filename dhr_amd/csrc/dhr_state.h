@@ -260,6 +260,8 @@ struct Timer {
 int ensure_ws(dhr_index* ix, Workspace& w, int n_queries, int k, int64_t keys_ld_min, int64_t cap_mult = 1, bool use_refine = true, bool queries_only = false);
 int check_queries(const dhr_index* ix, const dhr_query_batch* qb);
 int grow(void*& p, size_t& have, size_t need, int64_t& total);
+// exclude.hip: the host-side check of a batch's exclusion CSR (dhr_exclude_rows, dhr_search_excluding); the longest list and the row count come back
+int check_exclusions(int n_queries, const int64_t* excl_ptr_host, const int64_t* excl_rows, int64_t* max_list, int64_t* total);
 int prep_queries(dhr_index* ix, Workspace& w, const dhr_query_batch* qb, hipStream_t s);
 dhr::RescoreArgs base_rescore_args(const dhr_index* ix, const Workspace& w, int n_queries, bool gate);
 dhr::GemmArgs base_gemm_args(const dhr_index* ix, const Workspace& w, int n_queries);      // the caller adds the tile range and its mapping, the thresholds and lists, the dump

@@ -127,9 +127,12 @@ class GipIndex:
         _lib.check(self._lib.dhr_get_stats(self._h, C.byref(st)), "dhr_get_stats")
         return st.as_dict()
 
-    def search(self, q_value, q_index, k: int, *, out_device: bool = False, stream: int = 0):
+    def search(self, q_value, q_index, k: int, *, out_device: bool = False, stream: int = 0, exclude=None):
         """-> (scores fp32 [Q,k], rows int64 [Q,k]); rows are global (row_offset added), best first,
-        (-inf, -1) padding when k > n_rows.  numpy outputs unless out_device (then torch cuda tensors)."""
+        (-inf, -1) padding when k > n_rows.  numpy outputs unless out_device (then torch cuda tensors).
+        exclude: per-query lists of global rows that query must not return (_lib.make_exclusions: a list of row sequences or a (ptr, rows)
+        CSR tuple) -- dhr_search_excluding: the search runs k + the longest list deep and is filtered on the device, so a batch with one very
+        long list is better split."""
         qb, keep = self._qb(q_value, q_index)
         nq = qb.n_queries
         if out_device:
@@ -142,9 +145,53 @@ class GipIndex:
             scores = np.empty((nq, k), np.float32)
             rows = np.empty((nq, k), np.int64)
             ps, pr, kind = scores.ctypes.data, rows.ctypes.data, _lib.MEM_HOST
-        _lib.check(self._lib.dhr_search(self._h, C.byref(qb), int(k), ps, pr, kind, stream), "dhr_search")
+        if exclude is None:
+            _lib.check(self._lib.dhr_search(self._h, C.byref(qb), int(k), ps, pr, kind, stream), "dhr_search")
+        else:
+            e_ptr, e_rows, e_kind, e_keep = _lib.make_exclusions(exclude)
+            if len(e_ptr) != nq + 1:
+                raise ValueError(f"{len(e_ptr) - 1} exclusion lists for {nq} queries")
+            _lib.check(self._lib.dhr_search_excluding(self._h, C.byref(qb), int(k), e_ptr.ctypes.data, _lib._data_ptr(e_rows), e_kind, ps, pr, kind,
+                                                      stream), "dhr_search_excluding")
+            del e_keep
         del keep
         return scores, rows
+
+    def exclude_rows(self, scores, rows, exclude, k: int, *, stream: int = 0, return_valid: bool = False):
+        """Ranked lists that came from elsewhere (search_rerank, a PQ search, a merge) without the rows of `exclude` (as in search): scores fp32
+        [Q, n], rows int64 [Q, n] global rows, both numpy or both torch cuda tensors -> (scores [Q, k], rows [Q, k]) of the same kind: the first k surviving pairs in
+        their order, (-inf, -1) behind them; return_valid adds valid int32 [Q], the pairs each query kept (dhr_exclude_rows)."""
+        on_host = isinstance(scores, np.ndarray)
+        if on_host != isinstance(rows, np.ndarray):
+            raise ValueError("scores and rows must live in the same memory kind")
+        if tuple(scores.shape) != tuple(rows.shape) or len(scores.shape) != 2:
+            raise ValueError(f"scores {tuple(scores.shape)} and rows {tuple(rows.shape)} must be the same [Q, n]")
+        nq, n = int(scores.shape[0]), int(scores.shape[1])
+        e_ptr, e_rows, e_kind, e_keep = _lib.make_exclusions(exclude)
+        if len(e_ptr) != nq + 1:
+            raise ValueError(f"{len(e_ptr) - 1} exclusion lists for {nq} queries")
+        if on_host:
+            scores, rows = np.ascontiguousarray(scores, np.float32), np.ascontiguousarray(rows, np.int64)
+            if e_kind != _lib.MEM_HOST:
+                e_rows = e_rows.cpu().numpy()
+            out_s, out_r, out_v = np.empty((nq, k), np.float32), np.empty((nq, k), np.int64), np.empty((nq,), np.int32)
+            kind = _lib.MEM_HOST
+        else:
+            import torch
+            if not scores.is_cuda or not rows.is_cuda or scores.dtype != torch.float32 or rows.dtype != torch.int64:
+                raise ValueError("torch lists must be cuda tensors, float32 scores and int64 rows")
+            scores, rows = scores.contiguous(), rows.contiguous()
+            if e_kind != _lib.MEM_DEVICE:
+                e_rows = torch.as_tensor(e_rows, dtype=torch.int64).to(scores.device)
+            out_s = torch.empty((nq, k), dtype=torch.float32, device=scores.device)
+            out_r = torch.empty((nq, k), dtype=torch.int64, device=scores.device)
+            out_v = torch.empty((nq,), dtype=torch.int32, device=scores.device)
+            kind = _lib.MEM_DEVICE
+        _lib.check(self._lib.dhr_exclude_rows(self.device, kind, nq, n, _lib._data_ptr(scores), _lib._data_ptr(rows), e_ptr.ctypes.data,
+                                              _lib._data_ptr(e_rows), int(k), _lib._data_ptr(out_s), _lib._data_ptr(out_r), _lib._data_ptr(out_v),
+                                              stream), "dhr_exclude_rows")
+        del e_keep
+        return (out_s, out_r, out_v) if return_valid else (out_s, out_r)
 
     def search_rerank(self, q1_value, q1_index, q_value, q_index, k1: int, k: int, *, stream: int = 0):
         """Two-stage search on the device (dhr_search_rerank): top-k1 of the stage-1 batch, exact GIP of the full
@@ -325,6 +372,23 @@ def _sl(a, lo, hi):
     return None if a is None else a[lo:hi]
 
 
+def self_exclusions(qids, docids, row_base=0):
+    """--exclude_self: per query the (global) rows whose docid equals the query id -- none for most query sets, one where the queries are
+    corpus documents (arguana, quora; a corpus searched against itself)."""
+    wanted = set(qids)
+    rows_of = {}
+    for row, docid in enumerate(docids):
+        if docid in wanted:
+            rows_of.setdefault(docid, []).append(row + row_base)
+    return [np.asarray(rows_of.get(qid, ()), np.int64) for qid in qids]
+
+
+def _excl(args, lo, hi):
+    """the exclusion lists of queries [lo, hi) (main() with --exclude_self), or None"""
+    lists = getattr(args, "_exclude", None)
+    return None if lists is None else lists[lo:hi]
+
+
 def _corpus_index(corpus_embs, corpus_arg_idxs, args):
     if isinstance(corpus_embs, GipIndex):
         return corpus_embs, False
@@ -337,7 +401,7 @@ def IP_retrieval(qids, query_embs, corpus_embs, args):
     corpus_embs: array/tensor [N,K] or a prebuilt GipIndex (dense-only)."""
     index, owned = _corpus_index(corpus_embs, None, args)
     start_time = time.time()
-    scores, rows = _by_chunks(len(qids), lambda lo, hi: index.search(query_embs[lo:hi], None, args.topk))
+    scores, rows = _by_chunks(len(qids), lambda lo, hi: index.search(query_embs[lo:hi], None, args.topk, exclude=_excl(args, lo, hi)))
     res = _to_dicts(qids, rows, scores, index.row_offset, args)
     time_per_query = (time.time() - start_time) / len(qids)
     print('Retrieving {} queries ({:0.3f} s/query), average number of index use {}'.format(len(qids), time_per_query, 0.0))
@@ -361,7 +425,8 @@ def GIP_retrieval(qids, query_embs, query_arg_idxs, corpus_embs, corpus_arg_idxs
             if args.topk > n and not getattr(args, "allow_short", False):
                 raise RuntimeError("selected index k out of range")          # torch.topk, :123
             total_num_idx = args.emb_dim * len(qids)
-            scores, rows = _by_chunks(len(qids), lambda lo, hi: index.search(query_embs[lo:hi], _sl(query_arg_idxs, lo, hi), args.topk))
+            scores, rows = _by_chunks(len(qids), lambda lo, hi: index.search(query_embs[lo:hi], _sl(query_arg_idxs, lo, hi), args.topk,
+                                                                              exclude=_excl(args, lo, hi)))
         else:
             q = _np(query_embs).astype(np.float32)
             qi = _np(query_arg_idxs)
@@ -373,9 +438,15 @@ def GIP_retrieval(qids, query_embs, query_arg_idxs, corpus_embs, corpus_arg_idxs
             else:
                 q1, qi1 = q, None                                             # ungated inner product
             def two_stage(lo, hi):
+                excl = _excl(args, lo, hi)
                 if args.rerank:
-                    return index.search_rerank(q1[lo:hi], _sl(qi1, lo, hi), q[lo:hi], qi[lo:hi], k1, min(args.topk, k1))   # both stages on the device
-                return index.search(q1[lo:hi], _sl(qi1, lo, hi), k1)
+                    k2 = min(args.topk, k1)
+                    if excl is None:
+                        return index.search_rerank(q1[lo:hi], _sl(qi1, lo, hi), q[lo:hi], qi[lo:hi], k1, k2)   # both stages on the device
+                    # one row deeper from the last stage, the query's own row filtered out of that list on the device
+                    s2, r2 = index.search_rerank(q1[lo:hi], _sl(qi1, lo, hi), q[lo:hi], qi[lo:hi], k1, min(k2 + 1, k1))
+                    return index.exclude_rows(s2, r2, excl, k2)
+                return index.search(q1[lo:hi], _sl(qi1, lo, hi), k1, exclude=excl)
             scores, rows = _by_chunks(len(qids), two_stage)
         res = _to_dicts(qids, rows, scores, index.row_offset, args)
     finally:
@@ -408,12 +479,18 @@ def PQ_IP_retrieval(qids, query_embs, query_arg_idxs, corpus_embs, corpus_arg_id
         qi_np = _np(query_arg_idxs)
 
         def pq_stage(lo, hi):
+            excl = _excl(args, lo, hi)
+            deep = args.topk + (0 if excl is None else 1)        # --exclude_self: one row deeper from the last stage, filtered below
             s1, r1 = pq_index.search(q[lo:hi], k1)
             if not args.rerank:
-                return s1[:, : args.topk], r1[:, : args.topk]
-            s2 = index.score_rows(q[lo:hi], qi_np[lo:hi], r1)
-            order = np.lexsort((r1, -s2.astype(np.float64)), axis=1)[:, : args.topk]
-            return np.take_along_axis(s2, order, axis=1), np.take_along_axis(r1, order, axis=1)
+                s2, r2 = s1[:, :deep], r1[:, :deep]
+            else:
+                s2 = index.score_rows(q[lo:hi], qi_np[lo:hi], r1)
+                order = np.lexsort((r1, -s2.astype(np.float64)), axis=1)[:, :deep]
+                s2, r2 = np.take_along_axis(s2, order, axis=1), np.take_along_axis(r1, order, axis=1)
+            if excl is None:
+                return s2, r2
+            return index.exclude_rows(s2, r2, excl, min(args.topk, r2.shape[1]))
         scores, rows = _by_chunks(len(qids), pq_stage)
         res = _to_dicts(qids, rows, scores, index.row_offset, args)
     finally:
@@ -451,6 +528,9 @@ def build_parser():
     parser.add_argument("--save_device_index", type=str, default=None,
                         help="(not in the reference) also write the built index as a device-ready file; pass that file as "
                              "--index_path later to skip the pickle load and the re-layout")
+    parser.add_argument("--exclude_self", action='store_true',
+                        help="(not in the reference, which drops the docid == query_id line while writing the run and leaves a gap in the "
+                             "ranks) a query whose id is a corpus docid never retrieves that row: k results, ranks 1..k")
     parser.add_argument("--output", type=str, default=None, help="override the result file name")
     return parser
 
@@ -562,6 +642,8 @@ def main(argv=None):
             index = GipIndex(corpus_embs, None, device=args.device)
         if args.save_device_index:
             index.save(args.save_device_index, docids)
+    if args.exclude_self:
+        args._exclude = self_exclusions(qids, docids, index.row_offset)
     if query_arg_idxs is not None:
         if not args.PQIP:
             results, scores = GIP_retrieval(qids, query_embs, query_arg_idxs, index, None, args)

@@ -102,12 +102,16 @@ def recall_cap(qrels, results, k_values):
 
 def read_qrels_any(path):
     """Qrels in either of the two layouts the reference's pipelines use: the tab-separated 4 columns of rcap_eval.py:11-18, or the
-    space-separated TREC layout `qid 0 docid rel` that trec_eval reads (docs/dhr/msmarco-passage-train-eval.md:153-154)."""
+    space-separated TREC layout `qid 0 docid rel` that trec_eval reads (docs/dhr/msmarco-passage-train-eval.md:153-154).  A line of two
+    columns, `qid pid`, is a positive pair (rel = 1): the layout of the positives a hard-negative mining run excludes (mine_negatives.py)."""
     qrels = {}
     with open(path, 'r') as f:
         for line in f:
             fields = line.split()
             if not fields:
+                continue
+            if len(fields) == 2:
+                qrels.setdefault(fields[0], {})[fields[1]] = 1
                 continue
             if len(fields) != 4:
                 raise ValueError('{}: expected 4 fields per line, got {!r}'.format(path, line))

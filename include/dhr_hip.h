@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DHR_VERSION 105 /* 0.1.5: exception barrier on every entry point (DHR_ERR_NOMEM), a failed sharded step is collective (DHR_ERR_PEER), dhr_abi_size, dhr_host_shard::struct_size, dhr_comm_abort no longer frees the handle, counts + list prefixes in ONE all-gather; 0.1.4: dhr_search_pre / dhr_search_pre_ranks / dhr_search_begin_rest (first agreement of the sharded search in two rounds), dhr_host_shard::pre_ranks / pre / begin_rest, DHR_PARAM_LIST_STRIDE; 0.1.3: dhr_comm_info / dhr_comm_abort */
+#define DHR_VERSION 105 /* 0.1.5 (entry points added since, none changed: the number stands): dhr_exclude_rows / dhr_search_excluding / dhr_debug_exclude_chunk (per-query row exclusion); 0.1.5: exception barrier on every entry point (DHR_ERR_NOMEM), a failed sharded step is collective (DHR_ERR_PEER), dhr_abi_size, dhr_host_shard::struct_size, dhr_comm_abort no longer frees the handle, counts + list prefixes in ONE all-gather; 0.1.4: dhr_search_pre / dhr_search_pre_ranks / dhr_search_begin_rest (first agreement of the sharded search in two rounds), dhr_host_shard::pre_ranks / pre / begin_rest, DHR_PARAM_LIST_STRIDE; 0.1.3: dhr_comm_info / dhr_comm_abort */
 
 typedef enum dhr_status {
   DHR_OK = 0,
@@ -225,6 +225,37 @@ int dhr_search(dhr_index* index, const dhr_query_batch* queries, int32_t k, floa
  * Same n_queries in both batches; 0 < k <= k1 <= 1048576 (above 16384 the global-memory merge, slower). */
 int dhr_search_rerank(dhr_index* index, const dhr_query_batch* stage1, const dhr_query_batch* full, int32_t k1, int32_t k,
                       float* out_scores, int64_t* out_rows, int32_t out_mem_kind, void* stream);
+
+/* Per-query row exclusion (hard-negative mining: a query's positives; corpora searched against themselves: the query's own row).
+ * Exclusion lists are a CSR: excl_ptr_host int64 [n_queries + 1], a HOST array whatever the memory kind of the rest (as weights / teacher_split
+ * of dhr_train_loss: the host needs the longest list to size the launch and the search depth without a hidden device read; it is read before
+ * the call returns), offsets from 0 and never decreasing; excl_rows int64 GLOBAL rows in mem_kind memory, in any order, repeats allowed; rows
+ * < 0 and rows that occur in no list are ignored (a -1 never matches padding).  excl_rows may be NULL when every list is empty.
+ *
+ * dhr_exclude_rows: drops from each query's ranked list the rows of its exclusion list and keeps the k_out best of the rest (input order kept).
+ *   in_scores / in_rows [n_queries, n_in], best first, entries with row < 0 are padding (anywhere) and are dropped too; out_scores / out_rows
+ *   [n_queries, k_out]: the first k_out surviving pairs, then (-inf, -1); out_valid int32 [n_queries] (may be NULL): the pairs written.  Serves
+ *   the lists of dhr_search_rerank, dhr_pq_search, the sharded calls and the merges: ask them for k + E rows and filter.  All arrays but
+ *   excl_ptr_host live in mem_kind memory; input and output must not overlap.  Device arrays: the call ENQUEUES on `stream` and returns without
+ *   waiting (its one scratch block is allocated and freed in stream order); host arrays are staged through the device and complete on return.
+ *   One workgroup per query; the list is staged into LDS in chunks of DHR_EXCLUDE_CHUNK rows (dhr_debug_exclude_chunk returns the constant the
+ *   library was built with), a longer list costs further passes; no atomics on global memory: two calls on the same arguments are bit-identical.
+ *   DHR_ERR_INVALID: a NULL pointer, excl_ptr_host[0] != 0, a decreasing excl_ptr_host, n_in <= 0, k_out <= 0 or k_out > n_in, an unknown
+ *   mem_kind; DHR_ERR_UNSUPPORTED: n_in > 1048576 together with a list longer than one chunk.
+ * dhr_search_excluding: dhr_search, except that query q never returns a row of excl_rows[excl_ptr[q] .. excl_ptr[q+1]).  Runs the ordinary
+ *   search at depth k' = k + Emax (Emax: the longest list of the batch) into scratch of the handle, filters, and delivers [n_queries, k] to
+ *   out_mem_kind memory; excl_rows lives in excl_mem_kind memory.  Exact by construction: the top k' holds at most Emax excluded rows, hence
+ *   at least min(k, live rows) others, and they are the best of the others in the library's order.  Emax == 0 IS dhr_search (bit for bit).
+ *   k' > 1048576: DHR_ERR_UNSUPPORTED; k' > 16384 takes the global-memory select of any deep dhr_search (slower); k' > n_rows relies on the
+ *   (-inf, -1) tail.  ONE long list deepens the search of the whole batch: a caller with a few queries of thousands of exclusions puts them
+ *   in a batch of their own.  Afterwards dhr_get_stats describes the underlying search at depth k'. */
+#define DHR_EXCLUDE_CHUNK 2048 /* rows of an exclusion list per LDS pass of dhr_exclude_rows */
+int dhr_exclude_rows(int32_t device, int32_t mem_kind, int32_t n_queries, int32_t n_in, const float* in_scores, const int64_t* in_rows,
+                     const int64_t* excl_ptr_host, const int64_t* excl_rows, int32_t k_out, float* out_scores, int64_t* out_rows,
+                     int32_t* out_valid, void* stream);
+int dhr_search_excluding(dhr_index* index, const dhr_query_batch* queries, int32_t k, const int64_t* excl_ptr_host, const int64_t* excl_rows,
+                         int32_t excl_mem_kind, float* out_scores, int64_t* out_rows, int32_t out_mem_kind, void* stream);
+int32_t dhr_debug_exclude_chunk(void);
 
 /* Staged form of dhr_search for the row-sharded path (one handle per shard / rank).  After
  * dhr_search_begin every shard holds the r best exact scores of its SAMPLE per query (r =

@@ -790,6 +790,27 @@ int dhr_search_sharded(dhr_index* shard, dhr_comm* comm, const dhr_query_batch* 
 int dhr_search_sharded_local(dhr_index** shards, int32_t n_shards, const dhr_query_batch* queries, int32_t k, float* out_scores,
                              int64_t* out_rows, int32_t out_mem_kind, void* stream);
 
+/* k-means over whole fp16 rows (kmeans.hip): the clustering behind the query-cluster files of topic-aware sampling.
+ *   values [n, d] fp16 with row stride ld >= d (elements; a column range of a wider record is selected through the base pointer and ld, the
+ *   base need not be aligned), centroids [K, d] fp32 packed.  1 <= d <= 4096, 1 <= K <= 65536, 1 <= n < 2^31; K > n is legal.  mem_kind says
+ *   where EVERY array of the call lives: host arrays are staged through the device and complete on return, device arrays are only enqueued on
+ *   `stream` and nothing waits.  Every output is a function of the arguments alone (no atomics): two calls give the same bits.
+ * dhr_kmeans_assign: assign[i] = the j with the largest t(i, j) = <x_i, c_j> - 1/2 |c_j|^2 (the nearest centroid), the lowest such j on a tie;
+ *   dist[i] = |x_i|^2 - 2 t(i, assign[i]) (dist may be NULL).  No [n, K] array is made; device scratch is O(K * d).
+ * dhr_kmeans_update: centroid j becomes the fp32 mean of its members, added in increasing row order; a cluster without members keeps the centroid
+ *   it came with and gets counts[j] = 0.  An assign entry outside [0, K) is DHR_ERR_INVALID for host arrays; in device arrays, which are not read
+ *   back, such a row joins no cluster.
+ * dhr_kmeans: exactly `iters` (>= 0) rounds of assign + update, then one last assign against the final centroids (no early stop: that would need
+ *   a device read per round).  objective[t], t in [0, iters], is the float64 sum of dist after the t-th assignment, summed in a fixed order;
+ *   changed[t] the number of rows whose assignment differs from the round before, changed[0] = n.  assign, counts and objective[iters]
+ *   describe the final centroids. */
+int dhr_kmeans_assign(int32_t device, int32_t mem_kind, const void* values, int64_t ld, int64_t n, int32_t d, const float* centroids, int32_t K,
+                      int32_t* assign, float* dist, void* stream);
+int dhr_kmeans_update(int32_t device, int32_t mem_kind, const void* values, int64_t ld, int64_t n, int32_t d, const int32_t* assign, int32_t K,
+                      float* centroids, int64_t* counts, void* stream);
+int dhr_kmeans(int32_t device, int32_t mem_kind, const void* values, int64_t ld, int64_t n, int32_t d, int32_t K, int32_t iters, float* centroids,
+               int32_t* assign, int64_t* counts, double* objective, int64_t* changed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ import subprocess
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libdhr_hip.so")
 OBJDIR = os.path.join(CSRC, "build")
-SOURCES = ["abi.cpp", "kernels.hip", "gemm_w4.hip", "gemm_g8.hip", "index_build.hip", "search_core.hip", "api.hip", "sharded.hip", "pq_adc.hip", "select_global.hip", "host_io.hip", "lexical.hip", "gip_train.hip", "lexical_train.hip", "maxsim.hip", "aggretriever_train.hip", "lexical_proj.hip", "lexical_proj_train.hip", "train_loss.hip", "densify_sparse.hip", "exclude.hip", "kmeans.hip"]
+SOURCES = ["abi.cpp", "kernels.hip", "gemm_w4.hip", "gemm_g8.hip", "index_build.hip", "search_core.hip", "api.hip", "sharded.hip", "pq_adc.hip", "select_global.hip", "host_io.hip", "lexical.hip", "gip_train.hip", "lexical_train.hip", "maxsim.hip", "aggretriever_train.hip", "lexical_proj.hip", "lexical_proj_train.hip", "train_loss.hip", "densify_sparse.hip", "exclude.hip", "kmeans.hip", "stream_search.hip"]
 HEADERS = ["dhr_internal.h", "dhr_state.h", "search_plan.h", "seating.h", "index_layout.h", "sharded_plan.h", "host_stage.h", "op_dispatch.h", "abi_guard.h", "libdhr.map", "gemm_common.h", "gemm_g8.h", "lexical_common.h", "lexical_proj_common.h", "lexical_proj_layout.h", os.path.join("..", "..", "include", "dhr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 # A/B builds only (DHR_AB_VARIANTS=1 in the environment of the build, tools/ab_build.sh): the retired persistent-workgroup form of the integer

@@ -27,7 +27,8 @@ EXPORTS = ["dhr_version", "dhr_abi_sizes", "dhr_abi_size", "dhr_debug_fail_alloc
            "dhr_search_finish", "dhr_search_mid_ranks", "dhr_search_mid", "dhr_search_pre_ranks", "dhr_search_pre", "dhr_search_begin_rest", "dhr_search_rerank", "dhr_comm_unique_id", "dhr_comm_create", "dhr_comm_wrap", "dhr_comm_create_callback", "dhr_comm_destroy", "dhr_comm_info", "dhr_comm_abort", "dhr_search_sharded", "dhr_search_sharded_local", "dhr_search_sharded_host", "dhr_pq_create", "dhr_pq_destroy", "dhr_pq_device_bytes", "dhr_pq_search", "dhr_pq_adc_scores", "dhr_pq_last_scan", "dhr_index_save", "dhr_index_file_info", "dhr_index_load", "dhr_densify", "dhr_pq_train", "dhr_pq_encode", "dhr_pq_decode", "dhr_pq_train_nbits", "dhr_pq_encode_nbits", "dhr_pq_decode_nbits", "dhr_write_trec", "dhr_format_float", "dhr_lexical_head", "dhr_aggregate", "dhr_gip_scores_workspace", "dhr_gip_scores", "dhr_gip_scores_backward", "dhr_densify_backward", "dhr_lexical_head_train_workspace", "dhr_lexical_head_train", "dhr_lexical_head_backward", "dhr_maxsim_scores", "dhr_maxsim_scores_backward", "dhr_aggregate_train", "dhr_aggregate_backward", "dhr_term_weight_head",
            "dhr_term_weight_head_backward", "dhr_lexical_proj_workspace", "dhr_lexical_proj_head", "dhr_lexical_proj_train_workspace",
            "dhr_lexical_proj_train", "dhr_lexical_proj_backward", "dhr_train_loss_workspace", "dhr_train_loss", "dhr_densify_sparse", "dhr_exclude_rows", "dhr_search_excluding", "dhr_debug_exclude_chunk",
-           "dhr_kmeans_assign", "dhr_kmeans_update", "dhr_kmeans"]
+           "dhr_kmeans_assign", "dhr_kmeans_update", "dhr_kmeans",
+           "dhr_stream_search_create", "dhr_stream_search_add", "dhr_stream_search_result", "dhr_stream_search_device_bytes", "dhr_stream_search_destroy"]
 
 
 class DhrError(RuntimeError):
@@ -151,6 +152,17 @@ def load():
         lib.dhr_kmeans_update.argtypes = rows + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]      # assign, K, centroids, counts, stream
         # K, iters, centroids, assign, counts, objective, changed, stream
         lib.dhr_kmeans.argtypes = rows + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "dhr_stream_search_create"):   # (A/B libraries built from older sources lack the five)
+        seg = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]                # a, ld_a, b, ld_b, value_dtype
+        # device, mem_kind, queries, n_queries, d_a, d_b, k, block_rows, out, stream
+        lib.dhr_stream_search_create.argtypes = [C.c_int32, C.c_int32] + seg + [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                                 C.POINTER(C.c_void_p), C.c_void_p]
+        lib.dhr_stream_search_add.argtypes = [C.c_void_p, C.c_int32] + seg + [C.c_int64, C.c_int64, C.c_void_p]      # n_rows, row_base, stream
+        lib.dhr_stream_search_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.dhr_stream_search_device_bytes.argtypes = [C.c_void_p]
+        lib.dhr_stream_search_device_bytes.restype = C.c_int64
+        lib.dhr_stream_search_destroy.argtypes = [C.c_void_p]
+        lib.dhr_stream_search_destroy.restype = None
     lib.dhr_search_rerank.argtypes = [C.c_void_p, C.POINTER(QueryBatch), C.POINTER(QueryBatch), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_void_p]
     lib.dhr_index_save.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]

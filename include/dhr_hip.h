@@ -811,6 +811,32 @@ int dhr_kmeans_update(int32_t device, int32_t mem_kind, const void* values, int6
 int dhr_kmeans(int32_t device, int32_t mem_kind, const void* values, int64_t ld, int64_t n, int32_t d, int32_t K, int32_t iters, float* centroids,
                int32_t* assign, int64_t* counts, double* objective, int64_t* changed, void* stream);
 
+/* Streamed exact inner-product search over fp32 vectors of any width (stream_search.hip): the retrieval route that scores un-densified vectors,
+ * [lexical reps over the whole vocabulary | semantic reps], chunk by chunk with a running top-k per query.
+ *   score(q, r) = sum_c qa[q][c] pa[r][c] + sum_c qb[q][c] pb[r][c] over two column segments of d_a >= 1 and d_b >= 0 columns (q_b / p_b NULL
+ *   exactly when d_b = 0), d_a + d_b <= 131072; fp32 rows with row strides (elements), any alignment.  value_dtype is DHR_VAL_F32; DHR_VAL_F16 is
+ *   DHR_ERR_UNSUPPORTED.  1 <= n_queries <= 65536, 1 <= k <= 4096 (larger k: DHR_ERR_UNSUPPORTED).  block_rows: passage rows scored between two
+ *   selects, 0 for the default, else a multiple of 128 in [128, 65536]; device memory is 4 (n_queries + block_rows) (d_a + d_b) bytes of fp16
+ *   images, 8 n_queries block_rows of candidates and the lists.
+ *   A score is a function of its query row and its passage row alone, bit for bit: it does not depend on the call or block a row arrived in, on
+ *   the order of the calls or on block_rows.  Its error is at most 2^-15 sum_c |q_c p_c| (tests/test_stream_search.py derives the bound).  A row
+ *   that holds a NaN or an infinity gets what IEEE arithmetic gives; a NaN score enters no list and changes no other score.
+ * dhr_stream_search_create: splits the queries; the lists start as (-inf, -1).
+ * dhr_stream_search_add: scores n_rows passages (n_rows = 0: DHR_OK, nothing is launched) against every query and merges them into the lists;
+ *   their rows are reported as row_base + position.  mem_kind says where the arrays of THIS call live: host arrays are staged through the
+ *   device block by block and the call is complete on return; device arrays are only enqueued on `stream`.
+ * dhr_stream_search_result: the k best rows of every query over everything added so far, score descending, row ascending on exact ties,
+ *   (-inf, -1) beyond the rows seen; out_scores [n_queries, k], out_rows [n_queries, k].  May be called any number of times and does not end the
+ *   search. */
+typedef struct dhr_stream_search dhr_stream_search;
+int dhr_stream_search_create(int32_t device, int32_t mem_kind, const void* q_a, int64_t ld_qa, const void* q_b, int64_t ld_qb, int32_t value_dtype,
+                             int32_t n_queries, int32_t d_a, int32_t d_b, int32_t k, int32_t block_rows, dhr_stream_search** out, void* stream);
+int dhr_stream_search_add(dhr_stream_search* s, int32_t mem_kind, const void* p_a, int64_t ld_pa, const void* p_b, int64_t ld_pb, int32_t value_dtype,
+                          int64_t n_rows, int64_t row_base, void* stream);
+int dhr_stream_search_result(dhr_stream_search* s, float* out_scores, int64_t* out_rows, int32_t out_mem_kind, void* stream);
+int64_t dhr_stream_search_device_bytes(const dhr_stream_search* s);
+void dhr_stream_search_destroy(dhr_stream_search* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ INFO_DENSE_I8, INFO_I8_SCALE, INFO_I8_ROW_ERR, INFO_I8_ROW_NORM, INFO_ROW_NORM_M
 
 EXPORTS = ["dhr_version", "dhr_abi_sizes", "dhr_abi_size", "dhr_debug_fail_alloc", "dhr_set_option", "dhr_index_get_info", "dhr_last_error", "dhr_index_create", "dhr_index_destroy", "dhr_index_set_param",
            "dhr_index_device_bytes", "dhr_search", "dhr_score_rows", "dhr_merge_topk", "dhr_merge_topk_host", "dhr_merge_topk_lists", "dhr_merge_topk_lists_host",
-           "dhr_get_stats", "dhr_debug_bound_scores", "dhr_debug_query_margins", "dhr_debug_refine_bounds", "dhr_debug_query_seating", "dhr_debug_gemm_time", "dhr_debug_seq_to_tile", "dhr_debug_sharded_repairs", "dhr_search_sample_rank", "dhr_search_union_rank", "dhr_search_begin",
+           "dhr_get_stats", "dhr_debug_bound_scores", "dhr_debug_query_margins", "dhr_debug_refine_bounds", "dhr_debug_select_merge", "dhr_debug_query_seating", "dhr_debug_gemm_time", "dhr_debug_seq_to_tile", "dhr_debug_sharded_repairs", "dhr_search_sample_rank", "dhr_search_union_rank", "dhr_search_begin",
            "dhr_search_finish", "dhr_search_mid_ranks", "dhr_search_mid", "dhr_search_pre_ranks", "dhr_search_pre", "dhr_search_begin_rest", "dhr_search_rerank", "dhr_comm_unique_id", "dhr_comm_create", "dhr_comm_wrap", "dhr_comm_create_callback", "dhr_comm_destroy", "dhr_comm_info", "dhr_comm_abort", "dhr_search_sharded", "dhr_search_sharded_local", "dhr_search_sharded_host", "dhr_pq_create", "dhr_pq_destroy", "dhr_pq_device_bytes", "dhr_pq_search", "dhr_pq_adc_scores", "dhr_pq_last_scan", "dhr_index_save", "dhr_index_file_info", "dhr_index_load", "dhr_densify", "dhr_pq_train", "dhr_pq_encode", "dhr_pq_decode", "dhr_pq_train_nbits", "dhr_pq_encode_nbits", "dhr_pq_decode_nbits", "dhr_write_trec", "dhr_format_float", "dhr_lexical_head", "dhr_aggregate", "dhr_gip_scores_workspace", "dhr_gip_scores", "dhr_gip_scores_backward", "dhr_densify_backward", "dhr_lexical_head_train_workspace", "dhr_lexical_head_train", "dhr_lexical_head_backward", "dhr_maxsim_scores", "dhr_maxsim_scores_backward", "dhr_aggregate_train", "dhr_aggregate_backward", "dhr_term_weight_head",
            "dhr_term_weight_head_backward", "dhr_lexical_proj_workspace", "dhr_lexical_proj_head", "dhr_lexical_proj_train_workspace",
            "dhr_lexical_proj_train", "dhr_lexical_proj_backward", "dhr_train_loss_workspace", "dhr_train_loss", "dhr_densify_sparse", "dhr_exclude_rows", "dhr_search_excluding", "dhr_debug_exclude_chunk",
@@ -281,6 +281,10 @@ def load():
     # index, queries, row_lo, row_hi, tau_host, flat, out_u_dev, out_u2_dev, out_thr_host, out_unit_host, stream
     lib.dhr_debug_refine_bounds.argtypes = [C.c_void_p, C.POINTER(QueryBatch), C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "dhr_debug_select_merge"):     # (A/B libraries built from older sources lack it)
+        # device, n_queries, k, k_keep, kp, kps, sort_n, monotone, topk_keys_dev, in_keys_dev, ld_keys, cnt_dev, count_all, cap, margin_dev, tau_dev, thr_dev, stream
+        lib.dhr_debug_select_merge.argtypes = [C.c_int32] * 8 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
     if hasattr(lib, "dhr_debug_query_seating"):    # (A/B libraries built from older sources lack it)
         lib.dhr_debug_query_seating.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dhr_debug_gemm_time.argtypes = [C.c_void_p, C.POINTER(QueryBatch), C.c_int32, C.POINTER(C.c_double),

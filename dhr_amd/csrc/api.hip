@@ -680,6 +680,37 @@ extern "C" int dhr_debug_refine_bounds(dhr_index* ix, const dhr_query_batch* qb,
   return DHR_OK;
 } DHR_CATCH_STATUS
 
+// Test hook: ONE call of the running top-k merge, as every search ends its phases -- a SelectArgs filled from the arguments and handed to
+// launch_select: the launcher, the dispatch by kp (select_kernel<4> / <16>, select_big_kernel, launch_select_global) and the LDS attribute
+// handling are those of the searches.  No index handle: the lists, the keys and the thresholds are the caller's DEVICE arrays.  Whatever the
+// kernels assume silently about their arguments is refused here, before a device is touched (the contract: SelectArgs, dhr_internal.h).
+extern "C" int dhr_debug_select_merge(int32_t device, int32_t n_queries, int32_t k, int32_t k_keep, int32_t kp, int32_t kps, int32_t sort_n, int32_t monotone,
+                                      uint64_t* topk_keys_dev, const uint64_t* in_keys_dev, int64_t ld_keys, const uint32_t* cnt_dev, uint32_t count_all,
+                                      uint32_t cap, const float* margin_dev, float* tau_dev, float* thr_dev, void* stream) try {
+  if (!topk_keys_dev || !in_keys_dev || !margin_dev || !tau_dev || !thr_dev) return set_error(DHR_ERR_INVALID, "null argument");
+  if (n_queries <= 0) return set_error(DHR_ERR_INVALID, "n_queries must be positive");
+  const auto pow2_in = [](int64_t v, int64_t lo, int64_t hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; };
+  if (!pow2_in(kp, 64, 1 << 20)) return set_error(DHR_ERR_INVALID, "kp must be a power of two in [64, 1048576]");
+  if (!pow2_in(kps, 64, kp)) return set_error(DHR_ERR_INVALID, "kps must be a power of two in [64, kp]");
+  const int keep = k_keep ? k_keep : k;
+  if (k < 1 || k > keep || keep > kps) return set_error(DHR_ERR_INVALID, "need 1 <= k <= k_keep <= kps");
+  if (kp <= 4096 && (int64_t)sort_n - kps < 64) return set_error(DHR_ERR_INVALID, "sort_n leaves fewer than 64 keys of LDS behind the list");
+  if (kp <= 4096 && (int64_t)sort_n * 8 + 16 > 160 * 1024) return set_error(DHR_ERR_INVALID, "sort_n keys do not fit the LDS (sort_n*8 + 16 B > 160 KiB)");
+  if (kp > 16384 && n_queries > 65535) return set_error(DHR_ERR_INVALID, "more than 65535 queries on the global-memory path");
+  if (ld_keys < 0) return set_error(DHR_ERR_INVALID, "ld_keys must not be negative");
+  if (!cnt_dev && (int64_t)count_all > ld_keys) return set_error(DHR_ERR_INVALID, "count_all exceeds ld_keys");
+  if ((int64_t)cap > ld_keys) return set_error(DHR_ERR_INVALID, "cap exceeds ld_keys");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  SelectArgs sel{};
+  sel.topk_keys = topk_keys_dev; sel.in_keys = in_keys_dev; sel.ld_keys = ld_keys; sel.cnt = cnt_dev; sel.count_all = count_all; sel.cap = cap;
+  sel.k = k; sel.kp = kp; sel.sort_n = sort_n; sel.k_keep = k_keep; sel.kps = kps; sel.monotone = monotone ? 1 : 0;
+  sel.margin = margin_dev; sel.tau = tau_dev; sel.thr = thr_dev; sel.n_queries = n_queries;
+  HIP_TRY(launch_select(sel, s));             // (a failure of the global path, e.g. hipCUB's 2^31 item limit, comes back as DHR_ERR_HIP)
+  HIP_TRY(hipStreamSynchronize(s));
+  return DHR_OK;
+} DHR_CATCH_STATUS
+
 // Test hook: how the main pass of the latest dhr_search on this handle seated its batch (seating.h).  Returns 1 and fills the host arrays ([n_slots] each,
 // n_slots = the batch's query count rounded up to 256; any may be null) when that pass ran seated: slot -> query, query -> slot, the bound-list
 // lengths of the sampled run the order was taken from, the slot-ordered threshold mirror and the thresholds themselves as the pass left them.

@@ -244,6 +244,20 @@ struct RescoreArgs {
   int split;                  // set by launch_rescore: 1 = rescore_fast_kernel was launched beside this kernel and takes the batches it can
 };
 
+// One merge of new keys into the running top-k lists: launch_select picks select_kernel<4> (kp <= 1024), select_kernel<16> (kp <= 4096),
+// select_big_kernel (kp <= 16384) or launch_select_global by kp; all four keep ONE contract, pinned key by key by tests/test_select_merge.py
+// through dhr_debug_select_merge.  With keep = k_keep ? k_keep : k, and keys unique across the list and the input (the row is part of the key):
+//   * slots [0, keep) hold the keep greatest of {non-zero keys of the list} + {the first min(cnt[q], cap) input keys; count_all without cnt},
+//     descending, zeros behind the last key;
+//   * tau = the score of slot k - 1, -inf while that slot is empty -- also when an earlier call at a lower rank left a finite tau there (main_pass
+//     switches from the sampled rank to k with monotone = 0) --; with monotone, max(old tau, that).  thr = tau - margin in fp32.  The stale value
+//     would not lose a row either: every reader of thr takes a maximum with a threshold that was at least as high when the rank switched
+//     (raise_thr_main_kernel over thr_hat, which main_pass / adopt_thresholds start from that very thr), and nothing reads tau behind the switch;
+//   * slots [keep, kp) are nobody's input: emit_kernel, keys_to_rows_kernel, count_ge_kernel and emit_scores_kernel read [0, k), verify_kernel slot
+//     k - 1, raise_thr_rank_kernel / raise_thr_main_kernel slot r - 1 < k.  What a path leaves there differs and is only ever read back by that
+//     same path (kp is fixed per workspace): select_kernel zeroes [keep, kps) and leaves [kps, kp) alone, select_big_kernel leaves [keep, kp)
+//     alone, the global path sorts all kp slots and so keeps the next-best keys there (it ignores k_keep and kps).  On every path no slot at or
+//     past keep holds a key greater than slot keep - 1, given a list that came in sorted with nothing but zeros past keep.
 struct SelectArgs {
   uint64_t* topk_keys;        // [Q_pad][kp] sorted descending, 0 = empty
   const uint64_t* in_keys;    // [Q_pad][ld_keys]

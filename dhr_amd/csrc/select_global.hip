@@ -25,8 +25,8 @@ __global__ void sg_take_kernel(SelectArgs p, int64_t L, const uint64_t* __restri
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.kp; j += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t key = sorted[(int64_t)q * L + j];
     topk[j] = key;
-    if (j == p.k - 1 && key != 0ull) {
-      float t = ordered_f32((uint32_t)(key >> 32));
+    if (j == p.k - 1) {                       // an empty slot k-1 publishes -inf, as the LDS and in-place kernels do (SelectArgs, dhr_internal.h)
+      float t = key ? ordered_f32((uint32_t)(key >> 32)) : -INFINITY;
       if (p.monotone) t = fmaxf(t, p.tau[q]);
       p.tau[q] = t;
       p.thr[q] = t - p.margin[q];

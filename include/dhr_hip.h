@@ -677,6 +677,31 @@ int dhr_debug_query_margins(dhr_index* index, const dhr_query_batch* queries, fl
 int dhr_debug_refine_bounds(dhr_index* index, const dhr_query_batch* queries, int64_t row_lo, int64_t row_hi, const float* tau_host,
                             int32_t flat, float* out_u_dev, float* out_u2_dev, float* out_thr_host, float* out_unit_host, void* stream);
 
+/* Debug/test hook: one call of the running top-k merge that ends every phase of every search (dhr_search, the staged and sharded calls,
+ * dhr_search_rerank, dhr_search_excluding, dhr_pq_search), through the searches' own launcher: kp <= 1024 and kp <= 4096 run the two LDS
+ * kernels, kp <= 16384 the in-place kernel, larger kp the global-memory sort.  No index handle; every array is DEVICE memory of `device`.
+ *   topk_keys_dev  [n_queries][kp] u64, in/out: the running lists, sorted descending.  A key is (order-preserving image of the fp32 score) << 32 |
+ *                  (0xFFFFFFFF - row): the image flips the sign bit of a non-negative score and every bit of a negative one, and both zeros
+ *                  map to 0x80000000, so keys order by score descending, then row ascending.  0 is an empty slot.  Keys must be unique across
+ *                  a query's list and its input.  k_keep' = k_keep ? k_keep : k slots are kept; the global-memory path reads the slots behind
+ *                  them as part of the list, so they come in as zeros or as an earlier call left them.
+ *   in_keys_dev    [n_queries][ld_keys] u64: query q brings its first min(cnt_dev[q], cap) keys, or its first count_all where cnt_dev is null.
+ *   kps            the prefix of the list the LDS kernels hold (a power of two, k_keep' <= kps <= kp); sort_n: their LDS budget in keys
+ *                  (2 kp in the searches, 4 kp in dhr_pq_search; ignored for kp > 4096).
+ *   margin_dev, tau_dev (in/out), thr_dev (out)   [n_queries] fp32.
+ * After the call slots [0, k_keep') hold the k_keep' greatest keys of list and input, descending, zeros behind the last; tau is the score of slot
+ * k - 1, or -inf while that slot is empty, on every path; with monotone != 0 it is max(old tau, that); thr = tau - margin in fp32.  Slots
+ * [k_keep', kp) are defined per path and never hold a key greater than slot k_keep' - 1: the LDS kernels zero [k_keep', kps) and leave [kps, kp)
+ * as it was, the in-place kernel leaves [k_keep', kp) as it was, the global-memory path keeps the next-best keys there (no reader of a search
+ * looks past slot k - 1).  DHR_ERR_INVALID, before the device is touched, for: a null pointer (cnt_dev may be null); n_queries <= 0; kp not a
+ * power of two in [64, 2^20]; kps not a power of two in [64, kp]; not 1 <= k <= k_keep' <= kps; for kp <= 4096, sort_n - kps < 64 or
+ * sort_n * 8 + 16 bytes beyond the 160 KiB of LDS a workgroup may take; for kp > 16384, n_queries > 65535; ld_keys < 0; count_all > ld_keys
+ * without cnt_dev; cap > ld_keys.  A failure of the global-memory path (more than 2^31 - 1 keys in one sort) returns DHR_ERR_HIP.  Synchronises
+ * the stream.  (tests/test_select_merge.py) */
+int dhr_debug_select_merge(int32_t device, int32_t n_queries, int32_t k, int32_t k_keep, int32_t kp, int32_t kps, int32_t sort_n, int32_t monotone,
+                           uint64_t* topk_keys_dev, const uint64_t* in_keys_dev, int64_t ld_keys, const uint32_t* cnt_dev, uint32_t count_all,
+                           uint32_t cap, const float* margin_dev, float* tau_dev, float* thr_dev, void* stream);
+
 /* Debug/test hook: how the main pass of the latest dhr_search on this handle seated its batch (DHR_PARAM_SEAT_QUERIES).  Returns 1 and fills the
  * HOST arrays ([n_slots] each, n_slots = that batch's query count rounded up to 256; any may be null) when the pass ran seated: slot -> query,
  * query -> slot, the per-query bound-list lengths of the sampled run the order was taken from, the slot-ordered threshold mirror and the

@@ -16,6 +16,9 @@ dropped under "_dropped" (ALLOWED_TO_DIFFER says what may stand there: pq_assign
 The bad-argument exits of dhr_debug_refine_bounds came with that hook: its null-handle exit in the first file, the exits behind the handle check (bad
 range, null output, a range deeper than the candidate lists, a batch or an index without a refine level) as (status, error text) in the second.
 
+The bad-argument exits of dhr_debug_select_merge came with that hook too, all in the first file: it takes no handle and refuses whatever its
+kernels assume silently before it touches the device.
+
 The index holds gated values that are integer multiples of 2^-6 (make_golden_index_build.py: the two-bucket deal of the default image is then the
 same in every build), so the bound scores and the filter margins are pinned too."""
 import contextlib
@@ -96,6 +99,11 @@ def _check_cases(lib, _lib):
         if host:
             return lambda: lib.dhr_merge_topk_lists_host(nq, n_lists, list_len, scores, rows, k, outs, outr)
         return lambda: lib.dhr_merge_topk_lists(0, nq, n_lists, list_len, scores, rows, k, outs, outr, None)
+
+    def select(nq=2, k=10, k_keep=0, kp=64, kps=64, sort_n=128, monotone=0, topk=pout, keys=pout, ld_keys=64, cnt=pout, count_all=0, cap=64, margin=p32,
+               tau=p32, thr=pout):
+        # (host pointers stand in for the device arrays: every case is refused before the device is touched)
+        return lambda: lib.dhr_debug_select_merge(0, nq, k, k_keep, kp, kps, sort_n, monotone, topk, keys, ld_keys, cnt, count_all, cap, margin, tau, thr, None)
 
     def ranks(fn):
         def call():
@@ -237,6 +245,37 @@ def _check_cases(lib, _lib):
         "debug_bound_scores_null_handle": lambda: lib.dhr_debug_bound_scores(None, qbp, 0, 1, pout, None),
         "debug_query_margins_null_handle": lambda: lib.dhr_debug_query_margins(None, qbp, pout, None),
         "debug_refine_bounds_null_handle": lambda: lib.dhr_debug_refine_bounds(None, qbp, 0, 1, None, 0, pout, pout, None, None, None),
+        # ---- dhr_debug_select_merge, in the order of its checks (no handle: everything the kernels assume silently is refused up front)
+        "select_merge_null_list": select(topk=None),
+        "select_merge_null_keys": select(keys=None),
+        "select_merge_null_margin": select(margin=None),
+        "select_merge_null_tau": select(tau=None),
+        "select_merge_null_thr": select(thr=None),
+        "select_merge_null_beats_n_queries": select(thr=None, nq=0),
+        "select_merge_n_queries_zero": select(nq=0),
+        "select_merge_n_queries_beats_kp": select(nq=-1, kp=100),
+        "select_merge_kp_not_a_power_of_two": select(kp=96),
+        "select_merge_kp_below_64": select(kp=32, kps=32, sort_n=128),
+        "select_merge_kp_above_2_20": select(kp=1 << 21, kps=64),
+        "select_merge_kp_beats_kps": select(kp=96, kps=96),
+        "select_merge_kps_not_a_power_of_two": select(kp=1024, kps=96, sort_n=2048),
+        "select_merge_kps_below_64": select(kp=1024, kps=32, sort_n=2048),
+        "select_merge_kps_above_kp": select(kp=64, kps=128, sort_n=256),
+        "select_merge_k_zero": select(k=0),
+        "select_merge_k_above_k_keep": select(k=10, k_keep=9),
+        "select_merge_k_keep_negative": select(k=10, k_keep=-1),
+        "select_merge_k_keep_above_kps": select(k=10, k_keep=129, kp=1024, kps=128, sort_n=2048),
+        "select_merge_k_above_kps_without_k_keep": select(k=65, kp=128, kps=64, sort_n=256),
+        "select_merge_rank_beats_sort_n": select(k=0, sort_n=64),
+        "select_merge_sort_n_leaves_under_64": select(kp=64, kps=64, sort_n=127),
+        "select_merge_sort_n_beyond_the_lds": select(k=10, kp=4096, kps=4096, sort_n=5 * 4096, ld_keys=64),
+        "select_merge_sort_n_beats_ld_keys": select(sort_n=64, ld_keys=-1),
+        "select_merge_ld_keys_negative": select(ld_keys=-1, cap=0),
+        "select_merge_count_all_above_ld_keys": select(cnt=None, count_all=65),
+        "select_merge_count_all_beats_cap": select(cnt=None, count_all=65, cap=65),
+        "select_merge_cap_above_ld_keys": select(cap=65),
+        "select_merge_cap_above_ld_keys_without_cnt": select(cnt=None, count_all=64, cap=65),
+        "select_merge_too_many_queries_for_the_global_path": select(nq=65536, kp=32768, kps=32768),
         "debug_gemm_time_null_handle": lambda: lib.dhr_debug_gemm_time(None, qbp, 1, C.byref(err), None, None),
         "sample_rank_null_handle": lambda: [lib.dhr_search_sample_rank(None, 10)],
         "union_rank_null_handle": lambda: [lib.dhr_search_union_rank(None, 10)],

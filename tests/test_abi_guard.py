@@ -51,6 +51,7 @@ def test_every_extern_c_definition_is_a_function_try_block():
     hdr = open(os.path.join(ROOT, "include", "dhr_hip.h")).read()
     declared = set(re.findall(r"\b(dhr_[a-z0-9_]+)\s*\(", hdr)) - {"dhr_allgather_fn"}
     assert declared <= names | {"dhr_host_shard"}, declared - names
+    assert {"dhr_debug_refine_bounds", "dhr_debug_select_merge"} <= declared & names       # the handle-less test hooks are entry points like any other
     for path, name, rest in defs:
         if name in NOTHROW:
             continue

@@ -36,7 +36,7 @@ def test_the_table_covers_every_touched_entry_point(pinned):
     for prefix in ("densify_", "pq_train_", "pq_train_plain_", "pq_encode_", "pq_encode_plain_", "pq_decode_", "pq_decode_plain_", "pq_create_", "pq_search_null",
                    "pq_adc_scores_null", "pq_last_scan_null", "merge_", "merge_host_", "lists_", "lists_host_", "search_mid_", "search_begin_rest_", "search_finish_",
                    "search_begin_", "search_pre_", "search_async_mid_", "search_async_pre_", "search_async_begin_rest_", "search_async_begin_", "search_async_finish_",
-                   "sample_rank_", "union_rank_", "mid_ranks_", "pre_ranks_"):
+                   "sample_rank_", "union_rank_", "mid_ranks_", "pre_ranks_", "select_merge_"):
         assert any(name.startswith(prefix) for name in exits), prefix
     assert sum("beats" in name for name in exits) >= 20
     statuses = {v[0] for name, v in exits.items() if len(v) == 2 and isinstance(v[1], str)}
